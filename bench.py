@@ -6,7 +6,7 @@ build the network input, net(cond), net(uncond), CFG, conditioning-frame replace
 121x704x1280 video latent [1,16,16,88,160] (56 320 tokens), random-init Cosmos-7B weights (28 blocks x 4096, 32 heads),
 synthetic conditions of SURVEY.md 8d. Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N>1 = context parallel over the 16 latent frames, one process per GPU over RCCL. Both launch forms work:
   * under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`): RANK / WORLD_SIZE come
@@ -14,7 +14,8 @@ N>1 = context parallel over the 16 latent frames, one process per GPU over RCCL.
   * bare (`python bench.py --gpus N`): no WORLD_SIZE in the environment -> this process re-executes itself under
     `torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (self_launch_argv), the counterpart of the
     reference's `torchrun --nproc_per_node=N gen3c_single_image.py --num_gpus N` (gen3c_single_image.py:248-255).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0. --dump-outputs DIR writes the latent the last timed step returned (float32 .npy, fixed inputs) for
+output-for-output comparison of two builds.
 """
 from __future__ import annotations
 
@@ -302,6 +303,28 @@ def tokenizer_sample_index(numel: int, n: int = 8192, seed: int = 11):
     return torch.from_numpy(np.random.RandomState(seed).randint(0, numel, size=n).astype(np.int64))
 
 
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays: dict, budget: int = DUMP_BUDGET_BYTES) -> dict:
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float32. An output larger than its share of `budget` is replaced by the values
+    at a fixed seeded sample of flat positions (the same positions for the same shape in every run). Returns {name: what was written}."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = budget // max(1, len(arrays)) // 4  # float32 elements per array
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > share:
+            idx = torch.from_numpy(np.sort(np.random.RandomState(0).choice(n, size=share, replace=False))).to(flat.device)
+            flat = flat[idx]
+        arr = flat.float().cpu().numpy()
+        np.save(out_dir / f"{name}.npy", arr if n > share else arr.reshape(tuple(t.shape)))
+        info[name] = dict(shape=list(t.shape), dtype=str(t.dtype).replace("torch.", ""), saved="all" if n <= share else f"{share} sampled of {n}")
+    return info
+
+
 def stage_rooflines(dev):
     """The chunk's other two stages at the benchmark size, timed once each with hipEvents (rank 0, N = 1, outside the timed region):
     tokenizer encode / decode of one 121x704x1280 clip (algorithmic work SURVEY.md 8a-a15: 35.7 / 61.3 TFLOP, MFMA-bound) and the cache
@@ -465,17 +488,28 @@ def self_launch_argv(n_gpus: int, argv: list, port: int | None = None) -> list:
             "--master-port", str(port), str(Path(__file__).resolve()), *argv]
 
 
+def _at_least(lo: int):
+    def parse(v: str) -> int:
+        n = int(v)
+        if n < lo:
+            raise argparse.ArgumentTypeError(f"must be >= {lo}")
+        return n
+    return parse
+
+
 def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
-    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--steps", type=_at_least(1), default=2, help="timed denoise steps (the step index wraps around the 35-step schedule)")
+    ap.add_argument("--warmup", type=_at_least(0), default=1)
     ap.add_argument("--blocks", type=int, default=28, help="(debug only) number of DiT blocks; anything but 28 is not the benchmark")
     ap.add_argument("--latent", type=str, default="16,88,160", help="(debug only) latent T,H,W")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timers", action="store_true",
                     help="A/B: no hipEvent pairs around the launches of the timed region (the roofline / roofline_gemm entries are then null)")
     ap.add_argument("--no-extras", action="store_true", help="skip the tokenizer / renderer roofline entries (a few seconds after the timed region)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the latent the last one returned as DIR/latent.npy (float32; N > 1: gathered over the ranks)")
     ap.add_argument("--cp-config", type=str, default="auto",
                     help="N > 1: 'auto' = time the context-parallel configurations (head groups x attention kernel x collective schedule) on a few blocks "
                          "before the warm-up and run on the fastest; or 'G,kernel,schedule' e.g. '4,auto,gather_first' to pin one")
@@ -647,6 +681,7 @@ class RunGuard:
         import threading
         self.rank, self.world, self.base = rank, world, dict(base_line)
         self.phase, self.deadline, self.progress, self.done = "init", time.monotonic() + PHASE_DEADLINE_S["init"], {}, False
+        self.seconds = PHASE_DEADLINE_S["init"]
         self.store, self._lock, self._emitted = None, threading.Lock(), False
         try:
             from torch.distributed.distributed_c10d import _get_default_store
@@ -662,7 +697,8 @@ class RunGuard:
         self._t.start()
 
     def enter(self, phase: str, seconds: float | None = None):
-        self.phase, self.deadline = phase, time.monotonic() + (seconds if seconds is not None else PHASE_DEADLINE_S.get(phase, 300))
+        self.seconds = seconds if seconds is not None else PHASE_DEADLINE_S.get(phase, 300)
+        self.phase, self.deadline = phase, time.monotonic() + self.seconds
 
     def finish(self):
         self.done = True
@@ -703,7 +739,7 @@ class RunGuard:
             except Exception:
                 pass
             if err is None and time.monotonic() > self.deadline:
-                err = f"rank {self.rank}: phase '{self.phase}' exceeded its {PHASE_DEADLINE_S.get(self.phase, 300)} s deadline (hung collective?)"
+                err = f"rank {self.rank}: phase '{self.phase}' exceeded its {self.seconds:g} s deadline (hung collective?)"
             if err is not None and not self.done:
                 if self.rank == 0:
                     self._emit(err)
@@ -764,9 +800,9 @@ def main():
     # N > 1: from here on the run ends with a JSON line whatever happens (exception on any rank, hung collective) - see RunGuard
     guard = RunGuard(rank, world, base_line) if world > 1 else None
 
-    def guarded(phase, fn):
+    def guarded(phase, fn, seconds=None):
         if guard is not None:
-            guard.enter(phase)
+            guard.enter(phase, seconds)
         try:
             return fn()
         except Exception as e:  # noqa: BLE001 - whatever it is, the line must still be printed
@@ -840,11 +876,12 @@ def main():
         guard.progress.update(cp=cp_info)
 
     state = dict(xt=xt, step_id=0)
+    n_sched = len(den.scheduler.timesteps)  # step i runs schedule step i % n_sched: any --steps / --warmup
 
     def timed_region():
         xt_, step_id = state["xt"], 0
         for _ in range(args.warmup):
-            xt_ = den.denoise_step(xt_, step_id, cond, uncond, 1.0, 0.001, 1)
+            xt_ = den.denoise_step(xt_, step_id % n_sched, cond, uncond, 1.0, 0.001, 1)
             step_id += 1
         barrier()
         ops.enable_kernel_timers(not args.no_kernel_timers)
@@ -855,7 +892,7 @@ def main():
             raise RuntimeError(f"injected failure in the timed region on rank {rank}")
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            xt_ = den.denoise_step(xt_, step_id, cond, uncond, 1.0, 0.001, 1)
+            xt_ = den.denoise_step(xt_, step_id % n_sched, cond, uncond, 1.0, 0.001, 1)
             step_id += 1
         torch.cuda.synchronize()
         own = time.perf_counter() - t0  # this rank's own time to finish its K steps (before the closing barrier): load imbalance shows here
@@ -864,7 +901,8 @@ def main():
         state["xt"] = xt_
         return elapsed_, own
 
-    elapsed, own_elapsed = guarded("timed", timed_region)
+    # the deadline grows with the number of steps (a step of the full workload takes seconds on one GPU)
+    elapsed, own_elapsed = guarded("timed", timed_region, PHASE_DEADLINE_S["timed"] + 30 * (args.warmup + args.steps))
     xt = state["xt"]
     timers = ops.collected_kernel_timers()
     ops.enable_kernel_timers(False)
@@ -881,6 +919,15 @@ def main():
             return [round(float(t.item()), 2) for t in allr]
         rank_ms = guarded("timed", reduce_times)
     elapsed = float(tmax.item())
+
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: the next latent (N > 1: every rank's shard, concatenated along T)
+        from gen3c_amd.parallel import cat_outputs_cp
+        latent = guarded("dump", lambda: cat_outputs_cp(xt, 2, net.cp_group)) if world > 1 else xt
+        if rank == 0:
+            dumped = dict(dir=str(args.dump_outputs), arrays=dump_outputs(args.dump_outputs, {"latent": latent}))
+        del latent
 
     # ---- dominant kernel: self-attention flash-attention forward, timed live with hipEvents on its launch stream
     if guard is not None:
@@ -957,6 +1004,8 @@ def main():
         })
         if cp_info is not None:
             out["cp"] = cp_info
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         out["outside_timed_region"] = ("in-run rocprofv3 PMC passes, tokenizer / renderer entries, the wall-clock-per-video entry and the CPU baseline legs: rank 0, after the timed loop, "
                                        + ("run in this invocation (n_gpus = 1)" if world == 1 else "SKIPPED in this invocation (they run at n_gpus = 1 only)"))
         if not args.no_extras and world == 1 and roof is not None and "w4b" in roof["kernel"] and (N_tok, args.blocks) == (56320, 28):

@@ -286,3 +286,33 @@ def test_pmc_csv_parser_means_the_named_kernels_counter():
     assert bench.parse_pmc_csv(text, "flash_attn_fwd_w4b", "FETCH_SIZE") == (7.5e6, 2)
     assert bench.parse_pmc_csv(text, "flash_attn_fwd_w4b", "WRITE_SIZE") == (4.0e6, 1)
     assert bench.parse_pmc_csv(text, "gemm", "FETCH_SIZE") == (None, 0)
+
+
+def test_parser_steps_and_dump_outputs():
+    import bench
+    a = bench.build_parser().parse_args(["--steps", "50", "--warmup", "0", "--dump-outputs", "out"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (50, 0, "out")
+    assert bench.build_parser().parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.build_parser().parse_args(bad)
+
+
+def test_dump_outputs_float32_within_budget(tmp_path):
+    """--dump-outputs: a small output is written whole in float32 with its shape; one over its share of the budget is replaced by a fixed
+    seeded sample of its values (the same positions in every run), so the files stay within the budget."""
+    import numpy as np
+    import torch
+    import bench
+    x = torch.randn(2, 3, 5, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    info = bench.dump_outputs(tmp_path / "a", {"latent": x})
+    got = np.load(tmp_path / "a" / "latent.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 3, 5) and np.array_equal(got, x.float().numpy())
+    assert info["latent"] == dict(shape=[2, 3, 5], dtype="bfloat16", saved="all")
+    big = torch.arange(10000, dtype=torch.float32)
+    for d in ("b", "c"):
+        bench.dump_outputs(tmp_path / d, {"latent": big, "other": big[:10]}, budget=4096)
+    s1, s2 = np.load(tmp_path / "b" / "latent.npy"), np.load(tmp_path / "c" / "latent.npy")
+    assert s1.dtype == np.float32 and s1.shape == (512,) and np.array_equal(s1, s2) and len(np.unique(s1)) == 512
+    assert np.array_equal(np.load(tmp_path / "b" / "other.npy"), big[:10].numpy())
+    assert sum(f.stat().st_size - 128 for f in (tmp_path / "b").iterdir()) <= 4096
