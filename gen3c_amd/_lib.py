@@ -39,6 +39,8 @@ SIGNATURES = {
                                i32, f32, vp],
     "g3_flash_attn_fwd_ex_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, vp, vp, vp, i64, i64, i64, i32, i32, i32,
                                   i32, i32, f32, i32, vp],
+    "g3_flash_attn_fwd_carry_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, i32, i32, vp, vp, vp, vp, vp, i64, i64,
+                                     i64, i32, i32, i32, i32, i32, f32, i32, vp],
     "g3_flash_attn_kernel_name_ex": [i32, i32, i32, i32, i32],
     "g3_attn_merge_partials_bf16": [vp, vp, i32, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, vp],
     "g3_transpose_v_bf16": [vp, i64, vp, i64, i32, i32, i32, i32, vp],

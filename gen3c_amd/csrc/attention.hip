@@ -64,6 +64,15 @@ struct AttnParams {
     // then never makes the separate read + write pass of g3_qk_rmsnorm_rope_bf16.
     const bf16_t* q_norm_w;
     float q_norm_eps;
+    // CP form (flash_attn_fwd_w4b_carry_kernel, flash_attn_fwd_v3_kernel<CTX | 2>; g3_flash_attn_fwd_carry_bf16): the plain kernels never read these.
+    //  - carry_o / carry_lse: an earlier state of the same rows (normalised fp32 with the o strides, log2-domain LSE [B][H][Sq] as O32 / LSE above);
+    //    nullptr = none. The epilogue folds it into this launch's part and writes O (bf16) or a new O32 + LSE (carry_o may alias O32).
+    //  - kv_skip_begin / kv_skip_len (multiples of 64; 0 < begin < Skv or len == 0): logical key j is read at physical key j + (j >= begin ? len : 0),
+    //    in K and in V^T; kv_skip_vt_bytes = the same jump inside a V^T row (len * 2, or whole segments: len / vt_seg_len * vt_seg_stride * 2).
+    const float* carry_o;
+    const float* carry_lse;
+    int kv_skip_begin, kv_skip_len;
+    uint32_t kv_skip_vt_bytes;
 };
 
 G3_DEVICE int k_off(int row, int chunk) { return row * HD + ((chunk ^ (row & 15)) << 3); }          // [64][128]
@@ -521,8 +530,11 @@ constexpr int SGB_VALU = 0x2, SGB_MFMA = 0x8, SGB_DSR = 0x100, SGB_TRANS = 0x400
 #ifndef G3_AB_ATTN_ABLATE
 #define G3_AB_ATTN_ABLATE 0
 #endif
+// CTX & 2: the CP form (carry-in + skipped key range, AttnParams::carry_o / kv_skip_*; g3_flash_attn_fwd_carry_bf16): instantiations 2 / 3 only,
+// the plain kernels (0 / 1) compile without it.
 template <int CTX, int QA, int QBV, bool FOLD, bool MW = false, int MW_RD = 4, int MW_KREGS = 8>
 __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnParams p) {
+    constexpr bool CP = (CTX & 2) != 0;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
     bf16_t* sV = sK + 2 * KVB * HD;                     // [2][128][64]
@@ -583,9 +595,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
     const uint32_t k_lane = (uint32_t)k_row0 * k_row_bytes + (uint32_t)k_src_chunk * 16u;   // + kv0 * k_row_bytes (+ 32 rows)
     const uint32_t v_lane0 = (uint32_t)v_row0 * (uint32_t)p.vt_row * 2u + (uint32_t)v_src_chunk * 16u;  // + kv0 * 2
     const uint32_t v_lane1 = v_lane0 + 64u * (uint32_t)p.vt_row * 2u;
-    const uint32_t k_last = (uint32_t)(Skv - 1) * k_row_bytes + (uint32_t)k_src_chunk * 16u;  // clamp target for ragged tails
+    auto kv_phys = [&](int kv) -> int {  // CP: physical key of logical key kv (AttnParams::kv_skip_begin / kv_skip_len)
+        if constexpr (CP) return kv + (kv >= p.kv_skip_begin ? p.kv_skip_len : 0);
+        else return kv;
+    };
+    const uint32_t k_last = (uint32_t)kv_phys(Skv - 1) * k_row_bytes + (uint32_t)k_src_chunk * 16u;  // clamp target for ragged tails
     auto dma_k = [&](int kv0, int slot) {
         bf16_t* d = sK + slot * KVB * HD + wave * 64 * 8;
+        kv0 = kv_phys(kv0);  // (a 64-key tile never straddles the skip)
         uint32_t o0 = k_lane + (uint32_t)kv0 * k_row_bytes;
         uint32_t o1 = o0 + 32u * k_row_bytes;
         o0 = min(o0, k_last | 0u);  // rows past S_kv-1 re-read the last row (their scores are masked); chunk bits agree
@@ -598,6 +615,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
     const uint32_t seg_len = (uint32_t)p.vt_seg_len, seg_bytes = (uint32_t)p.vt_seg_stride * 2u;
     auto dma_v = [&](int kv0, int slot) {
         bf16_t* d = sV + slot * HD * KVB + wave * 64 * 8;
+        kv0 = kv_phys(kv0);
         uint32_t tile_off = (uint32_t)kv0 * 2u;
         if (seg_len) {  // a 64-key tile never straddles segments (seg_len % 64 == 0)
             const uint32_t sg = (uint32_t)kv0 / seg_len;
@@ -904,6 +922,54 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
         m_run = m_new;
     }
     const float inv = o_scale / l_tot;
+    if constexpr (CP) {  // carry-in: as in the w4b kernel (attention_w4b.hpp) - out = (w_c o_c + w_k acc / l) / (w_c + w_k); all 16 loads first
+        const int q_ld = q_ok ? q_idx : p.Sq - 1;
+        const int64_t li = ((int64_t)blockIdx.z * p.n_heads + blockIdx.y) * p.Sq + q_ld;
+        const int64_t o_hb = (int64_t)blockIdx.z * p.o_batch + (int64_t)blockIdx.y * p.o_head;
+        const float lse_k = m_run + __builtin_amdgcn_logf(l_tot);
+        f32x4 oc[4][4];
+        float lse_c = -INFINITY;
+        if (p.carry_lse) {  // wave-uniform; rows past Sq read row Sq - 1 and store nothing
+            const float* crow = p.carry_o + o_hb + (int64_t)q_ld * p.o_row + 4 * g;
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) oc[d][q4] = *reinterpret_cast<const f32x4*>(crow + 32 * d + 8 * q4);
+            lse_c = p.carry_lse[li];
+        } else {
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) oc[d][q4] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const float mm = fmaxf(lse_c, lse_k);
+        const float wc = __builtin_amdgcn_exp2f(lse_c - mm), wk = __builtin_amdgcn_exp2f(lse_k - mm);
+        const float rs = 1.0f / (wc + wk);
+        const float fc = wc * rs, fk = (wk * rs) * inv;
+        const bool use_c = fc > 0.f;
+        if (q_ok) {
+            const int64_t ro = o_hb + (int64_t)q_idx * p.o_row;
+#pragma unroll
+            for (int d = 0; d < 4; ++d)
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const int64_t off = ro + 32 * d + 8 * q4 + 4 * g;
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = (use_c ? fc * oc[d][q4][e] : 0.f) + fk * accO[d][4 * q4 + e];
+                    if (p.O32) {
+                        *reinterpret_cast<f32x4*>(p.O32 + off) = o;
+                    } else {
+                        bf16x4 ob;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) ob[e] = f32_to_bf16(o[e]);
+                        *reinterpret_cast<bf16x4*>(p.O + off) = ob;
+                    }
+                }
+            if (p.O32 && g == 0) p.LSE[li] = mm + __builtin_amdgcn_logf(wc + wk);
+        }
+        return;
+    }
     if (p.O32) {  // split-KV part: fp32 normalised partial + log-sum-exp (wave-uniform branch, after the loop)
         if (q_ok) {
             float* orow = p.O32 + (int64_t)blockIdx.z * p.o_batch + (int64_t)blockIdx.y * p.o_head + (int64_t)q_idx * p.o_row;
@@ -937,7 +1003,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 
 #include "attention_w4.hpp"
-#include "attention_w4b.hpp"
+#define W4B_CP 0
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_kernel
+#undef W4B_CP
+#define W4B_CP 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_carry_kernel: the same kernel with the CP form (carry-in + skipped key range)
+#undef W4B_CP
 
 }  // namespace
 
@@ -977,7 +1048,8 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
                              int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                              int64_t vt_seg_stride, void* o, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H,
                              int head_dim, float softmax_scale, void* stream, int variant_req = 0, float* o_partial = nullptr, float* lse = nullptr, int kv_dense = 0,
-                             const void* q_norm_w = nullptr, float q_norm_eps = 0.f) {
+                             const void* q_norm_w = nullptr, float q_norm_eps = 0.f, bool cp_form = false, const float* carry_o = nullptr,
+                             const float* carry_lse = nullptr, int kv_skip_begin = 0, int kv_skip_len = 0, uint32_t kv_skip_vt_bytes = 0) {
     if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: null operand");
     if ((o_partial != nullptr) != (lse != nullptr)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial and lse go together");
     if (o_partial && (((uintptr_t)o_partial & 15) || ((uintptr_t)lse & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: misaligned o_partial / lse");
@@ -988,8 +1060,9 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: strides must keep 16-byte (q,k,vt) / 8-byte (o) alignment");
     if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) || ((uintptr_t)o & 7))
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: misaligned pointer");
-    const int kv_span = vt_seg_len > 0 ? vt_seg_len : Skv;  // keys addressed through one vt_row
-    if (vt_seg_len < 0 || (vt_seg_len > 0 && ((vt_seg_len % KVB) || (Skv % vt_seg_len) || (vt_seg_stride & 7) || vt_seg_stride <= 0)))
+    const int skv_phys = Skv + kv_skip_len;  // keys the operands span (CP form: the skipped range included)
+    const int kv_span = vt_seg_len > 0 ? vt_seg_len : skv_phys;  // keys addressed through one vt_row
+    if (vt_seg_len < 0 || (vt_seg_len > 0 && ((vt_seg_len % KVB) || (skv_phys % vt_seg_len) || (vt_seg_stride & 7) || vt_seg_stride <= 0)))
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: segments must be a multiple of 64 keys, tile S_kv exactly, 16-byte aligned stride");
     if (vt_row < ((kv_span + 7) & ~7)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: vt leading dim %lld < keys per row rounded to 8", (long long)vt_row);
     AttnParams p;
@@ -1009,6 +1082,8 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         if (kd < Skv) p.kv_dense = kd;
     }
     p.q_norm_w = (const bf16_t*)q_norm_w; p.q_norm_eps = q_norm_eps;
+    p.carry_o = carry_o; p.carry_lse = carry_lse;
+    p.kv_skip_begin = kv_skip_begin; p.kv_skip_len = kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
     if (q_norm_w && ((uintptr_t)q_norm_w & 15)) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: misaligned q_norm_weight");
     const size_t smem = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
     static bool attr_set[64] = {};  // per device: hipFuncSetAttribute applies to the current device only
@@ -1017,6 +1092,9 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     // else 4. Explicit values are kept for A/B runs and tests: 1 non-pipelined, 2 software-pipelined, 3 LDS-DMA + pinned interleave,
     // 4 = 3 + folded scale/max on long contexts, 5-8 test forms of 4, 9 = w4 (one wave per SIMD), 10 = w4b, 11 = w4b + cross-barrier prefetch.
     int variant = attn_resolve_variant(Sq, Skv, B, H, variant_req);
+    if (cp_form && variant != 4 && variant != 11)
+        return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: the carry / key-skip form exists for the 8-wave (4) and one-wave-per-SIMD (11) kernels only "
+                                        "(variant %d chosen; 11 needs S_kv %% 64 == 0)", variant);
     if (o_partial && variant == 9) variant = 4;  // w4 (ragged S_kv) has no partial epilogue: the 8-wave kernel takes ragged tiles too
     if ((p.kv_dense || p.q_norm_w) && (variant < 3 || variant >= 9)) variant = 4;  // the zero-tail epilogue and the Q norm live in the v3 kernels
     if (variant >= 3 && vt_row < ((kv_span + KVB - 1) / KVB) * KVB) variant = 2;  // (also 6-8)  // v3 reads the whole last V^T tile unguarded
@@ -1024,16 +1102,22 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         // v3 addresses its K / V^T LDS-DMA sources with 32-bit BYTE offsets from the per-(batch, head) base pointers: the largest
         // offsets it forms must stay below 4 GiB, otherwise they wrap silently (e.g. a strided K view of a fused [S*B, 3*4096]
         // QKV buffer at B >= 4). Out-of-range problems run on v2 (64-bit addressing) when V^T is not segmented.
-        const uint64_t k_max = (uint64_t)(Skv - 1 + 2 * KVB) * (uint64_t)k_row * 2u + 256u;
-        const uint64_t n_seg = vt_seg_len > 0 ? (uint64_t)(Skv / vt_seg_len) : 1u;
+        const uint64_t k_max = (uint64_t)(skv_phys - 1 + 2 * KVB) * (uint64_t)k_row * 2u + 256u;
+        const uint64_t n_seg = vt_seg_len > 0 ? (uint64_t)(skv_phys / vt_seg_len) : 1u;
         const uint64_t v_max = (uint64_t)(HD - 1) * (uint64_t)vt_row * 2u + (n_seg - 1) * (uint64_t)vt_seg_stride * 2u + ((uint64_t)kv_span + KVB) * 2u + 256u;
         if (k_max > 0xFFFFFFFFull || v_max > 0xFFFFFFFFull) {
+            if (cp_form)
+                return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: K / V^T span (skipped keys included) exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes); "
+                                                "the 64-bit-addressing kernel has no carry form", (unsigned long long)k_max, (unsigned long long)v_max);
             if (vt_seg_len > 0)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: K / V^T span exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes)",
                                     (unsigned long long)k_max, (unsigned long long)v_max);
             variant = 2;
         }
     }
+    if (cp_form && variant < 3)
+        return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: V^T leading dimension %lld below ceil64 of the keys it spans forces the 64-bit-addressing kernel, which has "
+                                        "no carry form", (long long)vt_row);
     if (vt_seg_len > 0 && variant < 3)
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: segmented V^T is implemented by the default (v3) kernel only");
     if (o_partial && variant < 3)
@@ -1046,7 +1130,9 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     {
       std::lock_guard<std::mutex> attr_lock(attr_mu);
       if (!attr_set[dev_id]) {
-        const void* fns[16] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<false>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<true>),
+        const void* fns[19] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
+                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<2, 6, 8, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<3, 6, 8, false>),
+                               reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<false>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_kernel<1>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v2_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_v2_kernel<1>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false>),
@@ -1054,7 +1140,7 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false, true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<1>)};
-        for (int i = 0; i < 16; ++i) {
+        for (int i = 0; i < 19; ++i) {
             hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
@@ -1069,7 +1155,8 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         p.grid_q = (int)grid4.x; p.n_hb = H * B; p.n_heads = H;
         p.xcd_heads = (g3_opt_attn_xcd_heads && (H * B) % 8 == 0) ? 1 : 0;
         if (p.xcd_heads) grid4 = dim3(grid4.x * H * B, 1, 1);
-        if (variant == 11) hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        if (cp_form) hipLaunchKernelGGL(flash_attn_fwd_w4b_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        else if (variant == 11) hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<false>, grid4, dim3(W4_THREADS), smem, st, p);
         return g3_check_launch("g3_flash_attn_fwd_bf16");
     }
@@ -1081,7 +1168,8 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     }
 #define G3_LAUNCH_ATTN(KERNEL0, KERNEL1) do { if (long_ctx) hipLaunchKernelGGL(KERNEL0, grid, dim3(NTHREADS), smem, st, p); else hipLaunchKernelGGL(KERNEL1, grid, dim3(NTHREADS), smem, st, p); } while (0)
     // VALU quotas (6, 8) per MFMA measured best of {(4,4), (5,6), (6,8)} (profiles/r1_v5_attn_quota_ab.txt)
-    if (variant == 1) G3_LAUNCH_ATTN(flash_attn_fwd_kernel<0>, flash_attn_fwd_kernel<1>);
+    if (cp_form) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<2, 6, 8, true>), (flash_attn_fwd_v3_kernel<3, 6, 8, false>));  // variant 4's kernels
+    else if (variant == 1) G3_LAUNCH_ATTN(flash_attn_fwd_kernel<0>, flash_attn_fwd_kernel<1>);
     else if (variant == 2) G3_LAUNCH_ATTN(flash_attn_fwd_v2_kernel<0>, flash_attn_fwd_v2_kernel<1>);
     else if (variant == 3) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, false>), (flash_attn_fwd_v3_kernel<1, 6, 8, false>));
     else if (variant == 5) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, true>), (flash_attn_fwd_v3_kernel<1, 6, 8, true>));  // tests: folded arithmetic at every length
@@ -1132,6 +1220,46 @@ extern "C" int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q
     if (o_partial && ((o_row & 3) || (o_batch & 3) || (o_head & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial strides must be multiples of 4");
     return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
                              o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse);
+}
+
+/* ---- carry-in state + skipped key range (context parallelism without a merge pass) --------------------------------------------------------- */
+extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                            int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                            int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                            const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
+                                            int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
+                                            void* stream) {
+    const char* fn = "g3_flash_attn_fwd_carry_bf16";
+    if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "%s: variant %d out of range", fn, variant);
+    if (o && o_partial) return g3_set_error(G3_ERR_ARG, "%s: pass either o (bf16 result) or o_partial + lse, not both", fn);
+    if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
+    if ((o_row & 3) || (o_batch & 3) || (o_head & 3)) return g3_set_error(G3_ERR_ARG, "%s: o / o_partial / carry_o strides must be multiples of 4", fn);
+    if ((carry_o != nullptr) != (carry_lse != nullptr)) return g3_set_error(G3_ERR_ARG, "%s: carry_o and carry_lse go together", fn);
+    if (carry_o && (((uintptr_t)carry_o & 15) || ((uintptr_t)carry_lse & 3))) return g3_set_error(G3_ERR_ARG, "%s: misaligned carry_o (16 B) / carry_lse (4 B)", fn);
+    if (Skv <= 0) return g3_set_error(G3_ERR_ARG, "%s: bad shape", fn);
+    if (kv_skip_begin < 0 || kv_skip_len < 0 || (kv_skip_begin % KVB) || (kv_skip_len % KVB) || kv_skip_begin > Skv)
+        return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must be multiples of 64 with 0 <= begin <= S_kv %d", fn, kv_skip_begin, kv_skip_len, Skv);
+    if (vt_seg_len > 0 && kv_skip_len > 0 && ((kv_skip_begin % vt_seg_len) || (kv_skip_len % vt_seg_len)))
+        return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must cover whole V^T segments of %d keys", fn, kv_skip_begin, kv_skip_len, vt_seg_len);
+    if ((int64_t)Skv + kv_skip_len > 0x7fffffff) return g3_set_error(G3_ERR_ARG, "%s: S_kv + kv_skip_len overflows", fn);
+    const int64_t vt_jump = vt_seg_len > 0 ? (int64_t)(kv_skip_len / vt_seg_len) * vt_seg_stride : (int64_t)kv_skip_len;  // elements
+    if (vt_seg_len > 0 && vt_seg_stride <= 0) return g3_set_error(G3_ERR_ARG, "%s: vt_seg_stride must be positive", fn);
+    // a skip at either end is a different base (begin 0) or nothing at all (begin == S_kv): the kernels only ever see 0 < begin < S_kv
+    if (vt_seg_len == 0 && vt_row < ((int64_t)Skv + kv_skip_len + KVB - 1) / KVB * KVB)  // (the kernels read whole V^T tiles unguarded)
+        return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S_kv + kv_skip_len) forces the 64-bit-addressing kernel, which has no carry form", fn,
+                            (long long)vt_row);
+    if (kv_skip_len > 0 && kv_skip_begin == 0) {  // (the row stride stays; only the keys addressed inside a row move)
+        k = (const bf16_t*)k + (int64_t)kv_skip_len * k_row;
+        vt = (const bf16_t*)vt + vt_jump;
+        kv_skip_len = 0;
+    }
+    if (kv_skip_begin == Skv) kv_skip_len = 0;
+    if (kv_skip_len == 0) kv_skip_begin = 0;
+    const int64_t vt_jump_bytes = (vt_seg_len > 0 ? (int64_t)(kv_skip_len / vt_seg_len) * vt_seg_stride : (int64_t)kv_skip_len) * 2;
+    if (vt_jump_bytes > 0xFFFFFFFFll) return g3_set_error(G3_ERR_ARG, "%s: the skipped V^T range exceeds the kernel's 32-bit byte offsets", fn);
+    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
+                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse, 0, nullptr, 0.f, true, carry_o,
+                             carry_lse, kv_skip_begin, kv_skip_len, (uint32_t)vt_jump_bytes);
 }
 
 namespace {

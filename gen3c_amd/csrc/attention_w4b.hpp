@@ -1,4 +1,5 @@
-// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace.
+// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace - twice: W4B_CP 0 defines the helpers and
+// flash_attn_fwd_w4b_kernel, W4B_CP 1 flash_attn_fwd_w4b_carry_kernel (the CP form, see below; the plain kernel compiles without it).
 //
 // w4b: the one-wave-per-SIMD self-attention kernel (see attention_w4.hpp for the why) with the issue stream of a tile trimmed to what the
 // SIMD can hide under its MFMAs (MI355X_MICROARCH.md: <= 5 single-issue instructions per 32-cycle MFMA gap at one wave per SIMD; the w4
@@ -20,7 +21,12 @@
 // on the odd steps of region A and the LDS-DMA pieces sit on the even steps (one per 4 MFMAs); with a 1-D grid every XCD works through its
 // own (batch, head) pairs. PMC: 39.9 (XB) vs 41.1 cycles per 32-cycle MFMA.
 // Limits (checked by the launcher, which otherwise runs w4): S_kv a multiple of 64.
+// CP (flash_attn_fwd_w4b_carry_kernel, g3_flash_attn_fwd_carry_bf16 only): a skipped key range - logical
+// 64-key tile t is read at physical tile t + (t >= skip tile ? skipped tiles : 0), one more term in the K tile address and one more jump in the
+// V^T walk - and a carry-in state of the same rows folded in by the epilogue. The tile loop itself is the plain kernel's.
 
+#ifndef G3_ATTENTION_W4B_HELPERS
+#define G3_ATTENTION_W4B_HELPERS
 #define W4B_RING_AGPRS "a192","a193","a194","a195","a196","a197","a198","a199","a200","a201","a202","a203","a204","a205","a206","a207","a208","a209","a210","a211","a212","a213","a214","a215","a216","a217","a218","a219","a220","a221","a222","a223","a224","a225","a226","a227","a228","a229","a230","a231","a232","a233","a234","a235","a236","a237","a238","a239","a240","a241","a242","a243","a244","a245","a246","a247","a248","a249","a250","a251","a252","a253","a254","a255"
 #define W4B_OWNED W4_OWNED_AGPRS, W4B_RING_AGPRS
 constexpr int W4B_RING0 = 192;  // fragment n of a tile (K fragments 0..15, V^T fragments 16..31) sits in a[192 + 4 (n & 15) : +3]
@@ -196,8 +202,16 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 
 // XB: the tile barrier sits in the P.V region (before step 10) and steps 10..15 read the NEXT tile's first six K fragments across it, so a tile
 // starts with its operands in the ring; the four pair units that covered the head reads move into region A as half units.
+#endif  // G3_ATTENTION_W4B_HELPERS
+
+#if W4B_CP
+#define W4B_KERNEL flash_attn_fwd_w4b_carry_kernel
+#else
+#define W4B_KERNEL flash_attn_fwd_w4b_kernel
+#endif
 template <bool XB>
-__global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnParams p) {
+__global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
+    constexpr bool CP = W4B_CP;
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
     bf16_t* sV = sK + 2 * KVB * HD;                     // [2][128][64]
@@ -225,6 +239,23 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
     float* o32_base = p.O32;
     float* lse_base = p.LSE;
     asm volatile("" : "+s"(o32_base), "+s"(lse_base));
+    // CP: the carry-in state and the skipped key range, fetched here for the same reason. skip_t0 = first skipped logical tile (the launcher
+    // guarantees 0 < kv_skip_begin < S_kv, or kv_skip_len == 0), skip_nt = skipped tiles, v_skip = bytes the V^T walk jumps at tile skip_t0
+    const float* carry_o = nullptr;
+    const float* carry_lse = nullptr;
+    uint32_t skip_t0 = 0u, skip_nt = 0u, v_skip = 0u;
+    if constexpr (CP) {
+        carry_o = p.carry_o;
+        carry_lse = p.carry_lse;
+        skip_t0 = (uint32_t)p.kv_skip_begin / KVB;
+        skip_nt = (uint32_t)p.kv_skip_len / KVB;
+        v_skip = p.kv_skip_vt_bytes;
+        asm volatile("" : "+s"(carry_o), "+s"(carry_lse), "+s"(skip_t0), "+s"(skip_nt), "+s"(v_skip));
+    }
+    auto k_tile = [&](uint32_t t) -> uint32_t {  // physical K tile of logical tile t
+        if constexpr (CP) return t + (t >= skip_t0 ? skip_nt : 0u);
+        else return t;
+    };
 
     // ---- Q fragments of both halves, pre-multiplied by scale * log2(e), into a[128:191]; O accumulators a[0:127] = 0 (as w4)
     static_for<0, 16>([&](auto fc) {
@@ -297,7 +328,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
     // ---- prologue: K(0), V(0) (and K(1)) by LDS-DMA; scores of tile 0 with C = 0, then made relative to their exact row maximum
     dma_tile_builtin(Kbytes, dma_off, sK);
     dma_tile_builtin(Vbytes, dma_off + 4, sV);
-    if (nt > 1) dma_tile_builtin(Kbytes + k_tile_bytes, dma_off, sK + KVB * HD);
+    if (nt > 1) dma_tile_builtin(Kbytes + k_tile(1u) * k_tile_bytes, dma_off, sK + KVB * HD);
     G3_JITTER(wave, blockIdx.x + 5);
     lds_dma_publish_barrier();
     G3_JITTER(wave + 2, blockIdx.x);
@@ -345,6 +376,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
     }
     // wave-uniform source state of the in-stream LDS-DMA: V^T tile t+1 (byte offset inside a row, tiles left in its segment)
     uint32_t v_off_next = v_tile_off(KVB);
+    if constexpr (CP) v_off_next += skip_t0 == 1u ? v_skip : 0u;
     const uint32_t seg_tiles = seg_len ? seg_len / KVB : 0x7fffffffu;
     uint32_t v_seg_pos = seg_len ? (1u % seg_tiles) : 1u;  // position of tile 1 inside its segment
     const uint32_t v_seg_jump = seg_len ? seg_bytes - seg_len * 2u : 0u;
@@ -427,7 +459,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
         //      LDS-DMA piece I in steps 0..7: K(t+2) pieces 0..3 -> slot of K(t), V^T(t+1) pieces 0..3 -> slot of V^T(t-1)
         if constexpr (has_next) {
             const int t2 = min(t + 2, nt - 1);  // past the end: re-read the last tile (its slot is not consumed any more)
-            const char* kbase = Kbytes + (uint32_t)t2 * k_tile_bytes;
+            const char* kbase = Kbytes + k_tile((uint32_t)t2) * k_tile_bytes;
             const char* vbase = Vbytes + v_off_next;
             static_for<0, 16>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
@@ -460,6 +492,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
             const bool wrap = (v_seg_pos + 1u == seg_tiles);
             v_off_next += wrap ? (uint32_t)(KVB * 2) + v_seg_jump : (uint32_t)(KVB * 2);
             v_seg_pos = wrap ? 0u : v_seg_pos + 1u;
+            if constexpr (CP) v_off_next += (uint32_t)(t + 2) == skip_t0 ? v_skip : 0u;  // whole segments: the position inside one is unchanged
         }
         G3_JITTER(wave + blockIdx.x + 3, t);
         // ---- region B: O_h^T += V^T(t).P_h^T, step I: slice s = I >> 2, output block d = I & 3; pair units 20 + I in steps 0..11; the row-max
@@ -546,6 +579,56 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
         const float extra = (XB && h == 0) ? (pe[0][0] + pe[0][1]) + (pe[1][0] + pe[1][1]) : 0.f;
         const float inv = 1.0f / xor32_sum(((psum[h][0] + psum[h][1]) + (psum[h][2] + psum[h][3])) + extra);
         const int q_idx = qblk * W4_BQ + wave * 64 + 32 * h + l31;
+        if constexpr (CP) {
+            // carry-in: this launch's part is (acc / l, lse_k = m + log2 l), the earlier state of the same rows (carry_o normalised, carry_lse;
+            // -inf = no earlier keys) is folded in: out = (w_c o_c + w_k acc / l) / (w_c + w_k), w_x = 2^(lse_x - max(lse_c, lse_k)), fp32.
+            // carry_o may alias o_partial: each lane reads all its elements of the half before it writes any. The half's 16 loads go out together,
+            // unconditionally (rows past Sq read row Sq - 1 and store nothing), through a global-address-space pointer.
+            const bool q_ok = q_idx < p.Sq;
+            const int q_ld = q_ok ? q_idx : p.Sq - 1;
+            const int64_t li = ((int64_t)batch * p.n_heads + head) * p.Sq + q_ld;
+            const int64_t ro = (int64_t)batch * p.o_batch + (int64_t)head * p.o_head + (int64_t)q_idx * p.o_row;
+            const int64_t ro_ld = (int64_t)batch * p.o_batch + (int64_t)head * p.o_head + (int64_t)q_ld * p.o_row;
+            const float lse_k = m_run[h] - __builtin_amdgcn_logf(inv);
+            f32x4 oc[16];
+            float lse_c = -INFINITY;
+            if (carry_lse) {  // wave-uniform
+                using gf32x4 = const __attribute__((address_space(1))) f32x4;
+                gf32x4* crow = (gf32x4*)(carry_o + ro_ld + 4 * g);
+#pragma unroll
+                for (int c = 0; c < 16; ++c) oc[c] = crow[(32 * (c >> 2) + 8 * (c & 3)) / 4];
+                lse_c = ((const __attribute__((address_space(1))) float*)carry_lse)[li];
+            } else {
+#pragma unroll
+                for (int c = 0; c < 16; ++c) oc[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+            const float mm = fmaxf(lse_c, lse_k);
+            const float wc = __builtin_amdgcn_exp2f(lse_c - mm), wk = __builtin_amdgcn_exp2f(lse_k - mm);
+            const float rs = 1.0f / (wc + wk);
+            const float fc = wc * rs, fk = (wk * rs) * inv;  // lse_c = -inf: fc = 0, fk = inv (the plain result, bit for bit)
+            const bool use_c = fc > 0.f;                     // (an absent carry contributes nothing, whatever carry_o holds)
+            static_for<0, 16>([&](auto cc) {
+                constexpr int c = decltype(cc)::value, d = c >> 2, q4 = c & 3;
+                constexpr int R = 16 * (4 * h + d) + 4 * q4;
+                const int64_t off = ro + 32 * d + 8 * q4 + 4 * g;
+                float o[4];
+                o[0] = (use_c ? fc * oc[c][0] : 0.f) + fk * w4_acc_read<R + 0>();
+                o[1] = (use_c ? fc * oc[c][1] : 0.f) + fk * w4_acc_read<R + 1>();
+                o[2] = (use_c ? fc * oc[c][2] : 0.f) + fk * w4_acc_read<R + 2>();
+                o[3] = (use_c ? fc * oc[c][3] : 0.f) + fk * w4_acc_read<R + 3>();
+                if (!q_ok) return;
+                if (o32_base) {
+                    *reinterpret_cast<f32x4*>(o32_base + off) = f32x4{o[0], o[1], o[2], o[3]};
+                } else {
+                    bf16x4 ob;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ob[e] = f32_to_bf16(o[e]);
+                    *reinterpret_cast<bf16x4*>(p.O + off) = ob;
+                }
+            });
+            if (o32_base && g == 0 && q_ok) lse_base[li] = mm + __builtin_amdgcn_logf(wc + wk);
+            return;
+        }
         if (o32_base) {  // split-KV part (see AttnParams): fp32 normalised partial + log-sum-exp in the log2 domain
             float* prow = o32_base + (int64_t)batch * p.o_batch + (int64_t)head * p.o_head + (int64_t)q_idx * p.o_row;
             static_for<0, 16>([&](auto cc) {
@@ -574,3 +657,4 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4b_kernel(AttnP
         });
     });
 }
+#undef W4B_KERNEL

@@ -332,6 +332,11 @@ class VideoExtendGeneralDIT(nn.Module):
             self._cp_attn.configure(head_groups=int(g_), kernel=kern_, schedule=sched_)
         self._tables.clear()
 
+    def _cp_fused_qkv(self) -> bool:
+        """Context parallel with a schedule whose first phase runs on this rank's own K / V shard (local_first, local_carry): Q, K and V come
+        from ONE fused projection. gather_first projects K | V ahead of Q so that their exchange flies under the Q projection."""
+        return self._cp_attn is not None and self._cp_attn.schedule in ("local_first", "local_carry")
+
     def disable_context_parallel(self):
         self.cp_group = None
         self.cp_size = None
@@ -483,8 +488,8 @@ class VideoExtendGeneralDIT(nn.Module):
                 pos["full"] = (pe_sum / pos["norm"].reshape(Tp, Hp, Wp, 1)).reshape(S, D).contiguous()
                 del pe_sum
             h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
-            if self._cp_attn is not None and self._cp_attn.schedule == "local_first":
-                # local_first starts every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
+            if self._cp_fused_qkv():
+                # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
                 # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
                 # (M = 14 080) a separate N = 4096 Q projection is 3.44 rounds of 256 x 256 tiles on 256 workgroups and ran at 77 % of its cp = 1
                 # rate (profiles/r6_cp_rank_shapes.txt); inside the N = 12 288 projection the same tiles are part of 10.3 rounds.

@@ -236,7 +236,7 @@ def transpose_v(v: torch.Tensor, S: int, B: int, H: int, out: Optional[torch.Ten
 
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int,
                out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False, kv_dense: int = 0,
-               q_norm_weight: Optional[torch.Tensor] = None, q_norm_eps: float = 1e-6):
+               q_norm_weight: Optional[torch.Tensor] = None, q_norm_eps: float = 1e-6, carry=None, kv_skip=None):
     """q: [Sq*B, H*128], k: [Skv*B, H*128] (rows (s,b), b fastest), vt: [B, H, 128, ldvt] -> out [Sq*B, H*128].
     vt may also be 5-D [n_seg, B, H, 128, ld_seg]: V^T in key segments of Skv / n_seg keys each (a rank-major all-gather of
     per-rank V^T shards, see g3_flash_attn_fwd_kvseg_bf16).
@@ -244,7 +244,14 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv:
     partial=True: the keys are only PART of the rows' keys - returns (o_part fp32 [Sq*B, H*128], lse fp32 [B, H, Sq]) for attn_merge.
     kv_dense (0 < kv_dense < Skv): the CALLER guarantees all-zero K rows and V^T columns for keys [kv_dense, Skv) (zero-padded context tokens): they enter the
     softmax in closed form instead of through the tile loop; q_norm_weight ([128] bf16): q is the raw projection and its per-head RMSNorm runs inside the
-    kernel's Q load (both: g3_cross_attn_fwd_bf16)."""
+    kernel's Q load (both: g3_cross_attn_fwd_bf16).
+    carry=(o_part, lse): an earlier state of the same rows (what partial=True returns; o_part with the strides of this call's output) that the
+    kernel folds into its own part - the result is the attention over both key sets, as bf16 or (partial=True) as a new (o_part, lse), so launches
+    chain without a merge pass. kv_skip=(begin, len), multiples of 64: k / vt hold Skv + len keys and keys [begin, begin + len) are skipped (Skv
+    counts the attended keys). partial=True may then also take `out`, an fp32 view to write the part into (it may be carry's o_part).
+    Either one (or partial=True with `out`) runs g3_flash_attn_fwd_carry_bf16 - variant 0, 4 or 11 only; no fallback."""
+    if carry is not None or kv_skip is not None or (partial and out is not None):
+        return _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip)
     qr, qw, ldq = _rowmajor2d(q, "q")
     kr, kw, ldk = _rowmajor2d(k, "k")
     assert qr == Sq * B and kr == Skv * B and qw == H * 128 and kw == H * 128
@@ -293,6 +300,62 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv:
         _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial,
                                                       kernel=lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode()), timer))
     return (o_part, lse) if partial else out
+
+
+def _carry_kernel_name(plain: str) -> str:
+    """The CP instantiation g3_flash_attn_fwd_carry_bf16 launches in place of the plain kernel the launcher resolves to (attention.hip)."""
+    return {"flash_attn_fwd_w4b_kernel<true>": "flash_attn_fwd_w4b_carry_kernel<true>",
+            "flash_attn_fwd_v3_kernel<0, 6, 8, true>": "flash_attn_fwd_v3_kernel<2, 6, 8, true>",
+            "flash_attn_fwd_v3_kernel<1, 6, 8, false>": "flash_attn_fwd_v3_kernel<3, 6, 8, false>"}.get(plain, plain)
+
+
+def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip):
+    skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
+    skv_all = Skv + skip_len
+    qr, qw, ldq = _rowmajor2d(q, "q")
+    kr, kw, ldk = _rowmajor2d(k, "k")
+    assert qr == Sq * B and kr == skv_all * B and qw == H * 128 and kw == H * 128
+    assert vt.is_contiguous() and vt.dim() in (4, 5) and tuple(vt.shape[-4:-1]) == (B, H, 128)
+    ldvt = vt.shape[-1]
+    n_seg = vt.shape[0] if vt.dim() == 5 else 0
+    if n_seg:
+        assert skv_all % n_seg == 0
+    lse = None
+    if partial:
+        if out is None:
+            out = torch.empty((Sq * B, H * 128), dtype=torch.float32, device=q.device)
+        assert out.dtype == torch.float32, "partial=True writes fp32"
+        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+    elif out is None:
+        out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=q.device)
+    orows, ow, ldo = _rowmajor2d(out, "out")
+    assert (orows, ow) == (Sq * B, H * 128)
+    co = cl = 0
+    if carry is not None:
+        o_c, l_c = carry
+        if o_c.dtype != torch.float32 or o_c.shape != (Sq * B, H * 128) or o_c.stride() != out.stride():
+            raise ValueError(f"flash_attn: carry o_part must be fp32 {(Sq * B, H * 128)} with the output's strides {out.stride()} "
+                             f"(got {o_c.dtype} {tuple(o_c.shape)} {o_c.stride()})")
+        if l_c.dtype != torch.float32 or l_c.shape != (B, H, Sq) or not l_c.is_contiguous():
+            raise ValueError(f"flash_attn: carry lse must be contiguous fp32 {(B, H, Sq)}")
+        co, cl = _dev(o_c, "carry_o", torch.float32), _dev(l_c, "carry_lse", torch.float32)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(128)
+    lib = _lib.load()
+    timer = None
+    if _KERNEL_TIMERS is not None:
+        timer = HipTimer()
+        timer.start()
+    _lib.check(lib.g3_flash_attn_fwd_carry_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt,
+                                                128 * ldvt, skv_all // n_seg if n_seg else 0, B * H * 128 * ldvt if n_seg else 0, skip_begin, skip_len, co, cl,
+                                                0 if partial else _dev(out, "out"), _dev(out, "o_part", torch.float32) if partial else 0,
+                                                _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128,
+                                                float(softmax_scale), int(variant), _stream()), "g3_flash_attn_fwd_carry_bf16")
+    if timer is not None:
+        timer.stop()
+        _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, carry=carry is not None, kv_skip=skip_len,
+                                                      kernel=_carry_kernel_name(lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())), timer))
+    return (out, lse) if partial else out
 
 
 def attn_merge(parts, Sq: int, B: int, H: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:

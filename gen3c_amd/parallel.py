@@ -180,7 +180,7 @@ def run_jobs_round_robin(jobs: List[Callable[[], torch.Tensor]], group, shape, d
 # context-parallel self-attention
 # ------------------------------------------------------------------------------------------------------------------
 ATTN_KERNELS = {"auto": None, "w4b": 11, "wave8": 4}  # per-call kernel choice of g3_flash_attn_fwd_ex_bf16 ("auto": the even-fill rule below)
-CP_SCHEDULES = ("gather_first", "local_first")
+CP_SCHEDULES = ("gather_first", "local_first", "local_carry")
 
 
 def _default_backend():
@@ -191,6 +191,8 @@ def _default_backend():
         attention=lambda q, k, vt, Sq, Skv, B, H, out, variant=0: ops.flash_attn(q, k, vt, Sq, Skv, B, H, out=out, variant=variant),
         attention_partial=lambda q, k, vt, Sq, Skv, B, H, variant=0: ops.flash_attn(q, k, vt, Sq, Skv, B, H, variant=variant, partial=True),
         merge=lambda parts, Sq, B, H, out: ops.attn_merge(parts, Sq, B, H, out=out),
+        attention_carry=lambda q, k, vt, Sq, Skv, B, H, out=None, carry=None, kv_skip=None, partial=False, variant=0: ops.flash_attn(
+            q, k, vt, Sq, Skv, B, H, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
         timer=ops.HipTimer,
     )
 
@@ -207,6 +209,10 @@ class ContextParallelAttention:
     local shard at once): every head group first runs over THIS rank's K / V shard - no collective is waited for - and returns a normalised
     fp32 partial + log-sum-exp; the remote keys (ranks before / after this one in the gathered buffers) follow as the groups' exchanges land,
     and g3_attn_merge_partials_bf16 combines the parts. Costs one fp32 round trip of the group's output per part; hides the first exchange.
+    schedule "local_carry": the same phase 1 (an fp32 partial + log-sum-exp over the own shard, no wait), then ONE launch per group over every
+    remote key - an interior rank skips its own block inside the gathered buffers (g3_flash_attn_fwd_carry_bf16's kv_skip) - that carries the
+    phase-1 state in and writes bf16 straight into the group's columns of the output: two launches per group, no merge pass. Needs a backend with
+    "attention_carry", segmented V^T and world > 1; otherwise it runs as "local_first" (and `effective` says so).
 
     kernel: "auto" (the one-wave-per-SIMD kernel when the groups' workgroups together fill the 256 CUs evenly, else the 8-wave kernel), "w4b",
     "wave8" - passed PER CALL through the C ABI; no process-wide option is touched (launches go out on two streams).
@@ -307,11 +313,16 @@ class ContextParallelAttention:
         assert all(len(w) == 6 and w[2] is not None and w[3] is not None for w in pending["works"]), "gathered K / V buffers must stay referenced"
         works = pending["works"]
         variant = self._variant(S_local, S_all, B, pending["H"]) if q.is_cuda else 0
-        local_first = self.schedule == "local_first" and pending["segmented"] and self.world > 1 and "attention_partial" in be
+        split = pending["segmented"] and self.world > 1
+        local_carry = self.schedule == "local_carry" and split and "attention_carry" in be
+        local_first = not local_carry and self.schedule in ("local_first", "local_carry") and split and "attention_partial" in be
         # what this layer actually runs (a requested "local_first" needs segmented V^T and a split-KV backend; a forced one-wave kernel needs
         # S_all % 64 == 0): read by bench.py so that its autotune table and `cp.chosen` never label a fallback with the requested name
-        self.effective = dict(schedule="local_first" if local_first else "gather_first", kernel={11: "w4b", 4: "wave8"}.get(variant, str(variant)),
-                              head_groups=len(pending["works"]))
+        self.effective = dict(schedule="local_carry" if local_carry else "local_first" if local_first else "gather_first",
+                              kernel={11: "w4b", 4: "wave8"}.get(variant, str(variant)), head_groups=len(pending["works"]))
+        # local_carry: the phase-1 partials of all groups in ONE fp32 buffer shaped like `out`, so that a group's partial has the strides of its
+        # bf16 output columns (the carry-in form reads carry_o with the output's strides). Allocated here, before q_ready, like `out`.
+        o32 = torch.empty((pending["rows"], pending["H"] * 128), dtype=torch.float32, device=q.device) if local_carry else None
         two_streams = q.is_cuda and len(works) >= 2
         main = side = q_ready = None
         if two_streams:
@@ -327,7 +338,16 @@ class ContextParallelAttention:
 
         try:
             local_parts = {}
-            if local_first:
+            if local_carry:
+                # phase 1: as local_first, into this group's columns of o32 (the partial stays referenced by local_parts until phase 2 is enqueued)
+                for g, (wk, wv, kf, vf, ks, vs) in enumerate(works):
+                    st, ctx = on_stream(g)
+                    with ctx:
+                        if two_streams and st is side:
+                            st.wait_event(q_ready)
+                        local_parts[g] = be["attention_carry"](q[:, g * W:(g + 1) * W], ks, vs.reshape(1, B, Hg, 128, -1), S_local, S_local, B, Hg,
+                                                               out=o32[:, g * W:(g + 1) * W], partial=True, variant=variant)
+            elif local_first:
                 # phase 1: every group over this rank's own shard - the packed K columns and the local V^T that were SENT (w[4], w[5]); no wait
                 for g, (wk, wv, kf, vf, ks, vs) in enumerate(works):
                     st, ctx = on_stream(g)
@@ -338,11 +358,24 @@ class ContextParallelAttention:
             for g, (wk, wv, kf, vf, _ks, _vs) in enumerate(works):
                 st, ctx = on_stream(g)
                 with ctx:
-                    if two_streams and st is side and not local_first:
+                    if two_streams and st is side and not (local_first or local_carry):
                         st.wait_event(q_ready)
                     self._wait(be, g, wk, wv)
                     qg, og = q[:, g * W:(g + 1) * W], out[:, g * W:(g + 1) * W]
-                    if local_first:
+                    if local_carry:
+                        # phase 2: every remote key in one launch that resumes from the phase-1 state. Rank 0 / the last rank: the remote blocks
+                        # are contiguous (a sub-range of the gathered buffers); an interior rank skips its own block (whole V^T segments).
+                        vseg = vf.view(self.world, B, Hg, 128, -1)
+                        rows, r = pending["rows"], self.rank
+                        S_rem = (self.world - 1) * S_local
+                        if r == 0:
+                            kk, vv, skip = kf[rows:], vseg[1:], None
+                        elif r == self.world - 1:
+                            kk, vv, skip = kf[:r * rows], vseg[:r], None
+                        else:
+                            kk, vv, skip = kf, vseg, (r * S_local, S_local)
+                        be["attention_carry"](qg, kk, vv, S_local, S_rem, B, Hg, out=og, carry=local_parts[g], kv_skip=skip, variant=variant)
+                    elif local_first:
                         # phase 2: the other ranks' keys = the row blocks / V^T segments before and after this rank's in the gathered buffers
                         parts = [local_parts[g]]
                         vseg = vf.view(self.world, B, Hg, 128, -1)

@@ -122,6 +122,26 @@ int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q_batch, int
                               int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
                               int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant, void* stream);
 const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant);
+
+/* Carry-in form of g3_flash_attn_fwd_ex_bf16: a row's keys in a CHAIN of launches with no merge pass - the context-parallel schedule that
+ * TransformerEngine's CP attention runs behind attn_op.set_context_parallel_group (general_dit.py:536-541, module/attention.py:282-297) keeps
+ * a running softmax state per row; here each launch can resume from one.
+ *   carry_o / carry_lse  an earlier state of the same rows, or both NULL: carry_o fp32 normalised, addressed with the o strides (as o_partial),
+ *             carry_lse fp32 [B][H][Sq] in the log2 domain (what o_partial / lse hold). carry_lse = -inf: no earlier keys for that row. The
+ *             launch's own part (lse_k = m + log2 l) is folded in after the tile loop: M = max(lse_c, lse_k), w_x = 2^(lse_x - M),
+ *             out = (w_c o_c + w_k acc / l) / (w_c + w_k) in fp32, written as the bf16 o or as a new o_partial + lse (lse = M + log2(w_c + w_k)),
+ *             so chains of any length work. carry_o may alias o_partial (and carry_lse lse).
+ *   kv_skip_begin / kv_skip_len  multiples of 64: S_kv counts the ATTENDED keys only; logical key j is read at physical key
+ *             j + (j >= kv_skip_begin ? kv_skip_len : 0) in K and in V^T (plain or segmented: then whole segments). kv_skip_len = 0: none.
+ *             Context parallelism: an interior rank attends every remote key of the gathered buffers in one launch, skipping its own block.
+ * Kernels: variant 0 (automatic), 4 (8-wave) or 11 (one-wave-per-SIMD). G3_ERR_ARG, with nothing launched, for any other, for a problem that needs
+ * the 64-bit-addressing kernel (operands spanning more than 4 GiB, skipped keys included; V^T leading dim below ceil64 of the keys it spans), for a
+ * misaligned or out-of-range skip or one that splits a V^T segment, and for misaligned carry buffers (carry_o 16 B, carry_lse 4 B) or o strides. */
+int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                 int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
+                                 int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o, const float* carry_lse,
+                                 void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B,
+                                 int H, int head_dim, float softmax_scale, int variant, void* stream);
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);

@@ -52,13 +52,15 @@ def main():
     # both collective schedules of ContextParallelAttention, 2 head groups (alternating streams): "gather_first" = one launch per head group over
     # the gathered keys (same arithmetic per row as the non-CP call); "local_first" = own shard first, remote segments after the exchange,
     # fp32 partials merged (one extra rounding pattern: not bitwise, same tolerance)
-    for sched in ("gather_first", "local_first"):
+    # G3_CP_CHECK_SCHEDULES="local_carry" (tests/test_cp_carry_gpu.py): other schedules, same bar; the schedule that actually ran is printed
+    for sched in os.environ.get("G3_CP_CHECK_SCHEDULES", "gather_first,local_first").split(","):
         net._cp_attn.configure(head_groups=2, schedule=sched)
         part = den.denoise_step(split_inputs_cp(xt, 2, net.cp_group), 5, c, u, 1.0, 0.001, 1)
         torch.cuda.synchronize()
         rel = float((part.float() - ref).norm() / ref.norm())
         mx = float((part.float() - ref).abs().max())
-        print(f"[cp_check] rank {rank}/{world}: CP ({sched}) vs non-CP denoise step rel_l2={rel:.3e} max_abs={mx:.3e}", flush=True)
+        print(f"[cp_check] rank {rank}/{world}: CP ({sched}) vs non-CP denoise step rel_l2={rel:.3e} max_abs={mx:.3e} "
+              f"effective={net._cp_attn.effective['schedule']}", flush=True)
         good = good and rel < 5e-3 and np.isfinite(rel)
     net._cp_attn.configure(head_groups=4, schedule="gather_first")
 

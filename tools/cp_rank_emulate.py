@@ -7,6 +7,9 @@ other ranks' keys are this rank's own - irrelevant for timing). What this measur
 What it cannot: the xGMI exchange itself - the model printed at the end adds it under stated assumptions.
 
   python tools/cp_rank_emulate.py [--cps 1,2,4,8] [--steps 3] [--blocks 28] [--configs 4,auto,gather_first;4,w4b,gather_first;...] [--out gpurun_out/r6_cp_rank_shapes.json]
+
+Schedules (the third field of a config): gather_first, local_first, local_carry (own-shard partial, then ONE carry launch per head group over every remote
+key - no merge pass). The exchange model below replays each of them.
 """
 import argparse
 import json
@@ -151,9 +154,12 @@ def run_cp(cp, rank, configs, steps, blocks, dev, net):
                        ms_per_step=round(ms, 2), gathered_bytes_per_step=fr.bytes // steps, emulated_exchange_wait_ms_per_step=wait_ms, classes=table)
             results.append(res)
             a = sum(c["ms_per_step"] for c in table if c["kind"] == "attn" and c["Skv"] > 2048)
+            n_sa = sum(c["launches_per_step"] for c in table if c["kind"] == "attn" and c["Skv"] > 2048)
+            n_layers = sum(c["launches_per_step"] for c in table if c["kind"] == "attn" and c["Skv"] <= 2048)  # one cross-attention launch per layer
+            res["self_attention_launches_per_layer"] = round(n_sa / n_layers, 2) if n_layers else None
             g = sum(c["ms_per_step"] for c in table if c["kind"] == "gemm")
             print(f"cp={cp} rank={rank} cfg={cfg} eff={eff}: {ms:.1f} ms/step  (self-attn launches {a:.1f} ms [overlapping streams are summed], block GEMMs {g:.1f} ms, "
-                  f"emulated exchange wait {wait_ms})", flush=True)
+                  f"emulated exchange wait {wait_ms}; self-attention launches per layer {res['self_attention_launches_per_layer']})", flush=True)
     if cp > 1:
         net.disable_context_parallel()
     return results
@@ -165,7 +171,8 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=28)
     ap.add_argument("--rank", type=int, default=-1, help="-1: a middle rank (cp // 2)")
-    ap.add_argument("--configs", default="4,auto,gather_first;4,w4b,gather_first;2,auto,gather_first;8,auto,gather_first;4,auto,local_first;1,auto,gather_first")
+    ap.add_argument("--configs", default="4,auto,gather_first;4,w4b,gather_first;2,auto,gather_first;8,auto,gather_first;4,auto,local_first;4,auto,local_carry;"
+                                          "1,auto,gather_first")
     ap.add_argument("--out", default="gpurun_out/r6_cp_rank_shapes.json")
     args = ap.parse_args()
     torch.set_grad_enabled(False)
@@ -213,7 +220,8 @@ def main():
         # (the guide: ~153 GB/s per link peak; 375 = 35 % of 7 links' bidirectional peak - unmeasured here, hence three values). Per layer the schedule of parallel.py is
         # replayed: the G head groups' collectives go out back to back on RCCL's stream when K | V exist; gather_first: Q projection + its norm pass (q_ms), then group g's
         # attention as soon as group g's exchange has landed; local_first: every group's partial over this rank's own shard first (1 / cp of the attention, no wait), then
-        # group g's remote part once its exchange has landed. Attention wall time per layer = this run's step time minus its GEMM time minus the HBM-bound rest (the
+        # group g's remote part once its exchange has landed; local_carry: the same timeline (own-shard partials first, then ONE launch per group over every remote key
+        # once its exchange has landed, the merge pass folded into that launch's epilogue - its saving is inside the measured attention time). Attention wall time per layer = this run's step time minus its GEMM time minus the HBM-bound rest (the
         # cp = 1 rest scaled by 1 / cp) - launches on two streams overlap, so their summed durations overstate it. RCCL's own CU use while a collective is in flight is
         # NOT modelled (no second GPU here); the driver's --gpus 8 run measures all of it (bench.py `cp` object).
         base_attn = sum(c["ms_per_step"] for c in base["classes"] if c["kind"] == "attn")
@@ -240,11 +248,13 @@ def main():
                     for g_ in range(G):
                         t = max(t, (g_ + 1) * ex_g) + attn_layer / G
                     exposed = t - (q_ms + attn_layer)
-                else:
+                elif sched in ("local_first", "local_carry"):
                     t = attn_layer / cp
                     for g_ in range(G):
                         t = max(t, (g_ + 1) * ex_g) + attn_layer * (cp - 1) / cp / G
                     exposed = t - attn_layer
+                else:
+                    raise ValueError(f"exchange model: unknown schedule {sched}")
                 pred = r["ms_per_step"] + layers * exposed
                 r.setdefault("predicted", {})[str(int(bw))] = dict(exchange_ms_per_layer=round(ex_g * G, 3), exposed_ms_per_layer=round(exposed, 3), ms_per_step=round(pred, 1),
                                                                    speedup=round(base["ms_per_step"] / pred, 3))

@@ -98,6 +98,33 @@ for (Sq, Skv, H, live) in [(56320, 512, 8, 64), (1000, 512, 3, 0), (3000, 256, 2
     report(f"cross-attention form Sq={Sq} Skv={Skv} H={H} live={live} (q norm in the kernel)", a, b)
     del q, k, v, vt
 
+# ---- carry-in form (g3_flash_attn_fwd_carry_bf16: the local_carry context-parallel schedule): an interior rank's ONE launch over every remote key,
+# its own key block skipped inside the gathered buffers, the own block's fp32 partial carried in; bf16 and fp32-partial outputs
+for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)]:
+    Skv = Sl * nseg
+    q = torch.randn(Sl, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    k = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    vt = torch.stack([ops.transpose_v(v[i * Sl:(i + 1) * Sl], Sl, 1, H) for i in range(nseg)]).contiguous()
+    ld = vt.shape[-1]
+    for variant in (4, 11):
+        own_o, own_l = ops.flash_attn(q, k[rank * Sl:(rank + 1) * Sl].contiguous(), vt[rank:rank + 1].contiguous(), Sl, Sl, 1, H, partial=True, variant=variant)
+        torch.cuda.synchronize()
+        for partial in (False, True):
+            def run(lib):
+                o = torch.empty_like(q)
+                o32 = torch.empty(Sl, H * 128, device=dev, dtype=torch.float32)
+                lse = torch.empty(1, H, Sl, device=dev, dtype=torch.float32)
+                rc = lib.g3_flash_attn_fwd_carry_bf16(q.data_ptr(), H * 128, H * 128, 128, k.data_ptr(), H * 128, H * 128, 128, vt.data_ptr(), ld, H * 128 * ld, 128 * ld,
+                                                      Sl, H * 128 * ld, rank * Sl, Sl, own_o.data_ptr(), own_l.data_ptr(), None if partial else o.data_ptr(),
+                                                      o32.data_ptr() if partial else None, lse.data_ptr() if partial else None, H * 128, H * 128, 128,
+                                                      Sl, Skv - Sl, 1, H, 128, 1.0 / math.sqrt(128), variant, st)
+                assert rc == 0, lib.g3_last_error()
+                return torch.cat([o32.flatten(), lse.flatten()]) if partial else o
+            a, b = both(run)
+            report(f"carry-in form S_local={Sl} segs={nseg} rank={rank} H={H} variant={variant} {'fp32 partial' if partial else 'bf16'}", a, b)
+    del q, k, v, vt
+
 # ---- GEMM: every K-loop structure x epilogues x ragged shapes
 for (M, N, K, epi) in [(56320, 4096, 4096, 2), (7040, 12288, 4096, 0), (4096, 16384, 4096, 1), (3000, 4096, 16384, 2), (513, 264, 192, 3), (300, 520, 128, 0),
                        (256, 256, 64, 0), (8192, 12288, 4096, 0), (16384, 16384, 4096, 1), (8448, 4096, 2432, 2)]:
