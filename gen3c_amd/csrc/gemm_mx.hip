@@ -1,0 +1,304 @@
+// MXFP8 (OCP Microscaling Formats v1.0, e4m3 elements) quantisation and block GEMM for the opt-in low-precision DiT linears.
+//
+// Format (MXFP8 linears): a block is 32 consecutive elements along K of one row. Its shared exponent is
+//   X = floor(log2(amax_block)) - 8, stored as the E8M0 byte X + 127 clamped to 0..254 (all-zero block: byte 127, elements 0),
+// and every element is RNE(clamp(x / 2^X, -448, 448)) as OCP e4m3fn (not the MI300 fnuz variant). amax / 2^X lies in [256, 512), so the clamp
+// matters and no element is ever flushed to more than the format's own subnormal step.
+//
+// GEMM: C[M,N] = epi( sum_k (a 2^Xa)(w 2^Xw) ) on v_mfma_scale_f32_32x32x64_f8f6f4, which runs e4m3 operands at twice the bf16 rate and applies
+// the block scales inside the matrix core. The structure is the bf16 kernels' direct-to-LDS form (gemm.hip, gemm_bf16_nt_kernel) at the same
+// BYTES per K tile: 8 wave64 per 256 (token) x 256 (feature) tile, a K tile of 128 fp8 is a [256 rows][128 B] image per operand - byte for byte
+// the [rows][64] bf16 image of those kernels, with the same 16-byte chunk XOR swizzle - staged by global_load_lds_dwordx4 into two LDS stages,
+// plus one dword of 4 scale bytes per row and K tile (global_load_lds_dword). Weights are the MFMA's A operand, tokens its B operand, so the
+// accumulators come out in the layout gemm_epilogue.hpp's store_tile_lds takes: the epilogues (and their bf16 rounding points) are the bf16 GEMM's.
+//
+// Scaled-MFMA lane maps (32x32x64, 8-bit formats; measured with single-k probes and pinned by tests/test_mxfp8_gpu.py on exact small-integer
+// data): lane l = (r = l & 31, h = l >> 5) holds row r; operand bytes 0..15 are k = 16 h .. 16 h + 15 of the 64-deep step and bytes 16..31 are
+// k = 32 + 16 h .. 32 + 16 h + 15, so scale block 0 of the step is the low half of BOTH lane halves and block 1 the high half. The block-b scale
+// is the byte op_sel names of the scale VGPR of the lanes with h = b (row r). Each lane keeps the scale dword of its row (k blocks 4t .. 4t + 3
+// of K tile t) shifted right by 8 h, so k-step s uses op_sel byte 2 s in both lane halves.
+#include "common.hpp"
+#include "gen3c_hip.h"
+
+namespace {
+
+constexpr int BM = 256;
+constexpr int BN = 256;
+constexpr int NTHREADS = 512;
+constexpr int MX_BK = 128;   // fp8 elements (= bytes) per K tile
+constexpr int MX_BLOCK = 32;  // elements per scale block
+
+#include "gemm_epilogue.hpp"
+
+typedef int i32x8 __attribute__((ext_vector_type(8)));
+
+// ---------------------------------------------------------------------------------------------------------------
+// Quantisation
+// ---------------------------------------------------------------------------------------------------------------
+
+// OCP e4m3fn bits of RNE(y), |y| <= 448 (sign kept, so a negative value that rounds to zero gives 0x80). With e = max(floor(log2|y|), -6)
+// the step is 2^(e-3) and q = |y| / 2^(e-3) in [0, 16]; bits = 8 (e + 6) + q covers normals (q >= 8), subnormals (e = -6, q < 8) and the carry
+// of q = 16 into the next exponent in one expression.
+G3_DEVICE uint32_t e4m3_rne(float y) {
+    const uint32_t b = __float_as_uint(y);
+    int e = (int)((b >> 23) & 0xff) - 127;
+    e = e < -6 ? -6 : e;
+    const float q = rintf(ldexpf(fabsf(y), 3 - e));
+    return ((b >> 24) & 0x80) | (uint32_t)((e + 6) * 8 + (int)q);
+}
+
+// Shared exponent X of a block (E8M0 byte = X + 127). amax is a finite non-negative bf16 value widened to fp32.
+G3_DEVICE int mx_block_exponent(float amax) {
+    if (amax == 0.0f) return 0;
+    int X = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;  // subnormal amax: exponent field 0 -> X far below -127, clamped
+    return X < -127 ? -127 : (X > 127 ? 127 : X);
+}
+
+// 4 lanes per 32-element block, 8 elements (16 bytes) each: every load and store is a contiguous run across the wave.
+__global__ __launch_bounds__(256) void quant_mxfp8_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ q, int64_t ldq,
+                                                          uint8_t* __restrict__ scales, int64_t lds, int M, int K) {
+    const int per_row = K >> 3;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = idx < (int64_t)M * per_row;  // dead lanes still join the shuffles (their amax is 0)
+    const int row = live ? (int)(idx / per_row) : 0;
+    const int c8 = live ? (int)(idx - (int64_t)row * per_row) : 0;
+    bf16x8 v = zero_bf16x8();
+    if (live) v = load_bf16x8(x + (int64_t)row * ldx + 8 * c8);
+    float f[8];
+    float amax = 0.0f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        f[e] = (float)v[e];
+        amax = fmaxf(amax, fabsf(f[e]));
+    }
+    amax = fmaxf(amax, wave_xor_f32(amax, 1));
+    amax = fmaxf(amax, wave_xor_f32(amax, 2));
+    if (!live) return;
+    const int X = mx_block_exponent(amax);
+    u32x2 o = {0u, 0u};
+    if (amax != 0.0f) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float y = fminf(fmaxf(ldexpf(f[e], -X), -448.0f), 448.0f);
+            o[e >> 2] |= e4m3_rne(y) << (8 * (e & 3));
+        }
+    }
+    *reinterpret_cast<u32x2*>(q + (int64_t)row * ldq + 8 * c8) = o;
+    if ((c8 & 3) == 0) scales[(int64_t)row * lds + (c8 >> 2)] = (uint8_t)(X + 127);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// GEMM
+// ---------------------------------------------------------------------------------------------------------------
+
+struct MxParams {
+    GemmParams ep;  // C / gate / residual, M, N, K and the tile grid: what the shared epilogue reads
+    const uint8_t* A; int64_t lda; const uint8_t* As; int64_t ldas;  // activations [M][lda] e4m3, scales [M][ldas] E8M0
+    const uint8_t* W; int64_t ldw; const uint8_t* Ws; int64_t ldws;  // weights [N][ldw] e4m3, scales [N][ldws] E8M0
+};
+
+constexpr int MX_TILE_BYTES = BM * MX_BK;                          // one operand, one stage: 32 KiB
+constexpr int MX_SCALE_OFF = 2 * (BM + BN) * MX_BK;                // 128 KiB of operand stages, then [2 stages][256 A rows + 256 W rows] dwords
+constexpr int MX_SMEM = MX_SCALE_OFF + 2 * (BM + BN) * 4;          // 132 KiB
+
+G3_DEVICE i32x8 mx_frag(const char* tile, int row, int chunk) {  // 32 bytes = logical chunks `chunk`, `chunk` + 2 of a swizzled 128-B row
+    const u32x4 lo = *reinterpret_cast<const u32x4*>(tile + row * MX_BK + ((chunk ^ ((row >> 1) & 7)) << 4));
+    const u32x4 hi = *reinterpret_cast<const u32x4*>(tile + row * MX_BK + (((chunk + 2) ^ ((row >> 1) & 7)) << 4));
+    i32x8 r;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        r[e] = (int)lo[e];
+        r[4 + e] = (int)hi[e];
+    }
+    return r;
+}
+
+template <int EPI>
+__global__ __launch_bounds__(NTHREADS, 2) void gemm_mxfp8_nt_kernel(MxParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+    char* sA = smem_raw;                       // [2][BM][128]
+    char* sW = smem_raw + 2 * MX_TILE_BYTES;   // [2][BN][128]
+    const uint32_t* sS = reinterpret_cast<const uint32_t*>(smem_raw + MX_SCALE_OFF);  // [2][A rows 256 | W rows 256]
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = tid >> 6;
+    const int l31 = lane & 31;
+    const int g = lane >> 5;
+
+    // tile order of the bf16 kernels: a contiguous run of the global order per XCD, token tiles in super-rows of 4
+    const int nblk = p.ep.tiles_m * p.ep.tiles_n;
+    int bid = blockIdx.x;
+    {
+        const int q = nblk >> 3, r = nblk & 7;
+        const int xcd = bid & 7, slot = bid >> 3;
+        bid = ((xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+    }
+    constexpr int GM = 4;
+    const int per_group = GM * p.ep.tiles_n;
+    const int grp = bid / per_group;
+    const int within = bid - grp * per_group;
+    const int gm = min(GM, p.ep.tiles_m - grp * GM);
+    const int tile_n = within / gm;
+    const int tile_m = grp * GM + (within - tile_n * gm);
+    const int m0 = tile_m * BM;
+    const int n0 = tile_n * BN;
+    const int M = p.ep.M;
+
+    // ---- LDS-DMA sources: this lane fills physical chunk tid & 7 of rows (tid >> 3) + 64 i, i.e. logical chunk (tid & 7) ^ ((tid >> 4) & 7).
+    // Token rows past M read the last row (never stored); N is a multiple of 256 (host).
+    const int src_chunk = (tid & 7) ^ ((tid >> 4) & 7);
+    const uint8_t* ga[4];
+    const uint8_t* gw[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int row = (tid >> 3) + 64 * i;
+        ga[i] = p.A + (int64_t)min(m0 + row, M - 1) * p.lda + src_chunk * 16;
+        gw[i] = p.W + (int64_t)(n0 + row) * p.ldw + src_chunk * 16;
+    }
+    // scale dwords: threads 0..255 fetch token row tid's, 256..511 weight row (tid - 256)'s
+    const uint8_t* gs = tid < 256 ? p.As + (int64_t)min(m0 + tid, M - 1) * p.ldas : p.Ws + (int64_t)(n0 + tid - 256) * p.ldws;
+
+    auto stage = [&](int t, int buf) {
+        const int k0 = t * MX_BK;
+        char* dA = sA + buf * MX_TILE_BYTES + wave * 1024;  // wave-uniform base; the hardware adds lane * 16 bytes
+        char* dW = sW + buf * MX_TILE_BYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ga[i] + k0),
+                                             (__attribute__((address_space(3))) void*)(dA + i * 8192), 16, 0, 0);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gw[i] + k0),
+                                             (__attribute__((address_space(3))) void*)(dW + i * 8192), 16, 0, 0);
+        }
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gs + 4 * t),
+                                         (__attribute__((address_space(3))) void*)(smem_raw + MX_SCALE_OFF + buf * 2048 + wave * 256), 4, 0, 0);
+    };
+
+    // ---- wave tile: 128 features x 64 tokens (the layout store_tile_lds takes)
+    const int n_w0 = (wave & 1) * 128;
+    const int m_w0 = (wave >> 1) * 64;
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+
+    const int nk = p.ep.K / MX_BK;
+    stage(0, 0);
+    lds_dma_publish_barrier();
+
+    for (int t = 0; t < nk; ++t) {
+        const int buf = t & 1;
+        G3_JITTER(wave + blockIdx.x, t);
+        if (t + 1 < nk) stage(t + 1, buf ^ 1);  // buf ^ 1 was last read in iteration t - 1 (barrier passed)
+
+        const char* cA = sA + buf * MX_TILE_BYTES;
+        const char* cW = sW + buf * MX_TILE_BYTES;
+        const uint32_t* cS = sS + buf * 512;
+        uint32_t ws[4], as[2];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ws[i] = cS[256 + n_w0 + 32 * i + l31] >> (8 * g);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) as[j] = cS[m_w0 + 32 * j + l31] >> (8 * g);
+
+        i32x8 wf[2][4], af[2][2];
+        auto load_frags = [&](int ks, int slot) {
+            const int chunk = 4 * ks + g;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) wf[slot][i] = mx_frag(cW, n_w0 + 32 * i + l31, chunk);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) af[slot][j] = mx_frag(cA, m_w0 + 32 * j + l31, chunk);
+        };
+        load_frags(0, 0);
+        load_frags(1, 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[0][i], af[0][j], acc[i][j], 0, 0, 0, (int)ws[i], 0, (int)as[j]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(wf[1][i], af[1][j], acc[i][j], 0, 0, 2, (int)ws[i], 2, (int)as[j]);
+
+        lds_dma_publish_barrier();  // tile t + 1 has landed for every wave; every wave is done with stage buf
+    }
+
+    store_tile_lds<EPI>(p.ep, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
+}
+
+template <int EPI>
+int launch_mx(const MxParams& p, hipStream_t stream) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_nt_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
+        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "g3_gemm_mxfp8_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((gemm_mxfp8_nt_kernel<EPI>), dim3(p.ep.tiles_m * p.ep.tiles_n), dim3(NTHREADS), MX_SMEM, stream, p);
+    return g3_check_launch("g3_gemm_mxfp8_nt");
+}
+
+bool mx_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % MX_BK) == 0; }
+
+}  // namespace
+
+extern "C" int g3_quant_mxfp8_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream) {
+    if (!x || !q || !scales) return g3_set_error(G3_ERR_ARG, "g3_quant_mxfp8_bf16: null operand");
+    if (M <= 0 || K <= 0 || (K % MX_BLOCK)) return g3_set_error(G3_ERR_ARG, "g3_quant_mxfp8_bf16: need M > 0 and K a positive multiple of 32 (M=%d K=%d)", M, K);
+    if (ldx < K || (ldx & 7) || ldq < K || (ldq & 7) || lds < K / MX_BLOCK)
+        return g3_set_error(G3_ERR_ARG, "g3_quant_mxfp8_bf16: need ldx >= K, ldq >= K (multiples of 8), lds >= K/32 (ldx=%lld ldq=%lld lds=%lld K=%d)",
+                            (long long)ldx, (long long)ldq, (long long)lds, K);
+    if (((uintptr_t)x & 15) || ((uintptr_t)q & 7)) return g3_set_error(G3_ERR_ARG, "g3_quant_mxfp8_bf16: x must be 16-byte and q 8-byte aligned");
+    const int64_t threads = (int64_t)M * (K / 8);
+    const int64_t blocks = (threads + 255) / 256;
+    if (blocks > 0x7fffffffLL) return g3_set_error(G3_ERR_ARG, "g3_quant_mxfp8_bf16: tensor too large");
+    hipLaunchKernelGGL(quant_mxfp8_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx, (uint8_t*)q, ldq,
+                       (uint8_t*)scales, lds, M, K);
+    return g3_check_launch("g3_quant_mxfp8_bf16");
+}
+
+extern "C" int g3_gemm_mxfp8_nt(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws,
+                                int64_t ldws, void* c, int64_t ldc, int M, int N, int K, int epilogue, const void* gate, int gate_rows,
+                                int64_t ldg, const void* residual, int64_t ldr, void* stream) {
+    const char* f = "g3_gemm_mxfp8_nt";
+    if (!aq || !as || !wq || !ws || !c) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (!mx_shape_ok(M, N, K)) return g3_set_error(G3_ERR_ARG, "%s: need M > 0, N a multiple of 256 and K a multiple of 128 (M=%d N=%d K=%d)", f, M, N, K);
+    if (lda < K || ldw < K || (lda & 15) || (ldw & 15)) return g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= K and multiples of 16 (lda=%lld ldw=%lld)", f, (long long)lda, (long long)ldw);
+    if (ldas < K / MX_BLOCK || ldws < K / MX_BLOCK || (ldas & 3) || (ldws & 3))
+        return g3_set_error(G3_ERR_ARG, "%s: need scale strides >= K/32 and multiples of 4 (ldas=%lld ldws=%lld K=%d)", f, (long long)ldas, (long long)ldws, K);
+    if (((uintptr_t)aq | (uintptr_t)wq) & 15) return g3_set_error(G3_ERR_ARG, "%s: operands must be 16-byte aligned", f);
+    if (((uintptr_t)as | (uintptr_t)ws) & 3) return g3_set_error(G3_ERR_ARG, "%s: scales must be 4-byte aligned", f);
+    if (ldc < N || (ldc & 7) || ((uintptr_t)c & 15)) return g3_set_error(G3_ERR_ARG, "%s: C needs ldc >= N, ldc %% 8 == 0 and 16-byte alignment", f);
+    if (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL) return g3_set_error(G3_ERR_ARG, "%s: unsupported epilogue %d", f, epilogue);
+    if (epilogue == EPI_GATED_RESIDUAL &&
+        (!gate || !residual || gate_rows <= 0 || (ldg & 7) || (ldr & 7) || ldr < N || (gate_rows > 1 && ldg < N) ||
+         (((uintptr_t)gate | (uintptr_t)residual) & 15)))
+        return g3_set_error(G3_ERR_ARG, "%s: gated-residual epilogue needs gate [gate_rows][ldg >= N] and residual [M][ldr >= N], 16-byte aligned rows", f);
+    MxParams p{};
+    p.ep.tile_order_rowmajor = 0;
+    p.ep.wide_store = 1;
+    p.ep.C = (bf16_t*)c; p.ep.ldc = ldc;
+    p.ep.M = M; p.ep.N = N; p.ep.K = K;
+    p.ep.gate = (const bf16_t*)gate; p.ep.gate_rows = gate_rows > 0 ? gate_rows : 1; p.ep.ldg = ldg;
+    p.ep.R = (const bf16_t*)residual; p.ep.ldr = ldr;
+    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
+    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
+    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
+    hipStream_t s = (hipStream_t)stream;
+    switch (epilogue) {
+        case EPI_NONE: return launch_mx<EPI_NONE>(p, s);
+        case EPI_GELU: return launch_mx<EPI_GELU>(p, s);
+        default: return launch_mx<EPI_GATED_RESIDUAL>(p, s);
+    }
+}
+
+extern "C" const char* g3_gemm_mxfp8_kernel_name(int M, int N, int K, int epilogue) {
+    if (!mx_shape_ok(M, N, K) || (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL)) return nullptr;
+    static const char* const names[3] = {"gemm_mxfp8_nt_kernel<0>", "gemm_mxfp8_nt_kernel<1>", "gemm_mxfp8_nt_kernel<2>"};  // EPI_NONE, GELU, GATED_RESIDUAL
+    return names[epilogue];
+}

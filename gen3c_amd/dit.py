@@ -44,12 +44,16 @@ _V_OPERAND_SWAP = __import__("os").environ.get("G3_V_OPERAND_SWAP", "1") != "0"
 _CROSS_Q_NORM_IN_ATTENTION = __import__("os").environ.get("G3_CROSS_Q_NORM_IN_ATTENTION", "1") != "0"
 
 
-def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total):
+def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total, hq=None, wq=None):
     """a @ w^T with per-head RMSNorm (+ RoPE) on the first n_q (weight norm_q) and the next n_k (norm_k) output features; the rest plain.
-    Same rounding points either way (tested): the fused GEMM epilogue, or the plain GEMM followed by the in-place norm passes."""
-    if _FUSE_QKV_EPILOGUE:
+    Same rounding points either way (tested): the fused GEMM epilogue, or the plain GEMM followed by the in-place norm passes.
+    hq / wq: MXFP8 (q, scales) of h and of w (linear_precision "mxfp8"): the block-scaled GEMM, then the same in-place norm passes."""
+    if wq is not None:
+        y = ops.gemm_mxfp8_nt(hq[0], hq[1], wq[0], wq[1])
+    elif _FUSE_QKV_EPILOGUE:
         return ops.gemm_qk_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B)
-    y = ops.gemm_nt(h, w)
+    else:
+        y = ops.gemm_nt(h, w)
     if n_q and n_k:
         ops.qk_rmsnorm_rope_pair(y[:, :n_q + n_k], norm_q, n_q // 128, norm_k, n_k // 128, cos, sin, S, B)
     elif n_q:
@@ -57,6 +61,16 @@ def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total)
     elif n_k:
         ops.qk_rmsnorm_rope(y[:, n_q:n_q + n_k], norm_k, cos, sin, S, B, n_k // 128, out=y[:, n_q:n_q + n_k])
     return y
+
+
+LINEAR_PRECISIONS = ("bf16", "mxfp8")
+MXFP8_LINEARS = ("fa_qkv", "fa_out", "ca_q", "ca_out", "w1", "w2")  # the packed-weight names of the linears the mxfp8 mode quantises
+
+
+def _mx_rows(blk: dict, name: str, rows: slice):
+    """MXFP8 (q, scales) of rows `rows` of a packed weight, or None in the bf16 mode."""
+    mx = blk.get("mx")
+    return None if mx is None else (mx[name][0][rows], mx[name][1][rows])
 
 
 class DataType(Enum):
@@ -145,6 +159,7 @@ class VideoExtendGeneralDIT(nn.Module):
         device: Optional[torch.device | str] = None,
         dtype: torch.dtype = torch.bfloat16,
         init_weights: bool = True,
+        linear_precision: str = "bf16",
     ) -> None:
         super().__init__()
         # the GEN3C-Cosmos-7B configuration space (config/base/net.py:23-43 + cosmos-1-diffusion-gen3c.py:38-43);
@@ -181,6 +196,8 @@ class VideoExtendGeneralDIT(nn.Module):
         self.cross_attention_skip_zero_context = True
         self._tables: Dict[tuple, tuple] = {}
         self._packed = None
+        self.linear_precision = "bf16"
+        self.set_linear_precision(linear_precision)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
         D, Hd = model_channels, self.head_dim
@@ -277,6 +294,25 @@ class VideoExtendGeneralDIT(nn.Module):
         self._tables.clear()
         return out
 
+    def set_linear_precision(self, precision: str) -> None:
+        """"bf16" (default, the parity path) or "mxfp8": the six per-block linears (self-attention QKV and out-projection, cross-attention Q
+        and out-projection, MLP up and down) run on MXFP8 operands (OCP MX, e4m3 + a power-of-two scale per 32 k; g3_gemm_mxfp8_nt) with their
+        activations quantised per call. Patch embed, final layer, cross-attention K / V, adaLN and attention stay bf16. The mxfp8 mode is
+        outside the bf16 parity statement (DESIGN.md section 10 gives its measured quality)."""
+        if precision not in LINEAR_PRECISIONS:
+            raise ValueError(f"linear_precision must be one of {LINEAR_PRECISIONS}, got {precision!r}")
+        if precision != self.linear_precision:
+            self._packed = None  # the quantised weights are part of the packed weight set
+        self.linear_precision = precision
+
+    def _linear(self, a: torch.Tensor, blk: dict, name: str, **kw) -> torch.Tensor:
+        """One of the six block linears: the bf16 GEMM, or under "mxfp8" the activation quantised and the block-scaled GEMM."""
+        mx = blk.get("mx")
+        if mx is None:
+            return ops.gemm_nt(a, blk[name], **kw)
+        aq, as_ = ops.quant_mxfp8(a)
+        return ops.gemm_mxfp8_nt(aq, as_, mx[name][0], mx[name][1], **kw)
+
     def _weights_key(self) -> tuple:
         """Identity of the current weight set: (storage address, in-place version counter) of every parameter. Any in-place
         update (p.copy_, weight swapping) or re-assignment (load_state_dict(assign=True) on a sub-module) changes it."""
@@ -290,7 +326,8 @@ class VideoExtendGeneralDIT(nn.Module):
         # Inference tensors (a model built or loaded under torch.inference_mode()) carry no version counter - their key is the storage address
         # alone, and an in-place p.copy_(new) inside inference mode would leave the fused QKV / K-V copies stale. Such a weight set is re-fused on
         # every call (two concatenations per block: ~2 ms of a 1.7 s forward) instead of trusting the address.
-        if self._packed is not None and self._packed["key"] == key and self._packed["versioned"]:
+        if (self._packed is not None and self._packed["key"] == key and self._packed["versioned"]
+                and self._packed["precision"] == self.linear_precision):
             return self._packed
         if self._packed is not None and self._packed["key"] != key:
             self._tables.clear()  # the position tables derive from the pos-emb parameters (an unversioned re-fuse of the SAME storages keeps them)
@@ -311,7 +348,10 @@ class VideoExtendGeneralDIT(nn.Module):
                 w1=P[f"{mlp}.block.layer1.weight"], w2=P[f"{mlp}.block.layer2.weight"],
                 ada=[(P[f"{pre}.{j}.adaLN_modulation.1.weight"], P[f"{pre}.{j}.adaLN_modulation.2.weight"]) for j in range(3)],
             ))
-        self._packed = dict(blocks=blocks, P=P, key=key, versioned=cacheable(*P.values()))
+        if self.linear_precision == "mxfp8":  # quantised copies of the six block linears' weights, rebuilt with the rest of the set
+            for blk in blocks:
+                blk["mx"] = {n: ops.quant_mxfp8(blk[n]) for n in MXFP8_LINEARS}
+        self._packed = dict(blocks=blocks, P=P, key=key, versioned=cacheable(*P.values()), precision=self.linear_precision)
         return self._packed
 
     # ------------------------------------------------------------------------------------------------ context parallel
@@ -488,24 +528,33 @@ class VideoExtendGeneralDIT(nn.Module):
                 pos["full"] = (pe_sum / pos["norm"].reshape(Tp, Hp, Wp, 1)).reshape(S, D).contiguous()
                 del pe_sum
             h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
+            hq = ops.quant_mxfp8(h) if "mx" in blk else None
             if self._cp_fused_qkv():
                 # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
                 # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
                 # (M = 14 080) a separate N = 4096 Q projection is 3.44 rounds of 256 x 256 tiles on 256 workgroups and ran at 77 % of its cp = 1
                 # rate (profiles/r6_cp_rank_shapes.txt); inside the N = 12 288 projection the same tiles are part of 10.3 rounds.
-                qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH)
+                qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
+                                         wq=_mx_rows(blk, "fa_qkv", slice(None)))
                 pending = self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
                 o = self._cp_attn.finish(qkv[:, :D], pending)
             elif self._cp_attn is not None:
                 # K / V first, so their exchange is in flight while Q is still being projected (same fused weight, sliced;
                 # every output element sees the same K order, so this is bit-identical to the single fused GEMM)
                 # the per-head RMSNorm + RoPE of q and k (attention.py:262-280) run in the projections' epilogues
-                kv = _project_norm_rope(h, blk["fa_qkv"][D:], 0, D, None, blk["fa_kn"], cos, sin, S, B, nH)  # [S*B, 2D]: k normalised + rotated, v plain
+                kv = _project_norm_rope(h, blk["fa_qkv"][D:], 0, D, None, blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
+                                        wq=_mx_rows(blk, "fa_qkv", slice(D, None)))  # [S*B, 2D]: k normalised + rotated, v plain
                 pending = self._cp_attn.start(kv[:, :D], kv[:, D:], S, B, nH)
-                q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH)
+                q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH, hq=hq,
+                                       wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
                 o = self._cp_attn.finish(q, pending)
             else:
-                if _FUSE_QKV_EPILOGUE:
+                if hq is not None:  # mxfp8: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
+                    qkv = ops.gemm_mxfp8_nt(hq[0], hq[1], *blk["mx"]["fa_qkv"])
+                    ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
+                    q, k = qkv[:, :D], qkv[:, D:2 * D]
+                    vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
+                elif _FUSE_QKV_EPILOGUE:
                     # [S*B, 3D]: q and k normalised + rotated; the v heads go straight into V^T (their columns of qkv stay unwritten)
                     vt = self._vt_buffer(S, B, nH, dev)
                     qkv = ops.gemm_qk_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, vt=vt)
@@ -525,22 +574,23 @@ class VideoExtendGeneralDIT(nn.Module):
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
                 o = ops.flash_attn(q, k, vt, S, S, B, nH)
-            ops.gemm_nt(o, blk["fa_out"], out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
+            self._linear(o, blk, "fa_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- cross attention (unmasked over all M context tokens, general_dit.py:407-410)
             shift, scale, gate = self._modulation(emb, blk["ada"][1], adaln_lora, 3)
             h = ops.layernorm_modulate(xs, shift, scale)
             k, vt = ca_kv[bi]
             if _CROSS_Q_NORM_IN_ATTENTION:  # plain projection; to_q[1]'s per-head RMSNorm runs in the attention kernel's Q load (no RoPE in cross-attention)
-                o = ops.flash_attn(ops.gemm_nt(h, blk["ca_q"]), k, vt, S, M, B, nH, kv_dense=ca_dense, q_norm_weight=blk["ca_qn"])
+                o = ops.flash_attn(self._linear(h, blk, "ca_q"), k, vt, S, M, B, nH, kv_dense=ca_dense, q_norm_weight=blk["ca_qn"])
             else:
-                q = _project_norm_rope(h, blk["ca_q"], D, 0, blk["ca_qn"], None, None, None, S, B, nH)
+                q = _project_norm_rope(h, blk["ca_q"], D, 0, blk["ca_qn"], None, None, None, S, B, nH,
+                                       hq=ops.quant_mxfp8(h) if "mx" in blk else None, wq=_mx_rows(blk, "ca_q", slice(None)))
                 o = ops.flash_attn(q, k, vt, S, M, B, nH, kv_dense=ca_dense)
-            ops.gemm_nt(o, blk["ca_out"], out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
+            self._linear(o, blk, "ca_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- MLP
             shift, scale, gate = self._modulation(emb, blk["ada"][2], adaln_lora, 3)
             h = ops.layernorm_modulate(xs, shift, scale)
-            u = ops.gemm_nt(h, blk["w1"], epilogue=ops.EPI_GELU)
-            ops.gemm_nt(u, blk["w2"], out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
+            u = self._linear(h, blk, "w1", epilogue=ops.EPI_GELU)
+            self._linear(u, blk, "w2", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
 
         # ---- final layer (blocks.py:222-242) + unpatchify (general_dit.py:348-357)
         fl = (P["final_layer.adaLN_modulation.1.weight"], P["final_layer.adaLN_modulation.2.weight"])

@@ -84,6 +84,63 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None
     return out
 
 
+def quant_mxfp8(x: torch.Tensor, out=None):
+    """MXFP8 (OCP MX, e4m3fn) of a bf16 [M, K] matrix: (q [M, K] torch.float8_e4m3fn, scales [M, K/32] torch.uint8 E8M0).
+    out: an optional (q, scales) pair to write into. See g3_quant_mxfp8_bf16 for the rounding rule."""
+    M, K, ldx = _rowmajor2d(x, "x")
+    if out is None:
+        out = (torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device), torch.empty((M, K // 32), dtype=torch.uint8, device=x.device))
+    q, s = out
+    Mq, Kq, ldq = _rowmajor2d(q, "q")
+    Ms, Ks, lds = _rowmajor2d(s, "scales")
+    if (Mq, Kq) != (M, K) or (Ms, Ks) != (M, K // 32):
+        raise _lib.Gen3cHipError(f"quant_mxfp8: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match x {tuple(x.shape)}")
+    lib = _lib.load()
+    _lib.check(lib.g3_quant_mxfp8_bf16(_dev(x, "x"), ldx, _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, M, K,
+                                       _stream()), "g3_quant_mxfp8_bf16")
+    return q, s
+
+
+def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  epilogue: int = EPI_NONE, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M,N] = epi(dequant(aq, as_) @ dequant(wq, ws)^T) on the block-scaled matrix cores; operands as quant_mxfp8 returns them.
+    Same epilogues and rounding points as gemm_nt (NONE, GELU, GATED_RESIDUAL; out may be the residual)."""
+    M, K, lda = _rowmajor2d(aq, "aq")
+    N, Kw, ldw = _rowmajor2d(wq, "wq")
+    if K != Kw:
+        raise _lib.Gen3cHipError(f"gemm_mxfp8_nt: K mismatch {K} vs {Kw}")
+    Ma, Ka, ldas = _rowmajor2d(as_, "as_")
+    Nw, Kws, ldws = _rowmajor2d(ws, "ws")
+    if (Ma, Nw) != (M, N) or Ka * 32 != K or Kws * 32 != K:
+        raise _lib.Gen3cHipError(f"gemm_mxfp8_nt: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
+    Mo, No, ldc = _rowmajor2d(out, "out")
+    assert (Mo, No) == (M, N)
+    gp, grows, ldg, rp, ldr = 0, 1, 0, 0, 0
+    if gate is not None:
+        grows, gn, ldg = _rowmajor2d(gate, "gate")
+        assert gn == N
+        gp = _dev(gate, "gate")
+    if residual is not None:
+        rm, rn, ldr = _rowmajor2d(residual, "residual")
+        assert (rm, rn) == (M, N)
+        rp = _dev(residual, "residual")
+    lib = _lib.load()
+    timer = None
+    if _KERNEL_TIMERS is not None and M >= 4096:
+        timer = HipTimer()
+        timer.start()
+    f8 = torch.float8_e4m3fn
+    _lib.check(lib.g3_gemm_mxfp8_nt(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
+                                    _dev(ws, "ws", torch.uint8), ldws, _dev(out, "out"), ldc, M, N, K, epilogue, gp, grows, ldg, rp, ldr,
+                                    _stream()), "g3_gemm_mxfp8_nt")
+    if timer is not None:
+        timer.stop()
+        _KERNEL_TIMERS.append(("gemm_mxfp8_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    return out
+
+
 def gemv(a: torch.Tensor, w: torch.Tensor, add: Optional[torch.Tensor] = None, act_in: int = 0,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[M<=8, N] = act_in(a) @ w^T (+ add)."""

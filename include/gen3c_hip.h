@@ -65,6 +65,26 @@ int g3_gemm_bf16_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void
 /* Name of the kernel the call above launches for this shape under the options in force (aligned operands assumed): profilers / bench.py only. */
 const char* g3_gemm_kernel_name(int M, int N, int K, int epilogue);
 
+/* ---- opt-in MXFP8 DiT linears (OCP MX v1.0, e4m3fn elements; outside the bf16 parity statement, DESIGN.md "MXFP8 linears") -------------
+ * x [M][ldx] bf16 -> q [M][ldq] e4m3fn bytes + scales [M][lds] E8M0 bytes, one per 32 consecutive k of a row:
+ *   X = floor(log2(amax of the block)) - 8, byte X + 127 clamped to 0..254; q = RNE(clamp(x / 2^X, -448, 448)); an all-zero block gets byte 127
+ *   and zero elements. Needs K % 32 == 0, ldx and ldq multiples of 8 (>= K), lds >= K/32; x 16-byte, q 8-byte aligned. */
+int g3_quant_mxfp8_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream);
+
+/* C[M,N] = epi( sum_k (aq[m][k] 2^as[m][k/32]) (wq[n][k] 2^ws[n][k/32]) ) with fp32 accumulation on the block-scaled matrix cores; operands as
+ * g3_quant_mxfp8_bf16 writes them. Epilogues G3_EPI_NONE, G3_EPI_GELU, G3_EPI_GATED_RESIDUAL with the rounding points of g3_gemm_bf16_nt
+ * (C may alias the residual). Needs N % 256 == 0, K % 128 == 0, lda / ldw >= K multiples of 16 with 16-byte aligned operands, scale strides
+ * >= K/32 multiples of 4 with 4-byte aligned scales, ldc (ldg, ldr) multiples of 8 with 16-byte aligned rows, ldr >= N and ldg >= N when
+ * gate_rows > 1; anything else is refused with
+ * G3_ERR_ARG before any launch. */
+int g3_gemm_mxfp8_nt(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws,
+                     void* c, int64_t ldc, int M, int N, int K, int epilogue, const void* gate, int gate_rows, int64_t ldg,
+                     const void* residual, int64_t ldr, void* stream);
+
+/* Name of the kernel instantiation g3_gemm_mxfp8_nt launches for this shape and epilogue ("gemm_mxfp8_nt_kernel<epilogue>"), or NULL where it
+ * refuses the shape or epilogue: profilers / tools only. */
+const char* g3_gemm_mxfp8_kernel_name(int M, int N, int K, int epilogue);
+
 /* out[M<=8][N] = (act_in(a) . w^T) (+ add): TimestepEmbedding (blocks.py:60-80) and adaLN_modulation
  * (blocks.py:411-415, 442-447; FinalLayer blocks.py:212-216, 230). act_in: 0 none, 1 SiLU. */
 int g3_gemv_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, const void* add, int64_t ldadd, void* out,

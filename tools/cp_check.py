@@ -30,6 +30,7 @@ def main():
     net = VideoExtendGeneralDIT(max_img_h=64, max_img_w=64, max_frames=32, in_channels=81, model_channels=512, num_blocks=2, num_heads=4,
                                 adaln_lora_dim=64, crossattn_emb_channels=256, rope_t_extrapolation_ratio=2.0, device=dev, init_weights=False)
     net.initialize_weights(randomize_adaln=True, seed=11)
+    net.set_linear_precision(os.environ.get("G3_CP_CHECK_PRECISION", "bf16"))  # "mxfp8": the opt-in MXFP8 block linears on both sides of the comparison
     B, T, H, W, M = 1, 4 * world, 16, 24, 64
     rs = np.random.RandomState(3)
     nrm = lambda shape, std: torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32)).to(torch.bfloat16).to(dev)

@@ -1,0 +1,168 @@
+"""A/B of the opt-in MXFP8 DiT linears against the bf16 product path, in one process (measuring rules: both arms warmed up, then alternated).
+
+    python tools/mxfp8_ab.py --classes [--out FILE]   the six per-block linears at M = 112 640 (bench, B = 2) and 14 080 (cp = 8 rank), launch
+                                                     by launch: bf16 product GEMM (g3_gemm_bf16_nt) vs g3_gemm_mxfp8_nt, and the quantisation
+                                                     pass of each class's activations (time and counted bytes: 2 B read + 1 B + 1/32 B written)
+    python tools/mxfp8_ab.py --quant-only             only the quantisation passes (for a `rocprofv3 --kernel-trace --stats` run of its own)
+    python tools/mxfp8_ab.py --step [--steps N]       the full 28-block denoise step at the bench workload (net built as bench.py builds it: latent
+                                                     16 x 88 x 160, dense 512-token context), linear_precision bf16 vs mxfp8, both warmed up, then
+                                                     alternating; steps/s of each arm
+    python tools/mxfp8_ab.py --accum                  the scaled MFMA's accumulation error: the fa_qkv GEMM at M = 14 080 against the exact fp64
+                                                     sum of the dequantised operands on sampled outputs, next to the bf16 GEMM on the same values
+Results are appended to FILE (default profiles/r7_mxfp8_ab.txt)."""
+import argparse
+import sys
+import time
+from pathlib import Path
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+import torch  # noqa: E402
+
+from gen3c_amd import ops  # noqa: E402
+from tools.microbench import timeit  # noqa: E402
+
+D = 4096
+CLASSES = [("fa_qkv", 3 * D, D, 0), ("fa_out", D, D, 2), ("ca_q", D, D, 0), ("ca_out", D, D, 2), ("w1", 4 * D, D, 1), ("w2", D, 4 * D, 2)]
+
+
+def _log(out, line):
+    print(line, flush=True)
+    with open(out, "a") as f:
+        f.write(line + "\n")
+
+
+def classes(out, quant_only=False, rounds=3, iters=5):
+    dev = torch.device("cuda:0")
+    if not quant_only:
+        _log(out, f"== per-class GEMM A/B ({torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M')}): bf16 product kernel vs MXFP8, "
+                  f"{rounds} alternating rounds x {iters} launches, TF = 2MNK / time")
+    for M in (112640, 14080):
+        for name, N, K, epi in CLASSES:
+            torch.manual_seed(M + N + K)
+            a = torch.randn(M, K, device=dev).to(torch.bfloat16)
+            w = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
+            aq, as_ = ops.quant_mxfp8(a)
+            wq, ws = ops.quant_mxfp8(w)
+            qbytes = M * K * (2 + 1 + 1 / 32)
+            qms = min(timeit(lambda: ops.quant_mxfp8(a, out=(aq, as_)), iters) for _ in range(rounds))
+            if quant_only:
+                _log(out, f"quant {name:7s} M={M:6d} K={K:5d}: {qms:.3f} ms {qbytes / qms / 1e9:5.2f} TB/s (event-timed inside a rocprofv3 --kernel-trace --stats run)")
+                continue
+            gate = (torch.rand(2, N, device=dev) + 0.1).to(torch.bfloat16)
+            res = torch.randn(M, N, device=dev).to(torch.bfloat16)
+            c = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            kw = dict(gate=gate, residual=res) if epi == 2 else {}
+            bf = lambda: ops.gemm_nt(a, w, out=c, epilogue=epi, **kw)  # noqa: E731
+            mx = lambda: ops.gemm_mxfp8_nt(aq, as_, wq, ws, out=c, epilogue=epi, **kw)  # noqa: E731
+            bf(), mx()
+            t_bf, t_mx = [], []
+            for _ in range(rounds):
+                t_bf.append(timeit(bf, iters))
+                t_mx.append(timeit(mx, iters))
+            fl = 2.0 * M * N * K
+            b, m = min(t_bf), min(t_mx)
+            _log(out, f"{name:7s} M={M:6d} N={N:5d} K={K:5d} epi={epi}: bf16 {b:7.3f} ms {fl / b / 1e9:6.0f} TF | mxfp8 {m:7.3f} ms "
+                      f"{fl / m / 1e9:6.0f} TF | speed-up {b / m:5.3f}x (rounds bf16 {' '.join(f'{t:.3f}' for t in t_bf)}, "
+                      f"mxfp8 {' '.join(f'{t:.3f}' for t in t_mx)}) | quant A {qms:6.3f} ms {qbytes / qms / 1e9:5.2f} TB/s")
+            del a, w, aq, as_, wq, ws, gate, res, c
+            torch.cuda.empty_cache()
+
+
+def step(out, steps=3, rounds=3):
+    import numpy as np
+    from gen3c_amd.dit import VideoExtendGeneralDIT
+    from gen3c_amd.sampler import Gen3CDenoiser, VideoExtendCondition, add_condition_video_indicator_and_video_input_mask
+    dev = torch.device("cuda:0")
+    net = VideoExtendGeneralDIT(in_channels=16 + 16 * 4 + 1, rope_t_extrapolation_ratio=2.0, num_blocks=28, device=dev, init_weights=False)
+    net.initialize_weights(randomize_adaln=True, seed=1234)
+    net.cross_attention_skip_zero_context = False
+    T, Hl, Wl, B = 16, 88, 160, 1
+    rs = np.random.RandomState(1)
+    normal = lambda shape, std: torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32)).to(torch.bfloat16).to(dev)  # noqa: E731
+    den = Gen3CDenoiser(net, state_shape=(16, T, Hl, Wl))
+    den.scheduler.set_timesteps(35)
+    xt = normal((B, 16, T, Hl, Wl), den.scheduler.init_noise_sigma)
+    gt, pose = normal((B, 16, T, Hl, Wl), 0.5), normal((B, 64, T, Hl, Wl), 0.5)
+    ctx = normal((B, 512, 1024), 0.2)
+    ctx[:, 64:] = 0
+    pad = torch.zeros(B, 1, 8 * Hl, 8 * Wl, device=dev, dtype=torch.bfloat16)
+    fps = torch.tensor([24.0], device=dev)
+
+    def make_cond(p):
+        c = VideoExtendCondition(crossattn_emb=ctx, crossattn_mask=None, padding_mask=pad, fps=fps, video_cond_bool=True, condition_video_pose=p)
+        return add_condition_video_indicator_and_video_input_mask(gt, c, 1)
+
+    cond, uncond = make_cond(pose), make_cond(torch.zeros_like(pose))
+
+    def run(prec):
+        net.set_linear_precision(prec)
+        tm = ops.HipTimer()
+        x = xt
+        tm.start()
+        for i in range(steps):
+            x = den.denoise_step(x, i, cond, uncond, 1.0, 0.001, 1)
+        tm.stop()
+        torch.cuda.synchronize()
+        return tm.elapsed_ms() / steps, x
+
+    for prec in ("bf16", "mxfp8"):  # warm-up of both arms (weight quantisation, tables, context K / V)
+        run(prec)
+    res = {"bf16": [], "mxfp8": []}
+    outs = {}
+    for _ in range(rounds):
+        for prec in ("bf16", "mxfp8"):
+            ms, outs[prec] = run(prec)
+            res[prec].append(ms)
+    b, m = min(res["bf16"]), min(res["mxfp8"])
+    rel = float((outs["mxfp8"].float() - outs["bf16"].float()).norm() / outs["bf16"].float().norm())
+    _log(out, f"== full denoise step A/B ({torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M')}): 28 blocks, latent {T}x{Hl}x{Wl}, "
+              f"B = 1 (CFG branches batched: M = 112 640), dense context, {rounds} alternating rounds x {steps} steps after warm-up of both arms")
+    _log(out, f"bf16  {b:8.1f} ms/step  {1000 / b:.4f} steps/s  (rounds {' '.join(f'{t:.1f}' for t in res['bf16'])})")
+    _log(out, f"mxfp8 {m:8.1f} ms/step  {1000 / m:.4f} steps/s  (rounds {' '.join(f'{t:.1f}' for t in res['mxfp8'])})  "
+              f"steps/s {100 * (b / m - 1):+.1f} %, quantisation passes included; rel-L2 of the mxfp8 x_t after {steps} steps vs bf16 {rel:.3e}")
+
+
+def accum(out):
+    dev = torch.device("cuda:0")
+    M, N, K = 14080, 3 * D, D
+    torch.manual_seed(0)
+    a = torch.randn(M, K, device=dev).to(torch.bfloat16)
+    a[:, 5::613] *= 30
+    w = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
+    aq, as_ = ops.quant_mxfp8(a)
+    wq, ws = ops.quant_mxfp8(w)
+    deq = lambda q, s_: (q.float().view(q.shape[0], -1, 32) * torch.exp2(s_.float() - 127).unsqueeze(-1)).view(q.shape)  # noqa: E731
+    ad, wd = deq(aq, as_), deq(wq, ws)
+    rows = torch.randint(0, M, (512,), device=dev)
+    # both GEMMs round to bf16: each is measured against the exact fp64 sum, in ulps of it and relative to sum |a w|
+    ex = ad[rows].double() @ wd.double().T
+    s_abs = ad[rows].abs().double() @ wd.abs().double().T
+    mx = ops.gemm_mxfp8_nt(aq[rows].contiguous(), as_[rows].contiguous(), wq, ws).double()
+    bf = ops.gemm_nt(ad[rows].to(torch.bfloat16).contiguous(), wd.to(torch.bfloat16)).double()
+    ulp = torch.exp2(torch.floor(torch.log2(ex.abs().clamp_min(2.0 ** -126))) - 7)
+    rnd = ex.float().to(torch.bfloat16).double()  # the correctly rounded result
+    _log(out, f"== scaled-MFMA accumulation probe ({torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M')}): fa_qkv operands "
+              f"(N(0,1) activations with 30x outlier channels, N(0, 0.02) weights), {rows.numel()} sampled rows x {N} columns, K = {K}")
+    for name, y in (("mxfp8 GEMM", mx), ("bf16 GEMM on dequantised operands", bf)):
+        err = (y - ex).abs()
+        _log(out, f"{name:34s}: correctly rounded {float((y == rnd).double().mean()):.5f}, |err| / ulp(exact) max {float((err / ulp).max()):.3f}, "
+                  f"|err| / sum|a w| max {float((err / s_abs).max()):.3e} (2^{float(torch.log2((err / s_abs).max())):.1f})")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--classes", action="store_true")
+    ap.add_argument("--quant-only", action="store_true")
+    ap.add_argument("--step", action="store_true")
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--accum", action="store_true")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "r7_mxfp8_ab.txt"))
+    args = ap.parse_args()
+    if args.classes or args.quant_only:
+        classes(args.out, quant_only=args.quant_only)
+    if args.accum:
+        accum(args.out)
+    if args.step:
+        step(args.out, steps=args.steps)
