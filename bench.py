@@ -6,7 +6,7 @@ build the network input, net(cond), net(uncond), CFG, conditioning-frame replace
 121x704x1280 video latent [1,16,16,88,160] (56 320 tokens), random-init Cosmos-7B weights (28 blocks x 4096, 32 heads),
 synthetic conditions of SURVEY.md 8d. Inputs are resident in HBM before the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N>1 = context parallel over the 16 latent frames, one process per GPU over RCCL. Both launch forms work:
   * under a launcher (`python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`): RANK / WORLD_SIZE come
@@ -16,6 +16,11 @@ N>1 = context parallel over the 16 latent frames, one process per GPU over RCCL.
     reference's `torchrun --nproc_per_node=N gen3c_single_image.py --num_gpus N` (gen3c_single_image.py:248-255).
 Prints ONE JSON line on rank 0. --dump-outputs DIR writes the latent the last timed step returned (float32 .npy, fixed inputs) for
 output-for-output comparison of two builds.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, dump, print. The `roofline` / `roofline_gemm` entries
+come from the hipEvent pairs of the timed steps themselves (the attention's traffic quoted from profiles/). Everything that takes runs of
+its own - the in-run rocprofv3 traffic passes, the tokenizer / renderer rooflines, the zero-tail cross-attention steps, the wall-clock per
+video and the CPU baseline legs - runs only with --full (rank 0, n_gpus = 1; --no-extras / --no-cpu-baseline trim it).
 """
 from __future__ import annotations
 
@@ -504,10 +509,13 @@ def build_parser():
     ap.add_argument("--warmup", type=_at_least(0), default=1)
     ap.add_argument("--blocks", type=int, default=28, help="(debug only) number of DiT blocks; anything but 28 is not the benchmark")
     ap.add_argument("--latent", type=str, default="16,88,160", help="(debug only) latent T,H,W")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what takes runs of its own (n_gpus = 1): in-run rocprofv3 traffic passes, tokenizer / "
+                         "renderer rooflines, zero-tail cross-attention, wall-clock per video, CPU baseline legs (a few minutes)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
     ap.add_argument("--no-kernel-timers", action="store_true",
                     help="A/B: no hipEvent pairs around the launches of the timed region (the roofline / roofline_gemm entries are then null)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the tokenizer / renderer roofline entries (a few seconds after the timed region)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the in-run traffic passes, tokenizer / renderer rooflines, zero-tail cross-attention and wall-clock per video")
     ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
                     help="after the timed steps, write the latent the last one returned as DIR/latent.npy (float32; N > 1: gathered over the ranks)")
     ap.add_argument("--cp-config", type=str, default="auto",
@@ -1006,9 +1014,18 @@ def main():
             out["cp"] = cp_info
         if dumped is not None:
             out["dumped_outputs"] = dumped
+        # what takes runs of its own: --full only (a plain run ends with the line)
+        extras = args.full and not args.no_extras and world == 1
+        cpu_legs = args.full and not args.no_cpu_baseline and world == 1
+        if not args.full:
+            ran = "not run in this invocation (they run with --full)"
+        elif world == 1:
+            ran = "run in this invocation (--full, n_gpus = 1)"
+        else:
+            ran = "SKIPPED in this invocation (they run at n_gpus = 1 only)"
         out["outside_timed_region"] = ("in-run rocprofv3 PMC passes, tokenizer / renderer entries, the wall-clock-per-video entry and the CPU baseline legs: rank 0, after the timed loop, "
-                                       + ("run in this invocation (n_gpus = 1)" if world == 1 else "SKIPPED in this invocation (they run at n_gpus = 1 only)"))
-        if not args.no_extras and world == 1 and roof is not None and "w4b" in roof["kernel"] and (N_tok, args.blocks) == (56320, 28):
+                                       + ran)
+        if extras and roof is not None and "w4b" in roof["kernel"] and (N_tok, args.blocks) == (56320, 28):
             # the dominant kernel's memory-side traffic, measured now on this box instead of quoted from a committed file (the quoted figure stays as fallback)
             measured, how = measure_attention_traffic()
             if measured is not None:
@@ -1016,12 +1033,12 @@ def main():
                 out["roofline"]["traffic"], out["roofline"]["traffic_source"] = measured, how
             else:
                 out["roofline"]["traffic_source"] = (out["roofline"].get("traffic_source") or "") + f" [in-run measurement unavailable: {how}]"
-        if not args.no_extras and world == 1:
+        if extras:
             try:
                 out.update(stage_rooflines(dev))
             except Exception as e:  # the extras must never hide the measurement
                 out["roofline_extras_error"] = repr(e)
-        if not args.no_extras and world == 1:
+        if extras:
             try:  # the product's default cross-attention (zero-padded context tail in closed form), two steps, beside the dense timed region
                 net.cross_attention_skip_zero_context = True
                 xz = den.denoise_step(xt, 0, cond, uncond, 1.0, 0.001, 1)  # (rebuilds nothing: the K / V cache entry carries the live-key count)
@@ -1046,12 +1063,12 @@ def main():
                 out["cross_attention_zero_tail"] = {"error": repr(e)}
             finally:
                 net.cross_attention_skip_zero_context = False
-        if not args.no_extras and world == 1 and (N_tok, args.blocks) == (56320, 28):
+        if extras and (N_tok, args.blocks) == (56320, 28):
             try:
                 out["video_wallclock"] = video_wallclock(dev, net, ms_per_step)
             except Exception as e:  # the extras must never hide the measurement
                 out["video_wallclock"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if cpu_legs:
             try:
                 nthr = min(32, os.cpu_count() or 1)  # 32 threads measured fastest on the 2x64-core EPYC host
                 out["cpu_baseline"] = cpu_baseline(threads=nthr)

@@ -298,6 +298,14 @@ def test_parser_steps_and_dump_outputs():
             bench.build_parser().parse_args(bad)
 
 
+def test_parser_full_is_opt_in():
+    """A plain run times the steps and prints the line; what takes runs of its own (PMC passes, stage rooflines, wall-clock per video,
+    CPU baseline) needs --full."""
+    import bench
+    assert bench.build_parser().parse_args(["--steps", "5", "--warmup", "2"]).full is False
+    assert bench.build_parser().parse_args(["--full", "--no-cpu-baseline"]).full is True
+
+
 def test_dump_outputs_float32_within_budget(tmp_path):
     """--dump-outputs: a small output is written whole in float32 with its shape; one over its share of the budget is replaced by a fixed
     seeded sample of its values (the same positions in every run), so the files stay within the budget."""
