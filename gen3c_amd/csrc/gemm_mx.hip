@@ -19,6 +19,7 @@
 // of K tile t) shifted right by 8 h, so k-step s uses op_sel byte 2 s in both lane halves.
 #include "common.hpp"
 #include "gen3c_hip.h"
+#include "mx_quant.hpp"  // e4m3_rne, mx_block_exponent, mx_quant_quad: shared with norm_rope.hip
 
 namespace {
 
@@ -35,24 +36,6 @@ typedef int i32x8 __attribute__((ext_vector_type(8)));
 // ---------------------------------------------------------------------------------------------------------------
 // Quantisation
 // ---------------------------------------------------------------------------------------------------------------
-
-// OCP e4m3fn bits of RNE(y), |y| <= 448 (sign kept, so a negative value that rounds to zero gives 0x80). With e = max(floor(log2|y|), -6)
-// the step is 2^(e-3) and q = |y| / 2^(e-3) in [0, 16]; bits = 8 (e + 6) + q covers normals (q >= 8), subnormals (e = -6, q < 8) and the carry
-// of q = 16 into the next exponent in one expression.
-G3_DEVICE uint32_t e4m3_rne(float y) {
-    const uint32_t b = __float_as_uint(y);
-    int e = (int)((b >> 23) & 0xff) - 127;
-    e = e < -6 ? -6 : e;
-    const float q = rintf(ldexpf(fabsf(y), 3 - e));
-    return ((b >> 24) & 0x80) | (uint32_t)((e + 6) * 8 + (int)q);
-}
-
-// Shared exponent X of a block (E8M0 byte = X + 127). amax is a finite non-negative bf16 value widened to fp32.
-G3_DEVICE int mx_block_exponent(float amax) {
-    if (amax == 0.0f) return 0;
-    int X = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 8;  // subnormal amax: exponent field 0 -> X far below -127, clamped
-    return X < -127 ? -127 : (X > 127 ? 127 : X);
-}
 
 // 4 lanes per 32-element block, 8 elements (16 bytes) each: every load and store is a contiguous run across the wave.
 __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ q, int64_t ldq,
@@ -95,7 +78,11 @@ struct MxParams {
     GemmParams ep;  // C / gate / residual, M, N, K and the tile grid: what the shared epilogue reads
     const uint8_t* A; int64_t lda; const uint8_t* As; int64_t ldas;  // activations [M][lda] e4m3, scales [M][ldas] E8M0
     const uint8_t* W; int64_t ldw; const uint8_t* Ws; int64_t ldws;  // weights [N][ldw] e4m3, scales [N][ldws] E8M0
+    uint8_t* Q; int64_t ldq; uint8_t* S; int64_t lds;                // MX_OUT instantiations: the output as e4m3 [M][ldq] + E8M0 [M][lds] (ep.C unused)
 };
+
+// Template flag on top of the epilogue code: the output leaves as MXFP8 (g3_gemm_mxfp8_nt_mxout). gemm_mxfp8_nt_kernel<MX_OUT | EPI_NONE / EPI_GELU>.
+constexpr int MX_OUT = 0x100;
 
 constexpr int MX_TILE_BYTES = BM * MX_BK;                          // one operand, one stage: 32 KiB
 constexpr int MX_SCALE_OFF = 2 * (BM + BN) * MX_BK;                // 128 KiB of operand stages, then [2 stages][256 A rows + 256 W rows] dwords
@@ -111,6 +98,55 @@ G3_DEVICE i32x8 mx_frag(const char* tile, int row, int chunk) {  // 32 bytes = l
         r[4 + e] = (int)hi[e];
     }
     return r;
+}
+
+// store_tile_lds (gemm_epilogue.hpp) with another store: the same LDS transpose and the same rounding points up to and including the final
+// f32_to_bf16, then the lane's 8 bf16 values are quantised where they sit. After the transpose a lane owns 8 consecutive features of one token row
+// and the 4 lanes c2 = 4 b .. 4 b + 3 own the 32-element block b of the wave's 128 features: the block amax is two cross-lane steps (mx_quant_quad),
+// the lane stores 8 bytes of q and the quad's first lane the scale byte. What quant_mxfp8_kernel would compute from the bf16 tile, without the
+// tile ever reaching memory. The shuffles run BEFORE the row predicate (a quad is one token row: live or dead as a whole, but every lane takes part).
+template <int EPI>
+G3_DEVICE void store_tile_lds_mx(const MxParams& p, f32x16 (&acc)[4][2], int mw, int nw, int lane, char* stage) {
+    static_assert(EPI == EPI_NONE || EPI == EPI_GELU, "MXFP8 output: plain or GELU epilogue only");
+    const int l31 = lane & 31, g = lane >> 5;
+    const int rsub = lane >> 4, c2 = lane & 15;
+    const int n = nw + 8 * c2;  // < N: N is a multiple of the tile (host)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q4 + e];
+                *reinterpret_cast<f32x4*>(stage + l31 * 512 + (((8 * i + 2 * q4 + g) ^ l31) << 4)) = v;
+            }
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            const int row = 4 * s + rsub;
+            const int m = mw + 32 * j + row;
+            const f32x4 lo = *reinterpret_cast<const f32x4*>(stage + row * 512 + (((2 * c2) ^ row) << 4));
+            const f32x4 hi = *reinterpret_cast<const f32x4*>(stage + row * 512 + (((2 * c2 + 1) ^ row) << 4));
+            float v[8];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                v[e] = lo[e];
+                v[4 + e] = hi[e];
+            }
+            if (EPI == EPI_GELU) {  // the Linear's own rounding to bf16 (see store_tile), then GELU
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = gelu_erf_fast((float)f32_to_bf16(v[e]));
+            }
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (float)f32_to_bf16(v[e]);  // the bf16 the plain epilogue stores
+            int X;
+            const u32x2 o = mx_quant_quad(v, X);  // rows m >= M run the arithmetic too, on the accumulators of the clamped (last) token row: finite, discarded
+            if (m >= p.ep.M) continue;
+            *reinterpret_cast<u32x2*>(p.Q + (int64_t)m * p.ldq + n) = o;
+            if ((c2 & 3) == 0) p.S[(int64_t)m * p.lds + (n >> 5)] = (uint8_t)(X + 127);
+        }
+    }
 }
 
 template <int EPI>
@@ -228,22 +264,38 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mxfp8_nt_kernel(MxParams p) 
         lds_dma_publish_barrier();  // tile t + 1 has landed for every wave; every wave is done with stage buf
     }
 
-    store_tile_lds<EPI>(p.ep, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
+    if constexpr ((EPI & MX_OUT) != 0)
+        store_tile_lds_mx<EPI & ~MX_OUT>(p, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
+    else
+        store_tile_lds<EPI>(p.ep, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
 }
 
 template <int EPI>
-int launch_mx(const MxParams& p, hipStream_t stream) {
+int launch_mx(const MxParams& p, hipStream_t stream, const char* f = "g3_gemm_mxfp8_nt") {
     static bool attr_set = false;
     if (!attr_set) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_nt_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "g3_gemm_mxfp8_nt: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", f, hipGetErrorString(e));
         attr_set = true;
     }
     hipLaunchKernelGGL((gemm_mxfp8_nt_kernel<EPI>), dim3(p.ep.tiles_m * p.ep.tiles_n), dim3(NTHREADS), MX_SMEM, stream, p);
-    return g3_check_launch("g3_gemm_mxfp8_nt");
+    return g3_check_launch(f);
 }
 
 bool mx_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % MX_BK) == 0; }
+
+// What both GEMM entry points require of their MXFP8 operands; G3_OK or the error already set.
+int mx_check_operands(const char* f, const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws,
+                      int M, int N, int K) {
+    if (!aq || !as || !wq || !ws) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (!mx_shape_ok(M, N, K)) return g3_set_error(G3_ERR_ARG, "%s: need M > 0, N a multiple of 256 and K a multiple of 128 (M=%d N=%d K=%d)", f, M, N, K);
+    if (lda < K || ldw < K || (lda & 15) || (ldw & 15)) return g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= K and multiples of 16 (lda=%lld ldw=%lld)", f, (long long)lda, (long long)ldw);
+    if (ldas < K / MX_BLOCK || ldws < K / MX_BLOCK || (ldas & 3) || (ldws & 3))
+        return g3_set_error(G3_ERR_ARG, "%s: need scale strides >= K/32 and multiples of 4 (ldas=%lld ldws=%lld K=%d)", f, (long long)ldas, (long long)ldws, K);
+    if (((uintptr_t)aq | (uintptr_t)wq) & 15) return g3_set_error(G3_ERR_ARG, "%s: operands must be 16-byte aligned", f);
+    if (((uintptr_t)as | (uintptr_t)ws) & 3) return g3_set_error(G3_ERR_ARG, "%s: scales must be 4-byte aligned", f);
+    return G3_OK;
+}
 
 }  // namespace
 
@@ -266,13 +318,8 @@ extern "C" int g3_gemm_mxfp8_nt(const void* aq, int64_t lda, const void* as, int
                                 int64_t ldws, void* c, int64_t ldc, int M, int N, int K, int epilogue, const void* gate, int gate_rows,
                                 int64_t ldg, const void* residual, int64_t ldr, void* stream) {
     const char* f = "g3_gemm_mxfp8_nt";
-    if (!aq || !as || !wq || !ws || !c) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
-    if (!mx_shape_ok(M, N, K)) return g3_set_error(G3_ERR_ARG, "%s: need M > 0, N a multiple of 256 and K a multiple of 128 (M=%d N=%d K=%d)", f, M, N, K);
-    if (lda < K || ldw < K || (lda & 15) || (ldw & 15)) return g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= K and multiples of 16 (lda=%lld ldw=%lld)", f, (long long)lda, (long long)ldw);
-    if (ldas < K / MX_BLOCK || ldws < K / MX_BLOCK || (ldas & 3) || (ldws & 3))
-        return g3_set_error(G3_ERR_ARG, "%s: need scale strides >= K/32 and multiples of 4 (ldas=%lld ldws=%lld K=%d)", f, (long long)ldas, (long long)ldws, K);
-    if (((uintptr_t)aq | (uintptr_t)wq) & 15) return g3_set_error(G3_ERR_ARG, "%s: operands must be 16-byte aligned", f);
-    if (((uintptr_t)as | (uintptr_t)ws) & 3) return g3_set_error(G3_ERR_ARG, "%s: scales must be 4-byte aligned", f);
+    if (!c) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K)) return rc;
     if (ldc < N || (ldc & 7) || ((uintptr_t)c & 15)) return g3_set_error(G3_ERR_ARG, "%s: C needs ldc >= N, ldc %% 8 == 0 and 16-byte alignment", f);
     if (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL) return g3_set_error(G3_ERR_ARG, "%s: unsupported epilogue %d", f, epilogue);
     if (epilogue == EPI_GATED_RESIDUAL &&
@@ -301,4 +348,33 @@ extern "C" const char* g3_gemm_mxfp8_kernel_name(int M, int N, int K, int epilog
     if (!mx_shape_ok(M, N, K) || (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL)) return nullptr;
     static const char* const names[3] = {"gemm_mxfp8_nt_kernel<0>", "gemm_mxfp8_nt_kernel<1>", "gemm_mxfp8_nt_kernel<2>"};  // EPI_NONE, GELU, GATED_RESIDUAL
     return names[epilogue];
+}
+
+extern "C" int g3_gemm_mxfp8_nt_mxout(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws,
+                                      int64_t ldws, void* q_out, int64_t ldq, void* s_out, int64_t lds, int M, int N, int K, int epilogue,
+                                      void* stream) {
+    const char* f = "g3_gemm_mxfp8_nt_mxout";
+    if (!q_out || !s_out) return g3_set_error(G3_ERR_ARG, "%s: null output", f);
+    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K)) return rc;
+    if (ldq < N || (ldq & 7) || lds < N / MX_BLOCK)
+        return g3_set_error(G3_ERR_ARG, "%s: need ldq >= N (a multiple of 8) and lds >= N/32 (ldq=%lld lds=%lld N=%d)", f, (long long)ldq, (long long)lds, N);
+    if ((uintptr_t)q_out & 7) return g3_set_error(G3_ERR_ARG, "%s: q_out must be 8-byte aligned", f);
+    if (epilogue != EPI_NONE && epilogue != EPI_GELU)
+        return g3_set_error(G3_ERR_ARG, "%s: epilogue %d has no MXFP8 output (NONE and GELU only: the gated residual's output is the bf16 residual stream)", f, epilogue);
+    MxParams p{};
+    p.ep.tile_order_rowmajor = 0;
+    p.ep.wide_store = 1;
+    p.ep.M = M; p.ep.N = N; p.ep.K = K;
+    p.ep.gate_rows = 1;
+    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
+    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
+    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
+    p.Q = (uint8_t*)q_out; p.ldq = ldq; p.S = (uint8_t*)s_out; p.lds = lds;
+    hipStream_t s = (hipStream_t)stream;
+    return epilogue == EPI_GELU ? launch_mx<MX_OUT | EPI_GELU>(p, s, f) : launch_mx<MX_OUT | EPI_NONE>(p, s, f);
+}
+
+extern "C" const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int epilogue) {
+    if (!mx_shape_ok(M, N, K) || (epilogue != EPI_NONE && epilogue != EPI_GELU)) return nullptr;
+    return epilogue == EPI_GELU ? "gemm_mxfp8_nt_kernel<257>" : "gemm_mxfp8_nt_kernel<256>";  // MX_OUT | epilogue
 }

@@ -2,6 +2,7 @@
 // the V -> V^T re-layout consumed by the attention kernel, and small vector helpers.
 // All kernels move 16 bytes per lane per access (bf16x8) and keep the math in fp32.
 #include "common.hpp"
+#include "mx_quant.hpp"  // the MXFP8 quantiser shared with gemm_mx.hip (the MX instantiations below)
 
 namespace {
 
@@ -24,14 +25,22 @@ struct PosEmbArgs {
     int Hp, Wp, B;
 };
 
+// MX instantiations: h leaves as MXFP8 (e4m3 [rows][ldq] + one E8M0 byte per 32 features [rows][lds]) instead of bf16 - what g3_quant_mxfp8_bf16
+// would make of the bf16 `out`, which is then never written (g3_layernorm_modulate_mxfp8). Unused (zeros) in the bf16 instantiations.
+struct MxOut {
+    uint8_t* q; int64_t ldq; uint8_t* s; int64_t lds;
+};
+
 // POS: 0 plain; 1 the position embedding is rebuilt per row from its three axis tables (+ norm); 2 it is read from ONE materialised
 // table pe.pe_t [rows / B][D] (already summed, normalised and rounded: a row then costs one table read instead of three + a division per element)
-template <int POS>
+// MX: each value is rounded to bf16 as for `out`, then quantised in registers: a thread owns 8 consecutive features and lanes 4 i .. 4 i + 3 own chunks
+// 4 k .. 4 k + 3 = one 32-element block (D % 32 == 0, host: a quad is live or dead as a whole; dead lanes join the shuffles with amax 0).
+template <int POS, bool MX = false>
 __global__ __launch_bounds__(LN_THREADS) void ln_modulate_kernel(bf16_t* __restrict__ x, int64_t ldx,
                                                                  const bf16_t* __restrict__ shift,
                                                                  const bf16_t* __restrict__ scale, int64_t ldmod,
                                                                  int mod_rows, bf16_t* __restrict__ out, int64_t ldo,
-                                                                 int rows, int D, float eps, PosEmbArgs pe) {
+                                                                 int rows, int D, float eps, PosEmbArgs pe, MxOut mx) {
     __shared__ float red[2][LN_THREADS / 64];
     const int row = blockIdx.x;
     if (row >= rows) return;
@@ -110,6 +119,32 @@ __global__ __launch_bounds__(LN_THREADS) void ln_modulate_kernel(bf16_t* __restr
     const int mrow = row % mod_rows;
     const bf16_t* sh = shift + (int64_t)mrow * ldmod;
     const bf16_t* sc = scale + (int64_t)mrow * ldmod;
+    if constexpr (MX) {
+        uint8_t* qrow = mx.q + (int64_t)row * mx.ldq;
+        uint8_t* srow = mx.s + (int64_t)row * mx.lds;
+#pragma unroll
+        for (int c = 0; c < LN_MAX_CHUNKS; ++c) {
+            const int ch = tid + c * LN_THREADS;
+            const bool live = ch < nchunk;
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = 0.f;
+            if (live) {
+                const bf16x8 tsh = load_bf16x8(sh + ch * 8);
+                const bf16x8 tsc = load_bf16x8(sc + ch * 8);
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    f[e] = (float)f32_to_bf16((v[c][e] - mean) * rstd * (1.0f + (float)tsc[e]) + (float)tsh[e]);
+            }
+            int X;
+            const u32x2 o = mx_quant_quad(f, X);
+            if (live) {
+                *reinterpret_cast<u32x2*>(qrow + ch * 8) = o;
+                if ((ch & 3) == 0) srow[ch >> 2] = (uint8_t)(X + 127);
+            }
+        }
+        return;
+    }
     bf16_t* orow = out + (int64_t)row * ldo;
 #pragma unroll
     for (int c = 0; c < LN_MAX_CHUNKS; ++c) {
@@ -129,9 +164,11 @@ __global__ __launch_bounds__(LN_THREADS) void ln_modulate_kernel(bf16_t* __restr
 // One WAVE per row (round 6; D = 4096 exactly: 8 chunks of 8 per lane), four rows per workgroup: the row never leaves the wave's registers, the two reductions are
 // six cross-lane steps each - no LDS round trip, no workgroup barrier (the form above pays two per row). Same two-pass arithmetic (mean, then the centred squares);
 // the partial sums are formed per lane over 64 elements instead of per thread over 16, so mean / variance can differ in the last fp32 bit. POS 0 / 2 as above.
-template <int POS>
+// MX as above: lanes 4 i .. 4 i + 3 hold chunks 64 c + 4 i .. + 3, one block; every lane of a live wave is live.
+template <int POS, bool MX = false>
 __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(bf16_t* __restrict__ x, int64_t ldx, const bf16_t* __restrict__ shift, const bf16_t* __restrict__ scale,
-                                                               int64_t ldmod, int mod_rows, bf16_t* __restrict__ out, int64_t ldo, int rows, float eps, PosEmbArgs pe) {
+                                                               int64_t ldmod, int mod_rows, bf16_t* __restrict__ out, int64_t ldo, int rows, float eps, PosEmbArgs pe,
+                                                               MxOut mx) {
     constexpr int D = 4096;
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -167,7 +204,7 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(bf16_t* __restric
     const int mrow = row % mod_rows;
     const bf16_t* sh = shift + (int64_t)mrow * ldmod;
     const bf16_t* sc = scale + (int64_t)mrow * ldmod;
-    bf16_t* orow = out + (int64_t)row * ldo;
+    bf16_t* orow = MX ? nullptr : out + (int64_t)row * ldo;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const int ch = lane + 64 * c;
@@ -176,7 +213,17 @@ __global__ __launch_bounds__(256) void ln_modulate_wave_kernel(bf16_t* __restric
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = f32_to_bf16((v[c][e] - mean) * rstd * (1.0f + (float)tsc[e]) + (float)tsh[e]);
-        store_bf16x8(orow + ch * 8, o);
+        if constexpr (MX) {
+            float f[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = (float)o[e];
+            int X;
+            const u32x2 qv = mx_quant_quad(f, X);
+            *reinterpret_cast<u32x2*>(mx.q + (int64_t)row * mx.ldq + ch * 8) = qv;
+            if ((ch & 3) == 0) mx.s[(int64_t)row * mx.lds + (ch >> 2)] = (uint8_t)(X + 127);
+        } else {
+            store_bf16x8(orow + ch * 8, o);
+        }
     }
 }
 
@@ -438,10 +485,10 @@ extern "C" int g3_layernorm_modulate_bf16(const void* x, int64_t ldx, const void
         return g3_set_error(G3_ERR_ARG, "g3_layernorm_modulate_bf16: leading dims must be multiples of 8");
     if (D == 4096 && g3_opt_ln_wave_rows)
         hipLaunchKernelGGL(ln_modulate_wave_kernel<0>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)const_cast<void*>(x), ldx,
-                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, eps, PosEmbArgs{});
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, eps, PosEmbArgs{}, MxOut{});
     else
         hipLaunchKernelGGL(ln_modulate_kernel<0>, dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)const_cast<void*>(x), ldx,
-                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, PosEmbArgs{});
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, PosEmbArgs{}, MxOut{});
     return g3_check_launch("g3_layernorm_modulate_bf16");
 }
 
@@ -462,14 +509,70 @@ extern "C" int g3_posemb_layernorm_modulate_bf16(void* x, int64_t ldx, const voi
     PosEmbArgs pe{(const bf16_t*)pe_t, (const bf16_t*)pe_h, (const bf16_t*)pe_w, (const bf16_t*)pos_norm, Hp, Wp, B};
     if (materialised && D == 4096 && g3_opt_ln_wave_rows)
         hipLaunchKernelGGL(ln_modulate_wave_kernel<2>, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ldx, (const bf16_t*)shift, (const bf16_t*)scale,
-                           ldmod, mod_rows, (bf16_t*)out, ldo, rows, eps, pe);
+                           ldmod, mod_rows, (bf16_t*)out, ldo, rows, eps, pe, MxOut{});
     else if (materialised)
         hipLaunchKernelGGL(ln_modulate_kernel<2>, dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, ldx,
-                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, pe);
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, pe, MxOut{});
     else
         hipLaunchKernelGGL(ln_modulate_kernel<1>, dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, ldx,
-                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, pe);
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)out, ldo, rows, D, eps, pe, MxOut{});
     return g3_check_launch("g3_posemb_layernorm_modulate_bf16");
+}
+
+// The MXFP8 output of the two entry points above: what they refuse of it, G3_OK or the error already set.
+static int ln_mx_check(const char* f, int D, const void* q, int64_t ldq, const void* scales, int64_t lds) {
+    if (!q || !scales) return g3_set_error(G3_ERR_ARG, "%s: null output", f);
+    if (D % 32) return g3_set_error(G3_ERR_ARG, "%s: D=%d must be a multiple of 32 (one scale per 32 features)", f, D);
+    if (ldq < D || (ldq & 7) || lds < D / 32)
+        return g3_set_error(G3_ERR_ARG, "%s: need ldq >= D (a multiple of 8) and lds >= D/32 (ldq=%lld lds=%lld D=%d)", f, (long long)ldq, (long long)lds, D);
+    if ((uintptr_t)q & 7) return g3_set_error(G3_ERR_ARG, "%s: q must be 8-byte aligned", f);
+    return G3_OK;
+}
+
+extern "C" int g3_layernorm_modulate_mxfp8(const void* x, int64_t ldx, const void* shift, const void* scale, int64_t ldmod, int mod_rows, void* q,
+                                           int64_t ldq, void* scales, int64_t lds, int rows, int D, float eps, void* stream) {
+    const char* f = "g3_layernorm_modulate_mxfp8";
+    if (!x || !shift || !scale) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (rows <= 0 || D <= 0 || (D & 7) || D > LN_THREADS * 8 * LN_MAX_CHUNKS)
+        return g3_set_error(G3_ERR_ARG, "%s: D=%d must be a multiple of 8 and <= %d", f, D, LN_THREADS * 8 * LN_MAX_CHUNKS);
+    if ((ldx & 7) || (ldmod & 7) || mod_rows <= 0) return g3_set_error(G3_ERR_ARG, "%s: leading dims must be multiples of 8", f);
+    if (int rc = ln_mx_check(f, D, q, ldq, scales, lds)) return rc;
+    const MxOut mx{(uint8_t*)q, ldq, (uint8_t*)scales, lds};
+    // the same choice of form as g3_layernorm_modulate_bf16: the two differ in the last fp32 bit of mean / variance
+    if (D == 4096 && g3_opt_ln_wave_rows)
+        hipLaunchKernelGGL((ln_modulate_wave_kernel<0, true>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)const_cast<void*>(x), ldx,
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)nullptr, (int64_t)0, rows, eps, PosEmbArgs{}, mx);
+    else
+        hipLaunchKernelGGL((ln_modulate_kernel<0, true>), dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)const_cast<void*>(x), ldx,
+                           (const bf16_t*)shift, (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)nullptr, (int64_t)0, rows, D, eps, PosEmbArgs{}, mx);
+    return g3_check_launch(f);
+}
+
+extern "C" int g3_posemb_layernorm_modulate_mxfp8(void* x, int64_t ldx, const void* pe_t, const void* pe_h, const void* pe_w, const void* pos_norm, int T,
+                                                  int Hp, int Wp, int B, const void* shift, const void* scale, int64_t ldmod, int mod_rows, void* q,
+                                                  int64_t ldq, void* scales, int64_t lds, int D, float eps, void* stream) {
+    const char* f = "g3_posemb_layernorm_modulate_mxfp8";
+    const bool materialised = pe_t && !pe_h && !pe_w && !pos_norm;  // pe_t is then the finished embedding [T*Hp*Wp][D]
+    if (!x || !pe_t || !shift || !scale || (!materialised && (!pe_h || !pe_w || !pos_norm))) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (T <= 0 || Hp <= 0 || Wp <= 0 || B <= 0 || D <= 0 || (D & 7) || D > LN_THREADS * 8 * LN_MAX_CHUNKS)
+        return g3_set_error(G3_ERR_ARG, "%s: bad shape (T=%d Hp=%d Wp=%d B=%d D=%d)", f, T, Hp, Wp, B, D);
+    if ((ldx & 7) || (ldmod & 7) || mod_rows <= 0) return g3_set_error(G3_ERR_ARG, "%s: leading dims must be multiples of 8", f);
+    if (int rc = ln_mx_check(f, D, q, ldq, scales, lds)) return rc;
+    const int64_t rows64 = (int64_t)T * Hp * Wp * B;
+    if (rows64 > 0x7fffffff) return g3_set_error(G3_ERR_ARG, "%s: too many rows", f);
+    const int rows = (int)rows64;
+    PosEmbArgs pe{(const bf16_t*)pe_t, (const bf16_t*)pe_h, (const bf16_t*)pe_w, (const bf16_t*)pos_norm, Hp, Wp, B};
+    const MxOut mx{(uint8_t*)q, ldq, (uint8_t*)scales, lds};
+    if (materialised && D == 4096 && g3_opt_ln_wave_rows)
+        hipLaunchKernelGGL((ln_modulate_wave_kernel<2, true>), dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, ldx, (const bf16_t*)shift,
+                           (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)nullptr, (int64_t)0, rows, eps, pe, mx);
+    else if (materialised)
+        hipLaunchKernelGGL((ln_modulate_kernel<2, true>), dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, ldx, (const bf16_t*)shift,
+                           (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)nullptr, (int64_t)0, rows, D, eps, pe, mx);
+    else
+        hipLaunchKernelGGL((ln_modulate_kernel<1, true>), dim3(rows), dim3(LN_THREADS), 0, (hipStream_t)stream, (bf16_t*)x, ldx, (const bf16_t*)shift,
+                           (const bf16_t*)scale, ldmod, mod_rows, (bf16_t*)nullptr, (int64_t)0, rows, D, eps, pe, mx);
+    return g3_check_launch(f);
 }
 
 static int qk_rmsnorm_rope_launch(const char* what, const void* in, int64_t ld_in, const void* w_a, int h_a, const void* w_b, int h_b, const float* cos_table,

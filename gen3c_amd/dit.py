@@ -64,6 +64,7 @@ def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total,
 
 
 LINEAR_PRECISIONS = ("bf16", "mxfp8")
+MXFP8_PRODUCERS = ("separate", "fused")
 MXFP8_LINEARS = ("fa_qkv", "fa_out", "ca_q", "ca_out", "w1", "w2")  # the packed-weight names of the linears the mxfp8 mode quantises
 
 
@@ -160,6 +161,7 @@ class VideoExtendGeneralDIT(nn.Module):
         dtype: torch.dtype = torch.bfloat16,
         init_weights: bool = True,
         linear_precision: str = "bf16",
+        mxfp8_producers: str = "separate",
     ) -> None:
         super().__init__()
         # the GEN3C-Cosmos-7B configuration space (config/base/net.py:23-43 + cosmos-1-diffusion-gen3c.py:38-43);
@@ -198,6 +200,8 @@ class VideoExtendGeneralDIT(nn.Module):
         self._packed = None
         self.linear_precision = "bf16"
         self.set_linear_precision(linear_precision)
+        self.mxfp8_producers = "separate"
+        self.set_mxfp8_producers(mxfp8_producers)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
         D, Hd = model_channels, self.head_dim
@@ -305,13 +309,33 @@ class VideoExtendGeneralDIT(nn.Module):
             self._packed = None  # the quantised weights are part of the packed weight set
         self.linear_precision = precision
 
-    def _linear(self, a: torch.Tensor, blk: dict, name: str, **kw) -> torch.Tensor:
-        """One of the six block linears: the bf16 GEMM, or under "mxfp8" the activation quantised and the block-scaled GEMM."""
+    def set_mxfp8_producers(self, producers: str) -> None:
+        """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16".
+        "separate" (default): every producer writes bf16 and g3_quant_mxfp8_bf16 makes one more pass over it.
+        "fused": the kernels we own that feed a block linear quantise their output in registers - the three LayerNorm + AdaLN passes
+        (g3_layernorm_modulate_mxfp8, g3_posemb_layernorm_modulate_mxfp8) and the MLP-up GEMM's GELU epilogue (g3_gemm_mxfp8_nt_mxout) - so four
+        of a block's six bf16 hand-overs disappear. The attention outputs keep the separate pass. Bitwise the same network output either way
+        (the fused kernels round to bf16 where the separate chain does, then run the same quantiser arithmetic). The packed weights do not depend
+        on it."""
+        if producers not in MXFP8_PRODUCERS:
+            raise ValueError(f"mxfp8_producers must be one of {MXFP8_PRODUCERS}, got {producers!r}")
+        self.mxfp8_producers = producers
+
+    def _linear(self, a, blk: dict, name: str, out_mx: bool = False, **kw):
+        """One of the six block linears: the bf16 GEMM, or under "mxfp8" the activation quantised and the block-scaled GEMM.
+        a: the bf16 activation, or (mxfp8 only) the (q, scales) pair a fused producer already made of it. out_mx (mxfp8 only): the output
+        leaves as such a pair for the next linear."""
         mx = blk.get("mx")
         if mx is None:
             return ops.gemm_nt(a, blk[name], **kw)
-        aq, as_ = ops.quant_mxfp8(a)
+        aq, as_ = a if isinstance(a, tuple) else ops.quant_mxfp8(a)
+        if out_mx:
+            kw["out_mx"] = True
         return ops.gemm_mxfp8_nt(aq, as_, mx[name][0], mx[name][1], **kw)
+
+    def _ln(self, xs: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, fused: bool):
+        """LayerNorm + AdaLN modulate of the residual stream: bf16, or (fused mxfp8 producers) the MXFP8 pair the next linear consumes."""
+        return ops.layernorm_modulate_mxfp8(xs, shift, scale) if fused else ops.layernorm_modulate(xs, shift, scale)
 
     def _weights_key(self) -> tuple:
         """Identity of the current weight set: (storage address, in-place version counter) of every parameter. Any in-place
@@ -527,8 +551,12 @@ class VideoExtendGeneralDIT(nn.Module):
                 pe_sum = (pos["pe_t"][:, None, None, :] + pos["pe_h"][None, :, None, :]) + pos["pe_w"][None, None, :, :]
                 pos["full"] = (pe_sum / pos["norm"].reshape(Tp, Hp, Wp, 1)).reshape(S, D).contiguous()
                 del pe_sum
-            h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
-            hq = ops.quant_mxfp8(h) if "mx" in blk else None
+            fused = "mx" in blk and self.mxfp8_producers == "fused"  # the LayerNorms and w1 hand MXFP8 (q, scales) pairs to their linears
+            if fused:
+                h, hq = None, ops.posemb_layernorm_modulate_mxfp8(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
+            else:
+                h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
+                hq = ops.quant_mxfp8(h) if "mx" in blk else None
             if self._cp_fused_qkv():
                 # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
                 # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
@@ -577,19 +605,19 @@ class VideoExtendGeneralDIT(nn.Module):
             self._linear(o, blk, "fa_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- cross attention (unmasked over all M context tokens, general_dit.py:407-410)
             shift, scale, gate = self._modulation(emb, blk["ada"][1], adaln_lora, 3)
-            h = ops.layernorm_modulate(xs, shift, scale)
+            h = self._ln(xs, shift, scale, fused)
             k, vt = ca_kv[bi]
             if _CROSS_Q_NORM_IN_ATTENTION:  # plain projection; to_q[1]'s per-head RMSNorm runs in the attention kernel's Q load (no RoPE in cross-attention)
                 o = ops.flash_attn(self._linear(h, blk, "ca_q"), k, vt, S, M, B, nH, kv_dense=ca_dense, q_norm_weight=blk["ca_qn"])
             else:
-                q = _project_norm_rope(h, blk["ca_q"], D, 0, blk["ca_qn"], None, None, None, S, B, nH,
-                                       hq=ops.quant_mxfp8(h) if "mx" in blk else None, wq=_mx_rows(blk, "ca_q", slice(None)))
+                hq = h if fused else (ops.quant_mxfp8(h) if "mx" in blk else None)
+                q = _project_norm_rope(h, blk["ca_q"], D, 0, blk["ca_qn"], None, None, None, S, B, nH, hq=hq, wq=_mx_rows(blk, "ca_q", slice(None)))
                 o = ops.flash_attn(q, k, vt, S, M, B, nH, kv_dense=ca_dense)
             self._linear(o, blk, "ca_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- MLP
             shift, scale, gate = self._modulation(emb, blk["ada"][2], adaln_lora, 3)
-            h = ops.layernorm_modulate(xs, shift, scale)
-            u = self._linear(h, blk, "w1", epilogue=ops.EPI_GELU)
+            h = self._ln(xs, shift, scale, fused)
+            u = self._linear(h, blk, "w1", epilogue=ops.EPI_GELU, out_mx=fused)  # fused: u is the MXFP8 pair w2 consumes
             self._linear(u, blk, "w2", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
 
         # ---- final layer (blocks.py:222-242) + unpatchify (general_dit.py:348-357)

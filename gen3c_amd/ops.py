@@ -101,10 +101,8 @@ def quant_mxfp8(x: torch.Tensor, out=None):
     return q, s
 
 
-def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None,
-                  epilogue: int = EPI_NONE, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[M,N] = epi(dequant(aq, as_) @ dequant(wq, ws)^T) on the block-scaled matrix cores; operands as quant_mxfp8 returns them.
-    Same epilogues and rounding points as gemm_nt (NONE, GELU, GATED_RESIDUAL; out may be the residual)."""
+def _mx_operands(aq, as_, wq, ws):
+    """Shapes and strides of the MXFP8 operands of both GEMM forms, checked against each other. -> M, N, K, lda, ldas, ldw, ldws"""
     M, K, lda = _rowmajor2d(aq, "aq")
     N, Kw, ldw = _rowmajor2d(wq, "wq")
     if K != Kw:
@@ -113,6 +111,18 @@ def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: tor
     Nw, Kws, ldws = _rowmajor2d(ws, "ws")
     if (Ma, Nw) != (M, N) or Ka * 32 != K or Kws * 32 != K:
         raise _lib.Gen3cHipError(f"gemm_mxfp8_nt: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
+    return M, N, K, lda, ldas, ldw, ldws
+
+
+def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  epilogue: int = EPI_NONE, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, out_mx=None):
+    """out[M,N] = epi(dequant(aq, as_) @ dequant(wq, ws)^T) on the block-scaled matrix cores; operands as quant_mxfp8 returns them.
+    Same epilogues and rounding points as gemm_nt (NONE, GELU, GATED_RESIDUAL; out may be the residual).
+    out_mx: True or a (q, scales) pair to write into - the output leaves as MXFP8, bitwise quant_mxfp8 of the bf16 result, which is never
+    written (g3_gemm_mxfp8_nt_mxout; NONE and GELU only); returns (q, scales)."""
+    if out_mx is not None and out_mx is not False:
+        return _gemm_mxfp8_nt_mxout(aq, as_, wq, ws, out_mx, epilogue, out, gate, residual)
+    M, N, K, lda, ldas, ldw, ldws = _mx_operands(aq, as_, wq, ws)
     if out is None:
         out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
     Mo, No, ldc = _rowmajor2d(out, "out")
@@ -139,6 +149,38 @@ def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: tor
         timer.stop()
         _KERNEL_TIMERS.append(("gemm_mxfp8_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
     return out
+
+
+def _mx_out_pair(out, M: int, K: int, device, what: str):
+    """The (q, scales) pair an MXFP8-producing op writes: allocated, or the caller's, checked against [M, K]. -> q, s, ldq, lds"""
+    if out is None or out is True:
+        out = (torch.empty((M, K), dtype=torch.float8_e4m3fn, device=device), torch.empty((M, K // 32), dtype=torch.uint8, device=device))
+    q, s = out
+    Mq, Kq, ldq = _rowmajor2d(q, "q")
+    Ms, Ks, lds = _rowmajor2d(s, "scales")
+    if (Mq, Kq) != (M, K) or (Ms, Ks) != (M, K // 32):
+        raise _lib.Gen3cHipError(f"{what}: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match [{M}, {K}]")
+    return q, s, ldq, lds
+
+
+def _gemm_mxfp8_nt_mxout(aq, as_, wq, ws, out_mx, epilogue, out, gate, residual):
+    if out is not None or gate is not None or residual is not None:
+        raise _lib.Gen3cHipError("gemm_mxfp8_nt: out_mx takes no bf16 out, gate or residual (epilogues NONE and GELU only)")
+    M, N, K, lda, ldas, ldw, ldws = _mx_operands(aq, as_, wq, ws)
+    q, s, ldq, lds = _mx_out_pair(out_mx, M, N, aq.device, "gemm_mxfp8_nt")
+    lib = _lib.load()
+    timer = None
+    if _KERNEL_TIMERS is not None and M >= 4096:
+        timer = HipTimer()
+        timer.start()
+    f8 = torch.float8_e4m3fn
+    _lib.check(lib.g3_gemm_mxfp8_nt_mxout(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
+                                          _dev(ws, "ws", torch.uint8), ldws, _dev(q, "q", f8), ldq, _dev(s, "scales", torch.uint8), lds, M, N, K,
+                                          epilogue, _stream()), "g3_gemm_mxfp8_nt_mxout")
+    if timer is not None:
+        timer.stop()
+        _KERNEL_TIMERS.append(("gemm_mxfp8_nt_mxout", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    return q, s
 
 
 def gemv(a: torch.Tensor, w: torch.Tensor, add: Optional[torch.Tensor] = None, act_in: int = 0,
@@ -175,6 +217,20 @@ def layernorm_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor
     return out
 
 
+def layernorm_modulate_mxfp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out=None, eps: float = 1e-6):
+    """layernorm_modulate with the result as MXFP8: returns (q [rows, D] float8_e4m3fn, scales [rows, D/32] uint8), bitwise
+    quant_mxfp8(layernorm_modulate(x, shift, scale)) without the bf16 tensor in between. out: an optional (q, scales) pair to write into."""
+    rows, D, ldx = _rowmajor2d(x, "x")
+    B, Ds, ldmod = _rowmajor2d(shift, "shift")
+    assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    q, s, ldq, lds = _mx_out_pair(out, rows, D, x.device, "layernorm_modulate_mxfp8")
+    lib = _lib.load()
+    _lib.check(lib.g3_layernorm_modulate_mxfp8(_dev(x, "x"), ldx, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, B,
+                                               _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, rows, D, eps, _stream()),
+               "g3_layernorm_modulate_mxfp8")
+    return q, s
+
+
 def posemb_layernorm_modulate(x: torch.Tensor, pe_t: torch.Tensor, pe_h: Optional[torch.Tensor], pe_w: Optional[torch.Tensor],
                               pos_norm: Optional[torch.Tensor], T: int, Hp: int, Wp: int, B: int, shift: torch.Tensor, scale: torch.Tensor,
                               out: Optional[torch.Tensor] = None, eps: float = 1e-6) -> torch.Tensor:
@@ -199,6 +255,30 @@ def posemb_layernorm_modulate(x: torch.Tensor, pe_t: torch.Tensor, pe_h: Optiona
                                                      T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
                                                      _dev(out, "out"), out.stride(0), D, eps, _stream()), "g3_posemb_layernorm_modulate_bf16")
     return out
+
+
+def posemb_layernorm_modulate_mxfp8(x: torch.Tensor, pe_t: torch.Tensor, pe_h: Optional[torch.Tensor], pe_w: Optional[torch.Tensor],
+                                    pos_norm: Optional[torch.Tensor], T: int, Hp: int, Wp: int, B: int, shift: torch.Tensor, scale: torch.Tensor,
+                                    out=None, eps: float = 1e-6):
+    """posemb_layernorm_modulate (x updated IN PLACE the same way) with the result as MXFP8: returns (q, scales) as layernorm_modulate_mxfp8."""
+    rows, D, ldx = _rowmajor2d(x, "x")
+    assert rows == T * Hp * Wp * B
+    if pe_h is None:
+        assert pe_w is None and pos_norm is None and pe_t.shape == (T * Hp * Wp, D) and pe_t.is_contiguous()
+    else:
+        for t, n in ((pe_t, T), (pe_h, Hp), (pe_w, Wp)):
+            assert t.dim() == 2 and t.shape[0] >= n and t.shape[1] == D and t.is_contiguous()
+        assert pos_norm.numel() == T * Hp * Wp and pos_norm.is_contiguous()
+    Bm, Ds, ldmod = _rowmajor2d(shift, "shift")
+    assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    q, s, ldq, lds = _mx_out_pair(out, rows, D, x.device, "posemb_layernorm_modulate_mxfp8")
+    lib = _lib.load()
+    _lib.check(lib.g3_posemb_layernorm_modulate_mxfp8(_dev(x, "x"), ldx, _dev(pe_t, "pe_t"), _dev(pe_h, "pe_h") if pe_h is not None else 0,
+                                                      _dev(pe_w, "pe_w") if pe_w is not None else 0, _dev(pos_norm, "pos_norm") if pos_norm is not None else 0,
+                                                      T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
+                                                      _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, D, eps, _stream()),
+               "g3_posemb_layernorm_modulate_mxfp8")
+    return q, s
 
 
 def qk_rmsnorm_rope(x: torch.Tensor, weight: torch.Tensor, cos: Optional[torch.Tensor], sin: Optional[torch.Tensor],

@@ -85,6 +85,17 @@ int g3_gemm_mxfp8_nt(const void* aq, int64_t lda, const void* as, int64_t ldas, 
  * refuses the shape or epilogue: profilers / tools only. */
 const char* g3_gemm_mxfp8_kernel_name(int M, int N, int K, int epilogue);
 
+/* g3_gemm_mxfp8_nt whose OUTPUT is MXFP8 as well: q_out [M][ldq] e4m3fn + s_out [M][lds] E8M0 are bitwise what g3_quant_mxfp8_bf16 makes of the
+ * bf16 C of g3_gemm_mxfp8_nt with the same epilogue (rounded to bf16 at the same points, then the same quantiser arithmetic, in the epilogue's
+ * registers: C itself is never written). For a producer whose only consumer is the next MXFP8 linear (the MLP: layer1 + GELU into layer2).
+ * Epilogues G3_EPI_NONE and G3_EPI_GELU only. Operands as g3_gemm_mxfp8_nt; ldq >= N a multiple of 8, lds >= N/32, q_out 8-byte aligned;
+ * anything else is refused with G3_ERR_ARG before any launch. Rows >= M of the outputs are not written. */
+int g3_gemm_mxfp8_nt_mxout(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws,
+                           void* q_out, int64_t ldq, void* s_out, int64_t lds, int M, int N, int K, int epilogue, void* stream);
+
+/* Name of the instantiation g3_gemm_mxfp8_nt_mxout launches ("gemm_mxfp8_nt_kernel<256 + epilogue>"), or NULL where it refuses: tools only. */
+const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int epilogue);
+
 /* out[M<=8][N] = (act_in(a) . w^T) (+ add): TimestepEmbedding (blocks.py:60-80) and adaLN_modulation
  * (blocks.py:411-415, 442-447; FinalLayer blocks.py:212-216, 230). act_in: 0 none, 1 SiLU. */
 int g3_gemv_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, const void* add, int64_t ldadd, void* out,
@@ -176,6 +187,13 @@ int g3_transpose_v_bf16(const void* v, int64_t ld_in, void* vt, int64_t ldvt, in
 int g3_layernorm_modulate_bf16(const void* x, int64_t ldx, const void* shift, const void* scale, int64_t ldmod,
                                int mod_rows, void* out, int64_t ldo, int rows, int D, float eps, void* stream);
 
+/* The same with the result as MXFP8 (opt-in MXFP8 linears): q [rows][ldq] e4m3fn + scales [rows][lds] E8M0, bitwise what g3_quant_mxfp8_bf16
+ * makes of g3_layernorm_modulate_bf16's `out` under the same "ln_wave_rows" option - each value is rounded to bf16 first, then quantised in the
+ * kernel's registers; no bf16 output is written. Refuses what the bf16 call refuses and D % 32 != 0, ldq < D, ldq % 8 != 0, lds < D/32,
+ * q not 8-byte aligned, NULL q / scales (G3_ERR_ARG before any launch). */
+int g3_layernorm_modulate_mxfp8(const void* x, int64_t ldx, const void* shift, const void* scale, int64_t ldmod, int mod_rows, void* q,
+                                int64_t ldq, void* scales, int64_t lds, int rows, int D, float eps, void* stream);
+
 /* per-head RMSNorm(weight[128], eps) then (optional) non-interleaved RoPE with f32 cos/sin tables [S][128]:
  * replaces te.pytorch.RMSNorm + apply_rotary_pos_emb(fused=True) in Attention.cal_qkv (attention.py:262-280).
  * in/out rows are (s, b) pairs, b fastest; cos_table == sin_table == NULL skips RoPE (cross-attention, k of context). */
@@ -211,6 +229,12 @@ int g3_gemm_qk_norm_rope_bf16(const void* A, int64_t lda, const void* W, int64_t
 int g3_posemb_layernorm_modulate_bf16(void* x, int64_t ldx, const void* pe_t, const void* pe_h, const void* pe_w,
                                       const void* pos_norm, int T, int Hp, int Wp, int B, const void* shift, const void* scale,
                                       int64_t ldmod, int mod_rows, void* out, int64_t ldo, int D, float eps, void* stream);
+
+/* g3_posemb_layernorm_modulate_bf16 with the result as MXFP8 (see g3_layernorm_modulate_mxfp8: same output rules and refusals); x is updated
+ * in place exactly as by the bf16 call. */
+int g3_posemb_layernorm_modulate_mxfp8(void* x, int64_t ldx, const void* pe_t, const void* pe_h, const void* pe_w, const void* pos_norm, int T,
+                                       int Hp, int Wp, int B, const void* shift, const void* scale, int64_t ldmod, int mod_rows, void* q,
+                                       int64_t ldq, void* scales, int64_t lds, int D, float eps, void* stream);
 
 /* x += y (n % 8 == 0): "x = x + extra_per_block_pos_emb" (blocks.py:547-548). */
 int g3_add_inplace_bf16(void* x, const void* y, int64_t n, void* stream);

@@ -9,6 +9,10 @@
                                                      alternating; steps/s of each arm
     python tools/mxfp8_ab.py --accum                  the scaled MFMA's accumulation error: the fa_qkv GEMM at M = 14 080 against the exact fp64
                                                      sum of the dequantised operands on sampled outputs, next to the bf16 GEMM on the same values
+    python tools/mxfp8_ab.py --producers [--steps N]  mxfp8_producers "separate" vs "fused" (default FILE profiles/r8_mxfp8_producers_ab.txt): launch by launch at
+                                                     M = 112 640 and 14 080 - LayerNorm + quantiser vs the LayerNorm that emits MXFP8, plain and with the position
+                                                     embedding, and the w1 GELU GEMM + quantiser vs w1 with MXFP8 output - then the full mxfp8 step with either
+                                                     setting (torch.equal of the two arms' x_t asserted after 2 steps; the kernel timers confirm which launches ran)
 Results are appended to FILE (default profiles/r7_mxfp8_ab.txt)."""
 import argparse
 import sys
@@ -124,6 +128,123 @@ def step(out, steps=3, rounds=3):
               f"steps/s {100 * (b / m - 1):+.1f} %, quantisation passes included; rel-L2 of the mxfp8 x_t after {steps} steps vs bf16 {rel:.3e}")
 
 
+def _bench_step_setup(dev):
+    """The bench workload of step(): the 28-block net as bench.py builds it and one denoise step's inputs."""
+    import numpy as np
+    from gen3c_amd.dit import VideoExtendGeneralDIT
+    from gen3c_amd.sampler import Gen3CDenoiser, VideoExtendCondition, add_condition_video_indicator_and_video_input_mask
+    net = VideoExtendGeneralDIT(in_channels=16 + 16 * 4 + 1, rope_t_extrapolation_ratio=2.0, num_blocks=28, device=dev, init_weights=False)
+    net.initialize_weights(randomize_adaln=True, seed=1234)
+    net.cross_attention_skip_zero_context = False
+    T, Hl, Wl, B = 16, 88, 160, 1
+    rs = np.random.RandomState(1)
+    normal = lambda shape, std: torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32)).to(torch.bfloat16).to(dev)  # noqa: E731
+    den = Gen3CDenoiser(net, state_shape=(16, T, Hl, Wl))
+    den.scheduler.set_timesteps(35)
+    xt = normal((B, 16, T, Hl, Wl), den.scheduler.init_noise_sigma)
+    gt, pose = normal((B, 16, T, Hl, Wl), 0.5), normal((B, 64, T, Hl, Wl), 0.5)
+    ctx = normal((B, 512, 1024), 0.2)
+    ctx[:, 64:] = 0
+    pad = torch.zeros(B, 1, 8 * Hl, 8 * Wl, device=dev, dtype=torch.bfloat16)
+    fps = torch.tensor([24.0], device=dev)
+
+    def make_cond(p):
+        c = VideoExtendCondition(crossattn_emb=ctx, crossattn_mask=None, padding_mask=pad, fps=fps, video_cond_bool=True, condition_video_pose=p)
+        return add_condition_video_indicator_and_video_input_mask(gt, c, 1)
+
+    return net, den, xt, make_cond(pose), make_cond(torch.zeros_like(pose))
+
+
+def producers(out, steps=3, rounds=3, iters=5):
+    """mxfp8_producers "separate" vs "fused": the four fused hand-overs launch by launch, then the step."""
+    dev = torch.device("cuda:0")
+    _log(out, f"== MXFP8 producers A/B ({torch.cuda.get_device_name(0)}, {time.strftime('%Y-%m-%d %H:%M')}): separate = bf16 producer + g3_quant_mxfp8_bf16, "
+              f"fused = the producer emits MXFP8; both warmed, {rounds} alternating rounds x {iters} launches, min of rounds (all rounds listed)")
+    fmt = lambda ts: " ".join(f"{t:.3f}" for t in ts)  # noqa: E731
+
+    def ab(label, sep, fused):
+        sep(), fused()
+        t_s, t_f = [], []
+        for _ in range(rounds):
+            t_s.append(timeit(sep, iters))
+            t_f.append(timeit(fused, iters))
+        s_, f_ = min(t_s), min(t_f)
+        _log(out, f"{label}: separate {s_:7.3f} ms | fused {f_:7.3f} ms | saved {s_ - f_:6.3f} ms ({s_ / f_:5.3f}x) (rounds separate {fmt(t_s)}, fused {fmt(t_f)})")
+
+    for M in (112640, 14080):
+        B = 2
+        Tp, Hp, Wp = (16, 44, 80) if M == 112640 else (2, 44, 80)
+        assert Tp * Hp * Wp * B == M
+        torch.manual_seed(M)
+        x = torch.randn(M, D, device=dev).to(torch.bfloat16)
+        shift = (0.5 * torch.randn(B, D, device=dev)).to(torch.bfloat16)
+        scale = (0.5 * torch.randn(B, D, device=dev)).to(torch.bfloat16)
+        pe = (0.3 * torch.randn(M // B, D, device=dev)).to(torch.bfloat16)
+        h = torch.empty(M, D, device=dev, dtype=torch.bfloat16)
+        pair = (torch.empty(M, D, device=dev, dtype=torch.float8_e4m3fn), torch.empty(M, D // 32, device=dev, dtype=torch.uint8))
+        ab(f"LayerNorm + modulate        M={M:6d} D={D}",
+           lambda: ops.quant_mxfp8(ops.layernorm_modulate(x, shift, scale, out=h), out=pair),
+           lambda: ops.layernorm_modulate_mxfp8(x, shift, scale, out=pair))
+        # the position-embedding form updates x in place: a zero table keeps x (and the work per launch) the same over the repetitions
+        pe.zero_()
+        ab(f"posemb LayerNorm + modulate M={M:6d} D={D}",
+           lambda: ops.quant_mxfp8(ops.posemb_layernorm_modulate(x, pe, None, None, None, Tp, Hp, Wp, B, shift, scale, out=h), out=pair),
+           lambda: ops.posemb_layernorm_modulate_mxfp8(x, pe, None, None, None, Tp, Hp, Wp, B, shift, scale, out=pair))
+        del h, pe
+        aq, as_ = ops.quant_mxfp8(x)
+        wq, ws = ops.quant_mxfp8((torch.randn(4 * D, D, device=dev) * 0.02).to(torch.bfloat16))
+        u = torch.empty(M, 4 * D, device=dev, dtype=torch.bfloat16)
+        upair = (torch.empty(M, 4 * D, device=dev, dtype=torch.float8_e4m3fn), torch.empty(M, 4 * D // 32, device=dev, dtype=torch.uint8))
+        ab(f"w1 (GELU) -> MXFP8          M={M:6d} N={4 * D} K={D}",
+           lambda: ops.quant_mxfp8(ops.gemm_mxfp8_nt(aq, as_, wq, ws, out=u, epilogue=ops.EPI_GELU), out=upair),
+           lambda: ops.gemm_mxfp8_nt(aq, as_, wq, ws, epilogue=ops.EPI_GELU, out_mx=upair))
+        t_plain = min(timeit(lambda: ops.gemm_mxfp8_nt(aq, as_, wq, ws, out=u, epilogue=ops.EPI_GELU), iters) for _ in range(rounds))
+        t_mxo = min(timeit(lambda: ops.gemm_mxfp8_nt(aq, as_, wq, ws, epilogue=ops.EPI_GELU, out_mx=upair), iters) for _ in range(rounds))
+        fl = 2.0 * M * 4 * D * D
+        _log(out, f"   the w1 GEMM alone            M={M:6d}: bf16 output {t_plain:7.3f} ms {fl / t_plain / 1e9:6.0f} TF | MXFP8 output {t_mxo:7.3f} ms "
+                  f"{fl / t_mxo / 1e9:6.0f} TF (the in-epilogue quantisation costs {t_mxo - t_plain:+.3f} ms against the bf16 store)")
+        del x, u, upair, aq, as_, wq, ws, pair
+        torch.cuda.empty_cache()
+
+    net, den, xt, cond, uncond = _bench_step_setup(dev)
+    net.set_linear_precision("mxfp8")
+
+    def run(arm, n):
+        net.set_mxfp8_producers(arm)
+        tm = ops.HipTimer()
+        x = xt
+        tm.start()
+        for i in range(n):
+            x = den.denoise_step(x, i, cond, uncond, 1.0, 0.001, 1)
+        tm.stop()
+        torch.cuda.synchronize()
+        return tm.elapsed_ms() / n, x
+
+    arms = ("separate", "fused")
+    two = {arm: run(arm, 2)[1] for arm in arms}  # warm-up of both arms, and the equality check
+    same = torch.equal(two["separate"], two["fused"])
+    _log(out, f"== full mxfp8 denoise step, mxfp8_producers separate vs fused: 28 blocks, latent 16x88x160, B = 1 (CFG branches batched: M = 112 640), dense "
+              f"context; x_t after 2 steps torch.equal between the arms: {same}")
+    assert same, "mxfp8_producers='fused' changed x_t"
+    del two
+    # which launches each arm runs, from the kernel timers of one step (the separate arm must be the parent commit's launch list: no *_mxout entry)
+    for arm in arms:
+        ops.enable_kernel_timers(True)
+        run(arm, 1)
+        names = [n for n, _, _ in ops.collected_kernel_timers()]
+        ops.enable_kernel_timers(False)
+        _log(out, f"kernel timers, one step, {arm:8s}: " + ", ".join(f"{names.count(n)} x {n}" for n in sorted(set(names))))
+    res = {arm: [] for arm in arms}
+    for _ in range(rounds):
+        for arm in arms:
+            res[arm].append(run(arm, steps)[0])
+    s_, f_ = min(res["separate"]), min(res["fused"])
+    spread = lambda ts: 100 * (max(ts) - min(ts)) / min(ts)  # noqa: E731
+    _log(out, f"separate {s_:8.1f} ms/step  {1000 / s_:.4f} steps/s  (rounds {' '.join(f'{t:.1f}' for t in res['separate'])}; spread {spread(res['separate']):.2f} %)")
+    _log(out, f"fused    {f_:8.1f} ms/step  {1000 / f_:.4f} steps/s  (rounds {' '.join(f'{t:.1f}' for t in res['fused'])}; spread {spread(res['fused']):.2f} %)  "
+              f"fused / separate steps/s {s_ / f_:.4f} ({100 * (s_ / f_ - 1):+.2f} %; derived expectation +2 to +2.5 %), {rounds} alternating rounds x {steps} steps")
+
+
 def accum(out):
     dev = torch.device("cuda:0")
     M, N, K = 14080, 3 * D, D
@@ -158,11 +279,16 @@ if __name__ == "__main__":
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--accum", action="store_true")
-    ap.add_argument("--out", default=str(ROOT / "profiles" / "r7_mxfp8_ab.txt"))
+    ap.add_argument("--producers", action="store_true")
+    ap.add_argument("--out", default=None, help="default: profiles/r7_mxfp8_ab.txt; --producers writes to profiles/r8_mxfp8_producers_ab.txt")
     args = ap.parse_args()
+    out_r7 = args.out or str(ROOT / "profiles" / "r7_mxfp8_ab.txt")  # the default is resolved per mode: each section keeps its own record
+    out_r8 = args.out or str(ROOT / "profiles" / "r8_mxfp8_producers_ab.txt")
     if args.classes or args.quant_only:
-        classes(args.out, quant_only=args.quant_only)
+        classes(out_r7, quant_only=args.quant_only)
     if args.accum:
-        accum(args.out)
+        accum(out_r7)
     if args.step:
-        step(args.out, steps=args.steps)
+        step(out_r7, steps=args.steps)
+    if args.producers:
+        producers(out_r8, steps=args.steps)

@@ -2,9 +2,10 @@
 product library against the same sources built with -DG3_AB_JITTER=<n> (pseudo-random waves sleep n*64 cycles at tile / phase
 boundaries) and demands BITWISE equal outputs.
   build (here, before gpurun):  python tools/race_screen.py --build [n]
-  run (GPU box):                python tools/race_screen.py"""
+  run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]"""
 import ctypes as C
 import math
+import os
 import sys
 from pathlib import Path
 
@@ -34,6 +35,7 @@ dev = torch.device("cuda:0")
 st = torch.cuda.current_stream().cuda_stream
 g = torch.Generator(device=dev).manual_seed(3)
 bad = 0
+ONLY_MX = "--mxfp8-producers-only" in sys.argv  # run only the last section (the launches that emit MXFP8)
 
 
 def both(fn):
@@ -52,7 +54,7 @@ def report(what, a, b):
 
 
 # ---- attention (long and short contexts, ragged tails, segmented V^T)
-for (Sq, Skv, H, segs) in [(56320, 56320, 4, 1), (7040, 56320, 4, 8), (1000, 449, 3, 1), (56320, 512, 8, 1), (300, 128, 2, 2)]:
+for (Sq, Skv, H, segs) in [] if ONLY_MX else [(56320, 56320, 4, 1), (7040, 56320, 4, 8), (1000, 449, 3, 1), (56320, 512, 8, 1), (300, 128, 2, 2)]:
     q = torch.randn(Sq, H * 128, device=dev, generator=g).to(torch.bfloat16)
     k = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
     v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
@@ -76,7 +78,7 @@ for (Sq, Skv, H, segs) in [(56320, 56320, 4, 1), (7040, 56320, 4, 8), (1000, 449
     del q, k, v, vt
 
 # ---- cross-attention form (round 6): Q norm inside the Q load + zero key tail in closed form
-for (Sq, Skv, H, live) in [(56320, 512, 8, 64), (1000, 512, 3, 0), (3000, 256, 2, 100)]:
+for (Sq, Skv, H, live) in [] if ONLY_MX else [(56320, 512, 8, 64), (1000, 512, 3, 0), (3000, 256, 2, 100)]:
     q = torch.randn(Sq, H * 128, device=dev, generator=g).to(torch.bfloat16)
     k = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
     v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
@@ -100,7 +102,7 @@ for (Sq, Skv, H, live) in [(56320, 512, 8, 64), (1000, 512, 3, 0), (3000, 256, 2
 
 # ---- carry-in form (g3_flash_attn_fwd_carry_bf16: the local_carry context-parallel schedule): an interior rank's ONE launch over every remote key,
 # its own key block skipped inside the gathered buffers, the own block's fp32 partial carried in; bf16 and fp32-partial outputs
-for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)]:
+for (Sl, nseg, rank, H) in [] if ONLY_MX else [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)]:
     Skv = Sl * nseg
     q = torch.randn(Sl, H * 128, device=dev, generator=g).to(torch.bfloat16)
     k = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
@@ -126,7 +128,7 @@ for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)]:
     del q, k, v, vt
 
 # ---- GEMM: every K-loop structure x epilogues x ragged shapes
-for (M, N, K, epi) in [(56320, 4096, 4096, 2), (7040, 12288, 4096, 0), (4096, 16384, 4096, 1), (3000, 4096, 16384, 2), (513, 264, 192, 3), (300, 520, 128, 0),
+for (M, N, K, epi) in [] if ONLY_MX else [(56320, 4096, 4096, 2), (7040, 12288, 4096, 0), (4096, 16384, 4096, 1), (3000, 4096, 16384, 2), (513, 264, 192, 3), (300, 520, 128, 0),
                        (256, 256, 64, 0), (8192, 12288, 4096, 0), (16384, 16384, 4096, 1), (8448, 4096, 2432, 2)]:
     a_ = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
     w_ = (torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16)
@@ -149,7 +151,7 @@ for (M, N, K, epi) in [(56320, 4096, 4096, 2), (7040, 12288, 4096, 0), (4096, 16
     del a_, w_, gate, res
 
 # ---- implicit-GEMM convolutions (tokenizer geometries: 1x3x3, causal 3x1x1, strided)
-for (C_in, C_out, T, Hh, Ww, kt, kh, kw, st_, sh, sw) in [(128, 256, 5, 48, 64, 1, 3, 3, 1, 1, 1), (256, 256, 6, 40, 48, 3, 1, 1, 1, 1, 1), (128, 128, 5, 48, 64, 1, 3, 3, 1, 2, 2),
+for (C_in, C_out, T, Hh, Ww, kt, kh, kw, st_, sh, sw) in [] if ONLY_MX else [(128, 256, 5, 48, 64, 1, 3, 3, 1, 1, 1), (256, 256, 6, 40, 48, 3, 1, 1, 1, 1, 1), (128, 128, 5, 48, 64, 1, 3, 3, 1, 2, 2),
                                                            (256, 256, 7, 24, 32, 3, 1, 1, 2, 1, 1)]:
     x_ = torch.randn(T * Hh * Ww, C_in, device=dev, generator=g).to(torch.bfloat16)
     w_ = (torch.randn(kt * kh * kw, C_out, C_in, device=dev, generator=g) / math.sqrt(C_in * kt * kh * kw)).to(torch.bfloat16)
@@ -172,7 +174,7 @@ for (C_in, C_out, T, Hh, Ww, kt, kh, kw, st_, sh, sw) in [(128, 256, 5, 48, 64, 
         x, y = both(run)
         report(f"conv {C_in}->{C_out} k=({kt},{kh},{kw}) s=({st_},{sh},{sw}) on {T}x{Hh}x{Ww} pingpong={pp} conv_w4={w4} residual={with_res}", x, y)
 # ---- split-KV attention: partial outputs + merge (round 3)
-for (Sq, Skv, H, variant) in [(7040, 14080, 4, 11), (7040, 14080, 4, 4), (1000, 448, 2, 4)]:
+for (Sq, Skv, H, variant) in [] if ONLY_MX else [(7040, 14080, 4, 11), (7040, 14080, 4, 4), (1000, 448, 2, 4)]:
     q = torch.randn(Sq, H * 128, device=dev, generator=g).to(torch.bfloat16)
     k = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
     v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
@@ -190,7 +192,7 @@ for (Sq, Skv, H, variant) in [(7040, 14080, 4, 11), (7040, 14080, 4, 4), (1000, 
     report(f"split-KV partial attention Sq={Sq} Skv={Skv} H={H} variant={variant}", a, b)
 # ---- the whole tokenizer at the size bench.py times it (round 4): 121 x 704 x 1280, channels = 128 - the 1.79 GB activations, the spatial attention's frames
 # on two streams with per-stream score buffers, GroupNorm statistics from conv epilogues, all 16 latent frames in the temporal attention
-if "--no-tokenizer" not in sys.argv:
+if "--no-tokenizer" not in sys.argv and not ONLY_MX:
     import bench  # noqa: E402
     from gen3c_amd.tokenizer import CausalVideoTokenizerNet  # noqa: E402
     for lib in (base, alt):
@@ -216,6 +218,46 @@ if "--no-tokenizer" not in sys.argv:
         report(f"tokenizer {what} 121x704x1280 channels=128, product vs jitter build", outs[0][i], outs[1][i])
         report(f"tokenizer {what} 121x704x1280 channels=128, product run twice", outs[0][i], outs[2][i])
     del outs, clip, tnet
+# ---- the producers that emit MXFP8 from their registers (mxfp8_producers = "fused"): the GEMM with MXFP8 output (its K loop carries the jitter; the epilogue
+# transposes through each wave's own LDS slice and quantises across lane quads) and the two LayerNorm forms, plain and with the position embedding
+LN_WAVE_START = int(os.environ.get("G3_LN_WAVE_ROWS", "0"))  # what both libraries start with (csrc/api.hip); restored after each case
+for (M, N, K, epi) in [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
+    aq, as_ = ops.quant_mxfp8(torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16))
+    wq, ws = ops.quant_mxfp8((torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16))
+
+    def run(lib):
+        q = torch.zeros(M, N, device=dev, dtype=torch.uint8)
+        s = torch.zeros(M, N // 32, device=dev, dtype=torch.uint8)
+        rc = lib.g3_gemm_mxfp8_nt_mxout(aq.data_ptr(), K, as_.data_ptr(), K // 32, wq.data_ptr(), K, ws.data_ptr(), K // 32, q.data_ptr(), N, s.data_ptr(), N // 32,
+                                        M, N, K, epi, st)
+        assert rc == 0, lib.g3_last_error()
+        return torch.cat([q.flatten(), s.flatten()])
+    a, b = both(run)
+    report(f"gemm_mxfp8 with MXFP8 output {M}x{N}x{K} epi{epi}", a, b)
+    del aq, as_, wq, ws
+for (T_, Hp, Wp, B_, D_, wave) in [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
+    rows = T_ * Hp * Wp * B_
+    x_ = torch.randn(rows, D_, device=dev, generator=g).to(torch.bfloat16)
+    pe = (0.3 * torch.randn(T_ * Hp * Wp, D_, device=dev, generator=g)).to(torch.bfloat16)
+    sh_ = (0.5 * torch.randn(B_, D_, device=dev, generator=g)).to(torch.bfloat16)
+    sc_ = (0.5 * torch.randn(B_, D_, device=dev, generator=g)).to(torch.bfloat16)
+    for posemb in (False, True):
+        def run(lib):
+            lib.g3_set_option(b"ln_wave_rows", wave)
+            xx = x_.clone()
+            q = torch.zeros(rows, D_, device=dev, dtype=torch.uint8)
+            s = torch.zeros(rows, D_ // 32, device=dev, dtype=torch.uint8)
+            if posemb:
+                rc = lib.g3_posemb_layernorm_modulate_mxfp8(xx.data_ptr(), D_, pe.data_ptr(), None, None, None, T_, Hp, Wp, B_, sh_.data_ptr(), sc_.data_ptr(), D_, B_,
+                                                            q.data_ptr(), D_, s.data_ptr(), D_ // 32, D_, 1e-6, st)
+            else:
+                rc = lib.g3_layernorm_modulate_mxfp8(xx.data_ptr(), D_, sh_.data_ptr(), sc_.data_ptr(), D_, B_, q.data_ptr(), D_, s.data_ptr(), D_ // 32, rows, D_, 1e-6, st)
+            assert rc == 0, lib.g3_last_error()
+            lib.g3_set_option(b"ln_wave_rows", LN_WAVE_START)
+            return torch.cat([q.flatten(), s.flatten(), xx.view(torch.uint8).flatten()])
+        a, b = both(run)
+        report(f"LayerNorm -> MXFP8 rows={rows} D={D_} {'wave' if wave else 'workgroup'} form{' + position embedding' if posemb else ''}", a, b)
+    del x_, pe, sh_, sc_
 for lib in (base, alt):
     lib.g3_set_option(b"attn_variant", 0)
     lib.g3_set_option(b"gemm_pingpong", 3)
