@@ -35,7 +35,15 @@ _FUSE_QKV_EPILOGUE = __import__("os").environ.get("G3_FUSE_QKV_EPILOGUE", "0") !
 # "token" operand is the weight and whose output rows are the 128 H value features - so it lands directly in the V^T [B, H, 128, S] layout the attention kernel reads and
 # the separate transpose pass (g3_transpose_v_bf16: 10.7 ms of a 3.3 s step) disappears. Same products, same K order per element: bitwise equal to the
 # transpose of the fused projection's v columns (tests/test_kernels_gpu.py). 0: fused [S*B, 3D] projection + transpose (A/B).
+# The swapped GEMM's output width is the token count S, and g3_gemm_bf16_nt stores 4 columns at a time (it refuses N % 4 != 0): a token count that is
+# no multiple of 4 (a 45 x 45 patch grid = 2025 tokens, ...) takes the fused projection + transpose whatever this switch says (_v_by_operand_swap).
 _V_OPERAND_SWAP = __import__("os").environ.get("G3_V_OPERAND_SWAP", "1") != "0"
+
+
+def _v_by_operand_swap(S: int) -> bool:
+    """True when the self-attention V projection of an S-token forward runs with the operands swapped (_V_OPERAND_SWAP): the switch is on
+    and S, the swapped GEMM's N, is a multiple of 4."""
+    return _V_OPERAND_SWAP and S % 4 == 0
 
 
 # 1 (default, round 6): the cross-attention's Q goes from the projection GEMM straight into the attention kernel, which applies to_q[1]'s per-head RMSNorm while
@@ -587,7 +595,7 @@ class VideoExtendGeneralDIT(nn.Module):
                     vt = self._vt_buffer(S, B, nH, dev)
                     qkv = ops.gemm_qk_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, vt=vt)
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
-                elif _V_OPERAND_SWAP:
+                elif _v_by_operand_swap(S):
                     # q | k: plain GEMM, then normalised + rotated IN PLACE by one pass; v: projected straight into V^T (operands swapped, see _V_OPERAND_SWAP)
                     qk = ops.gemm_nt(h, blk["fa_qkv"][:2 * D])
                     ops.qk_rmsnorm_rope_pair(qk, blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
@@ -596,7 +604,7 @@ class VideoExtendGeneralDIT(nn.Module):
                     hv = h.view(S, B, D)
                     for b_ in range(B):
                         ops.gemm_nt(blk["fa_qkv"][2 * D:], hv[:, b_], out=vt[b_].view(D, -1)[:, :S])
-                else:  # plain GEMM, then q / k normalised + rotated IN PLACE in the fused buffer and v transposed
+                else:  # (also every S % 4 != 0) plain GEMM, then q / k normalised + rotated IN PLACE in the fused buffer and v transposed
                     qkv = ops.gemm_nt(h, blk["fa_qkv"])
                     ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)  # one pass over q | k
                     q, k = qkv[:, :D], qkv[:, D:2 * D]

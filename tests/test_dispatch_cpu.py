@@ -66,3 +66,17 @@ def test_cache_keys_work_on_inference_tensors():
                                     adaln_lora_dim=8, crossattn_emb_channels=16, device="cpu", init_weights=True)
         k1 = net._weights_key()  # parameters created under inference mode
     assert k1 == net._weights_key()
+
+
+def test_v_projection_takes_the_operand_swap_only_at_token_counts_the_gemm_accepts(monkeypatch):
+    """dit.py: _v_by_operand_swap - the swapped V GEMM's output width is the token count S and g3_gemm_bf16_nt refuses N % 4 != 0, so the arm is taken
+    exactly at S % 4 == 0 with the switch on (45 x 45 patches = 2025 and 47 x 47 = 2209 tokens fall back; the benchmark's 56 320 swap), never with it off."""
+    from gen3c_amd import dit
+    sizes = list(range(1, 131)) + [2025, 2209, 56320]
+    monkeypatch.setattr(dit, "_V_OPERAND_SWAP", True)
+    for S in sizes:
+        assert dit._v_by_operand_swap(S) is (S % 4 == 0), S
+    assert not dit._v_by_operand_swap(2025) and not dit._v_by_operand_swap(2209) and dit._v_by_operand_swap(56320)
+    monkeypatch.setattr(dit, "_V_OPERAND_SWAP", False)
+    for S in sizes:
+        assert dit._v_by_operand_swap(S) is False, S

@@ -74,16 +74,19 @@ def test_gemm_full_size_sampled_rows_and_row_subsets(N, K, epi):
 
 
 def _bench_launch_operands(dev, H=32, B=2, seed=11, chain="default"):
-    """The operands of the benchmark's self-attention launch, produced the way the DiT forward produces them (gen3c_amd/dit.py, the branch
-    `_FUSE_QKV_EPILOGUE` selects; chain="default" follows the product's default, whatever it is):
-      * "separate" (the default since round 3): ONE plain QKV projection into a [S*B, 3*H*128] buffer, then q and k normalised + rotated IN PLACE
-        by g3_qk_rmsnorm_rope_bf16 on strided column views of it and the v columns transposed into V^T by g3_transpose_v_bf16;
-      * "fused": g3_gemm_qk_norm_rope_bf16 does all three in the projection's epilogue.
-    Either way q / k handed to the attention kernel are strided column views of the buffer (k offsets reach 2.77 GB of the kernel's 32-bit
-    byte-offset budget at H = 32, B = 2; the in-place norm passes address the same range)."""
+    """The operands of the benchmark's self-attention launch, produced the way the DiT forward produces them (gen3c_amd/dit.py, the arms of the
+    self-attention block; chain="default" resolves through the predicates forward() itself uses, so it follows the product's default, whatever it is):
+      * "swap" (the default since round 6, dit._v_by_operand_swap): the q | k projection on the first 2 D rows of the fused weight, q and k normalised +
+        rotated IN PLACE by ONE pass (g3_qk_rmsnorm_rope_pair_bf16), and V projected with the operands swapped, one GEMM per batch item (N = S,
+        ldw = B D) straight into vt[b][:, :S];
+      * "separate" (G3_V_OPERAND_SWAP=0, and every S % 4 != 0): ONE plain QKV projection into a [S*B, 3*H*128] buffer, then q and k normalised + rotated
+        IN PLACE on strided column views of it and the v columns transposed into V^T by g3_transpose_v_bf16;
+      * "fused" (G3_FUSE_QKV_EPILOGUE=1): g3_gemm_qk_norm_rope_bf16 does all three in the projection's epilogue.
+    In every chain q / k handed to the attention kernel are strided column views of the buffer `qkv` ([S*B, 2 D] in "swap", [S*B, 3 D] otherwise; k offsets
+    reach 2.77 GB of the kernel's 32-bit byte-offset budget at H = 32, B = 2 in the 3 D form; the in-place norm passes address the same range)."""
     from gen3c_amd import dit, ops
     if chain == "default":
-        chain = "fused" if dit._FUSE_QKV_EPILOGUE else "separate"
+        chain = "fused" if dit._FUSE_QKV_EPILOGUE else ("swap" if dit._v_by_operand_swap(S) else "separate")
     g = torch.Generator(device=dev).manual_seed(seed)
     Dm = H * HD
     h = torch.randn(S * B, Dm, device=dev, generator=g).to(torch.bfloat16)
@@ -96,6 +99,12 @@ def _bench_launch_operands(dev, H=32, B=2, seed=11, chain="default"):
     vt = torch.zeros(B, H, HD, ops.ceil_to(S, 64), device=dev, dtype=torch.bfloat16)
     if chain == "fused":
         qkv = ops.gemm_qk_norm_rope(h, w, Dm, Dm, nq, nk, cos, sin, S, B, vt=vt)
+    elif chain == "swap":
+        qkv = ops.gemm_nt(h, w[:2 * Dm])
+        ops.qk_rmsnorm_rope_pair(qkv, nq, H, nk, H, cos, sin, S, B)
+        hv = h.view(S, B, Dm)
+        for b_ in range(B):
+            ops.gemm_nt(w[2 * Dm:], hv[:, b_], out=vt[b_].view(Dm, -1)[:, :S])
     else:
         assert chain == "separate"
         qkv = ops.gemm_nt(h, w)
@@ -117,7 +126,7 @@ def test_bench_attention_launch_w4b_xcd_grid_vs_fp32():
     op = _bench_launch_operands(dev, H, B)
     Dm, qkv, vt = op["Dm"], op["qkv"], op["vt"]
     q, k = qkv[:, :Dm], qkv[:, Dm:2 * Dm]
-    assert q.stride(0) == 3 * Dm and k.data_ptr() - qkv.data_ptr() == 2 * Dm  # strided views, nothing repacked
+    assert q.stride(0) == qkv.shape[1] and qkv.shape[1] in (2 * Dm, 3 * Dm) and k.data_ptr() - qkv.data_ptr() == 2 * Dm  # strided views, nothing repacked
     ops.enable_kernel_timers(True)
     out = ops.flash_attn(q, k, vt, S, S, B, H)
     launched = [m for (n, m, _t) in ops.collected_kernel_timers() if n == "flash_attn_fwd"]
@@ -140,17 +149,16 @@ def test_bench_attention_launch_w4b_xcd_grid_vs_fp32():
     print(f"[bench attention launch w4b<true> S=56320 H=32 B=2] worst rel-L2 over 8 (batch, head) pairs = {worst:.3e}")
 
 
-@pytest.mark.parametrize("chain", ["separate", "fused"])
+@pytest.mark.parametrize("chain", ["separate", "fused", "swap"])
 def test_bench_qkv_epilogue_vs_fp32_norm_rope(chain):
-    """Both forms of the QKV chain at the benchmark size (S = 56 320, B = 2, D = 4096) - "separate" = what the DiT forward runs by default (plain
-    projection, in-place norm + RoPE passes over 2.77 GB of strided views, V transpose), "fused" = the opt-in epilogue - against an fp32 evaluation
-    of Attention.cal_qkv (attention.py:247-280: Linear, per-head RMSNorm with weight, non-interleaved RoPE; v plain) on sampled rows, and against
-    each other (same rounding points; the sum of squares is accumulated in another order)."""
-    from gen3c_amd import dit
+    """The three forms of the QKV chain at the benchmark size (S = 56 320, B = 2, D = 4096) - "swap" = what the DiT forward runs by default (q | k
+    projection + one in-place norm + RoPE pass, V by two operand-swapped GEMMs at N = 56 320, ldw = B D), "separate" = plain projection, in-place norm +
+    RoPE passes over 2.77 GB of strided views, V transpose, "fused" = the opt-in epilogue - against an fp32 evaluation of Attention.cal_qkv
+    (attention.py:247-280: Linear, per-head RMSNorm with weight, non-interleaved RoPE; v plain) on sampled rows, and against each other ("swap" is
+    bitwise "separate"; "fused" has the same rounding points with the sum of squares accumulated in another order)."""
     from oracle import dit_oracle
     dev = torch.device("cuda:0")
     H, B = 32, 2
-    assert ("fused" if dit._FUSE_QKV_EPILOGUE else "separate") in ("separate", "fused")
     op = _bench_launch_operands(dev, H, B, seed=12, chain=chain)
     Dm, qkv, vt = op["Dm"], op["qkv"], op["vt"]
     g = torch.Generator(device=dev).manual_seed(5)
@@ -178,6 +186,12 @@ def test_bench_qkv_epilogue_vs_fp32_norm_rope(chain):
         assert torch.equal(other["vt"], vt)
         r = _rel_l2(other["qkv"][:, :2 * Dm], qkv[:, :2 * Dm])
         assert r < 1e-3, f"fused vs separate chain: rel-L2 {r:.3e}"
+    if chain == "swap":
+        # same products in the same K order per element, the same norm + RoPE kernel on the same q | k values: V^T (its zero tail included) and q | k are
+        # the transpose chain's bits ("bitwise")
+        other = _bench_launch_operands(dev, H, B, seed=12, chain="separate")
+        assert torch.equal(vt, other["vt"]), "V^T of the operand-swap chain differs from the GEMM + transpose chain's"
+        assert qkv.shape == (S * B, 2 * Dm) and torch.equal(qkv, other["qkv"][:, :2 * Dm])
 
 
 def test_dit_full_size_single_block_vs_fp32_oracle():

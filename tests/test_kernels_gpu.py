@@ -174,7 +174,9 @@ def attn_variant(request):
 
 @pytest.mark.parametrize("Sq,Skv,B,H", [(256, 256, 1, 1), (512, 512, 1, 2), (300, 200, 1, 2), (96, 40, 2, 3), (1024, 512, 1, 4),
                                          (2048, 2048, 1, 2), (64, 64, 1, 1), (64, 65, 1, 1), (100, 128, 1, 1), (70, 129, 1, 1),
-                                         (512, 4160, 1, 1), (128, 192, 1, 1), (128, 250, 1, 1), (128, 320, 1, 2), (64, 449, 1, 1)])
+                                         (512, 4160, 1, 1), (128, 192, 1, 1), (128, 250, 1, 1), (128, 320, 1, 2), (64, 449, 1, 1),
+                                         # self-attention shapes, Sq = Skv odd (the token counts of tests/test_dit_shapes_gpu.py): below one tile, ragged, past 2048
+                                         (25, 25, 1, 1), (189, 189, 2, 2), (2209, 2209, 2, 2)])
 def test_flash_attn(Sq, Skv, B, H, attn_variant):
     from gen3c_amd import ops
     dev = _dev()
@@ -282,15 +284,15 @@ def test_flash_attn_segmented_vt_matches_plain():
 def test_flash_attn_one_wave_per_simd_long_context(variant):
     """The one-wave-per-SIMD kernels (attention_w4.hpp / attention_w4b.hpp) on what their hand-laid tile stream has to get right: many tiles
     (ring slots and LDS-DMA bases wrap), keys whose scores tower over the running maximum late in the context (rescale branch with fragment
-    reads in flight), an odd and an even number of tiles, query counts that do not fill the last workgroup, batch > 1, strided views, and
-    V^T handed over in key segments (bit-identical to the contiguous layout)."""
+    reads in flight), an odd and an even number of tiles, an odd key count (2209 = 47 x 47: ragged last tile), query counts that do not fill the last
+    workgroup, batch > 1, strided views, and V^T handed over in key segments (bit-identical to the contiguous layout)."""
     from gen3c_amd import ops
     dev = _dev()
     ops.set_option("attn_variant", variant)
     try:
         g = torch.Generator(device=dev).manual_seed(1234 + variant)
         for (Sq, Skv, B, H, qscale, spikes) in [(300, 4160, 1, 2, 1.0, ()), (256, 3008, 2, 2, 1.0, (2900,)), (96, 2624, 1, 1, 6.0, (70, 2500)), (520, 8256, 1, 3, 1.0, (40, 8200)),
-                                                (64, 64, 1, 1, 1.0, ()), (130, 128, 1, 2, 1.0, (100,))]:
+                                                (64, 64, 1, 1, 1.0, ()), (130, 128, 1, 2, 1.0, (100,)), (189, 2209, 2, 2, 1.0, (2150,))]:
             W = H * 128
             big = torch.randn(max(Sq, Skv) * B, 3 * W, device=dev, generator=g).to(torch.bfloat16)
             q, k, v = (big[:Sq * B, :W] * qscale).to(torch.bfloat16), big[:Skv * B, W:2 * W], big[:Skv * B, 2 * W:]
@@ -429,11 +431,12 @@ def test_cross_attention_q_norm_inside_the_kernel(Sq, Skv, B, H, live):
     assert r_fused < 6e-3 and r_fused <= 1.2 * r_sep + 1e-4 and r_both < 2e-3
 
 
-@pytest.mark.parametrize("S,B,H,K", [(512, 2, 4, 512), (1000, 2, 2, 256), (4096, 1, 8, 1024), (2048, 2, 16, 4096)])
+@pytest.mark.parametrize("S,B,H,K", [(512, 2, 4, 512), (1000, 2, 2, 256), (4096, 1, 8, 1024), (2048, 2, 16, 4096), (180, 2, 2, 256)])
 def test_v_projection_by_operand_swap_is_the_transposed_projection(S, B, H, K):
     """Round 6 (gen3c_amd/dit.py: _V_OPERAND_SWAP): V^T[b] = W_v . h[:, b]^T - the V projection with the GEMM's operands swapped, one launch per batch item,
     written straight into the V^T [B, H, 128, ld] buffer - is BITWISE the transpose pass applied to the fused projection's v columns (same products,
-    same K order per element), on shapes that run the deferred-epilogue kernel (2048 x 2 x 16 heads x K 4096), the plain one-wave kernel and ragged tiles."""
+    same K order per element), on shapes that run the deferred-epilogue kernel (2048 x 2 x 16 heads x K 4096), the plain one-wave kernel and ragged tiles
+    (180 tokens: S % 4 == 0 but no whole 64-key tile, so the V^T rows keep a zero tail the swapped GEMM must not touch)."""
     from gen3c_amd import ops
     dev = _dev()
     g = torch.Generator(device=dev).manual_seed(S + H + K)
@@ -451,6 +454,24 @@ def test_v_projection_by_operand_swap_is_the_transposed_projection(S, B, H, K):
     assert torch.equal(vt, ref)
     qk = ops.gemm_nt(h, w[:2 * D])
     assert torch.equal(qk, qkv[:, :2 * D]), "a row slice of the fused weight gives the same q | k columns"
+
+
+def test_v_projection_by_operand_swap_is_refused_at_a_token_count_that_is_no_multiple_of_4():
+    """The guard in gen3c_amd/dit.py (_v_by_operand_swap) relies on this: the swapped V GEMM at N = S with S % 4 != 0 raises (g3_gemm_bf16_nt stores 4
+    columns at a time) instead of writing anything - the V^T buffer, tail included, is left as it was."""
+    from gen3c_amd import _lib, ops
+    dev = _dev()
+    S, B, H, K = 189, 2, 2, 256
+    D, ld = H * 128, ops.ceil_to(S, 64)
+    g = torch.Generator(device=dev).manual_seed(S)
+    h = torch.randn(S * B, K, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(D, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16)
+    vt = torch.full((B, H, 128, ld), 3.0, device=dev, dtype=torch.bfloat16)
+    for b in range(B):
+        with pytest.raises(_lib.Gen3cHipError, match=r"g3_gemm_bf16_nt: need .*N.* % 4"):
+            ops.gemm_nt(w, h.view(S, B, K)[:, b], out=vt[b].view(D, ld)[:, :S])
+    torch.cuda.synchronize()
+    assert bool((vt == 3.0).all())
 
 
 @pytest.mark.parametrize("S,B,Hq,Hk,rope", [(333, 2, 8, 8, True), (130, 1, 16, 8, True), (97, 2, 8, 24, False), (1000, 2, 32, 32, True)])

@@ -7,18 +7,13 @@ arithmetic adds its own distance r_bf16, measured in the same test as the bf16 n
   (a) against the fake-quantised oracle: rel-L2 <= 1.5 (r_bf16 + 1.44e-3);
   (b) against the plain fp32 oracle (the recorded quality bar): rel-L2 <= 1.5 (r_bf16 + 2.86e-3).
 """
-import types
-
 import pytest
 import torch
-import torch.nn.functional as F
 
-from tests.mxfp8_ref import fake_quant
+from tests._mxfp8_tiny_dit import _oracle  # the fake-quantised oracle, shared with tests/test_dit_shapes_gpu.py
 
 pytestmark = pytest.mark.gpu
 
-MX_KEYS = ("0.block.attn.to_q.0.weight", "0.block.attn.to_k.0.weight", "0.block.attn.to_v.0.weight", "0.block.attn.to_out.0.weight",
-           "1.block.attn.to_q.0.weight", "1.block.attn.to_out.0.weight", "2.block.layer1.weight", "2.block.layer2.weight")
 EMU_FLIPS, EMU_QUANT = 1.44e-3, 2.86e-3
 
 
@@ -49,29 +44,6 @@ def _run(net, inp, dev):
     y = net(crossattn_mask=None, **{k: v.to(dev) for k, v in inp.items()})
     torch.cuda.synchronize()
     return y
-
-
-def _oracle(sd, inp, fake=False, bf16_inputs=False):
-    """fp32 oracle; fake=True: the six block linears see MXFP8 fake-quantised inputs and weights (oracle/ untouched: its F is swapped here)."""
-    from oracle import dit_oracle
-    ids = {id(v) for k, v in sd.items() if k.startswith("blocks.") and k.split(".blocks.", 1)[-1] in MX_KEYS}
-
-    def linear(x, w, b=None):
-        if id(w) in ids:
-            xin = x.to(torch.bfloat16).float() if bf16_inputs else x
-            return F.linear(fake_quant(xin), fake_quant(w), b)
-        return F.linear(x, w, b)
-
-    saved = dit_oracle.F
-    if fake:
-        dit_oracle.F = types.SimpleNamespace(**{n: getattr(F, n) for n in dir(F) if not n.startswith("__")})
-        dit_oracle.F.linear = linear
-    try:
-        f = lambda t: t.float()
-        return dit_oracle.dit_forward(sd, f(inp["x"]), f(inp["timesteps"]), f(inp["crossattn_emb"]), f(inp["condition_video_input_mask"]),
-                                      f(inp["condition_video_pose"]), f(inp["padding_mask"]), inp["fps"], num_blocks=2, num_heads=2)
-    finally:
-        dit_oracle.F = saved
 
 
 def _rel(a, b):
