@@ -73,6 +73,9 @@ struct AttnParams {
     const float* carry_lse;
     int kv_skip_begin, kv_skip_len;
     uint32_t kv_skip_vt_bytes;
+    // no-max form (flash_attn_fwd_w4b_nm_kernel; g3_self_attn_fwd_bounded_bf16): the caller's bound on |q.k| * scale_log2, the constant reference point of
+    // the softmax. No other kernel reads it.
+    float logit_bound_log2;
 };
 
 G3_DEVICE int k_off(int row, int chunk) { return row * HD + ((chunk ^ (row & 15)) << 3); }          // [64][128]
@@ -1003,11 +1006,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 
 #include "attention_w4.hpp"
+#define W4B_NM 0
 #define W4B_CP 0
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_kernel
 #undef W4B_CP
 #define W4B_CP 1
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_carry_kernel: the same kernel with the CP form (carry-in + skipped key range)
+#undef W4B_CP
+#undef W4B_NM
+#define W4B_CP 0
+#define W4B_NM 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_kernel: the same kernel without the running row maximum (bounded logits)
+#undef W4B_NM
 #undef W4B_CP
 
 }  // namespace
@@ -1044,12 +1054,23 @@ extern "C" const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int 
 
 extern "C" const char* g3_flash_attn_kernel_name(int Sq, int Skv, int B, int H) { return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, 0); }
 
+// The no-max form's range: P >= 2^(-2 bound) must stay a normal fp32 with room to spare (v_exp_f32 and the MFMA flush below 2^-126).
+constexpr float NM_BOUND_LOG2_MAX = 60.0f;
+static float attn_bound_log2(float logit_bound) { return logit_bound * 1.4426950408889634f; }
+static bool attn_bound_usable(float bound_log2) { return bound_log2 > 0.f && bound_log2 <= NM_BOUND_LOG2_MAX; }  // (false for NaN)
+
+extern "C" const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant) {
+    if (attn_resolve_variant(Sq, Skv, B, H, variant) == 11 && attn_bound_usable(attn_bound_log2(logit_bound))) return "flash_attn_fwd_w4b_nm_kernel<true>";
+    return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, variant);
+}
+
 static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
                              int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                              int64_t vt_seg_stride, void* o, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H,
                              int head_dim, float softmax_scale, void* stream, int variant_req = 0, float* o_partial = nullptr, float* lse = nullptr, int kv_dense = 0,
                              const void* q_norm_w = nullptr, float q_norm_eps = 0.f, bool cp_form = false, const float* carry_o = nullptr,
-                             const float* carry_lse = nullptr, int kv_skip_begin = 0, int kv_skip_len = 0, uint32_t kv_skip_vt_bytes = 0) {
+                             const float* carry_lse = nullptr, int kv_skip_begin = 0, int kv_skip_len = 0, uint32_t kv_skip_vt_bytes = 0,
+                             float logit_bound = 0.f) {
     if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: null operand");
     if ((o_partial != nullptr) != (lse != nullptr)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial and lse go together");
     if (o_partial && (((uintptr_t)o_partial & 15) || ((uintptr_t)lse & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: misaligned o_partial / lse");
@@ -1084,6 +1105,7 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     p.q_norm_w = (const bf16_t*)q_norm_w; p.q_norm_eps = q_norm_eps;
     p.carry_o = carry_o; p.carry_lse = carry_lse;
     p.kv_skip_begin = kv_skip_begin; p.kv_skip_len = kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
+    p.logit_bound_log2 = attn_bound_log2(logit_bound);
     if (q_norm_w && ((uintptr_t)q_norm_w & 15)) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: misaligned q_norm_weight");
     const size_t smem = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
     static bool attr_set[64] = {};  // per device: hipFuncSetAttribute applies to the current device only
@@ -1130,7 +1152,7 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     {
       std::lock_guard<std::mutex> attr_lock(attr_mu);
       if (!attr_set[dev_id]) {
-        const void* fns[19] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
+        const void* fns[20] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_kernel<true>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<2, 6, 8, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<3, 6, 8, false>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<false>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_kernel<1>),
@@ -1140,7 +1162,7 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false, true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<1>)};
-        for (int i = 0; i < 19; ++i) {
+        for (int i = 0; i < 20; ++i) {
             hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
@@ -1155,7 +1177,10 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         p.grid_q = (int)grid4.x; p.n_hb = H * B; p.n_heads = H;
         p.xcd_heads = (g3_opt_attn_xcd_heads && (H * B) % 8 == 0) ? 1 : 0;
         if (p.xcd_heads) grid4 = dim3(grid4.x * H * B, 1, 1);
-        if (cp_form) hipLaunchKernelGGL(flash_attn_fwd_w4b_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        // bounded logits (g3_self_attn_fwd_bounded_bf16): the no-max form, for the plain XB kernel's problems only; everything else runs as it always did
+        const bool no_max = variant == 11 && !cp_form && vt_seg_len == 0 && !p.kv_dense && attn_bound_usable(p.logit_bound_log2);
+        if (no_max) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        else if (cp_form) hipLaunchKernelGGL(flash_attn_fwd_w4b_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else if (variant == 11) hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<false>, grid4, dim3(W4_THREADS), smem, st, p);
         return g3_check_launch("g3_flash_attn_fwd_bf16");
@@ -1220,6 +1245,20 @@ extern "C" int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q
     if (o_partial && ((o_row & 3) || (o_batch & 3) || (o_head & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial strides must be multiples of 4");
     return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
                              o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse);
+}
+
+/* ---- self-attention with bounded logits: the no-max form of the one-wave-per-SIMD kernel where it applies, else exactly g3_flash_attn_fwd_ex_bf16 -------- */
+extern "C" int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                             int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                             int vt_seg_len, int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row,
+                                             int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale,
+                                             float logit_bound, int variant, void* stream) {
+    if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: variant %d out of range", variant);
+    if (o && o_partial) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: pass either o (bf16 result) or o_partial + lse, not both");
+    if (o_partial && ((o_row & 3) || (o_batch & 3) || (o_head & 3))) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: o_partial strides must be multiples of 4");
+    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
+                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse, 0, nullptr, 0.f, false, nullptr, nullptr, 0, 0, 0u,
+                             logit_bound);
 }
 
 /* ---- carry-in state + skipped key range (context parallelism without a merge pass) --------------------------------------------------------- */

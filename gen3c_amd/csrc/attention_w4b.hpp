@@ -1,5 +1,6 @@
-// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace - twice: W4B_CP 0 defines the helpers and
-// flash_attn_fwd_w4b_kernel, W4B_CP 1 flash_attn_fwd_w4b_carry_kernel (the CP form, see below; the plain kernel compiles without it).
+// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace - three times: W4B_CP 0 defines the helpers and
+// flash_attn_fwd_w4b_kernel, W4B_CP 1 flash_attn_fwd_w4b_carry_kernel (the CP form, see below; the plain kernel compiles without it),
+// W4B_NM 1 flash_attn_fwd_w4b_nm_kernel (the no-max form, see below).
 //
 // w4b: the one-wave-per-SIMD self-attention kernel (see attention_w4.hpp for the why) with the issue stream of a tile trimmed to what the
 // SIMD can hide under its MFMAs (MI355X_MICROARCH.md: <= 5 single-issue instructions per 32-cycle MFMA gap at one wave per SIMD; the w4
@@ -24,6 +25,11 @@
 // CP (flash_attn_fwd_w4b_carry_kernel, g3_flash_attn_fwd_carry_bf16 only): a skipped key range - logical
 // 64-key tile t is read at physical tile t + (t >= skip tile ? skipped tiles : 0), one more term in the K tile address and one more jump in the
 // V^T walk - and a carry-in state of the same rows folded in by the epilogue. The tile loop itself is the plain kernel's.
+// NM (flash_attn_fwd_w4b_nm_kernel, g3_self_attn_fwd_bounded_bf16 only; XB form): the caller guarantees |q.k| * scale * log2(e) <=
+// AttnParams::logit_bound_log2 (per-head RMSNorm of q and k bounds it), so the reference point of the softmax is that
+// constant instead of a running row maximum: every P = exp2(s - bound) lies in [2^(-2 bound), 1], nothing is ever rescaled, and the tile
+// loses the 32 v_max3 of the chains, the fold / lane exchange of steps 14, 15 (bare P.V steps that keep the read-ahead) and the rescale test
+// with the branch behind it. Softmax does not depend on its reference point; the epilogues (LSE = m_run - log2(1 / l)) are the plain kernel's.
 
 #ifndef G3_ATTENTION_W4B_HELPERS
 #define G3_ATTENTION_W4B_HELPERS
@@ -204,7 +210,9 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 // starts with its operands in the ring; the four pair units that covered the head reads move into region A as half units.
 #endif  // G3_ATTENTION_W4B_HELPERS
 
-#if W4B_CP
+#if W4B_NM
+#define W4B_KERNEL flash_attn_fwd_w4b_nm_kernel
+#elif W4B_CP
 #define W4B_KERNEL flash_attn_fwd_w4b_carry_kernel
 #else
 #define W4B_KERNEL flash_attn_fwd_w4b_kernel
@@ -212,6 +220,8 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 template <bool XB>
 __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     constexpr bool CP = W4B_CP;
+    constexpr bool NM = W4B_NM;
+    static_assert(!NM || (XB && !CP), "the no-max form exists for the plain XB kernel only");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
     bf16_t* sV = sK + 2 * KVB * HD;                     // [2][128][64]
@@ -251,6 +261,12 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
         skip_nt = (uint32_t)p.kv_skip_len / KVB;
         v_skip = p.kv_skip_vt_bytes;
         asm volatile("" : "+s"(carry_o), "+s"(carry_lse), "+s"(skip_t0), "+s"(skip_nt), "+s"(v_skip));
+    }
+    // NM: the logit bound (log2 domain), fetched here for the same reason
+    float bound = 0.f;
+    if constexpr (NM) {
+        bound = p.logit_bound_log2;
+        asm volatile("" : "+s"(bound));
     }
     auto k_tile = [&](uint32_t t) -> uint32_t {  // physical K tile of logical tile t
         if constexpr (CP) return t + (t >= skip_t0 ? skip_nt : 0u);
@@ -325,7 +341,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     float xa[2], xb[2];                            // XB: exp2 results of a half unit between its two steps
     const int nt = p.Skv / KVB;                     // launcher: S_kv % 64 == 0
 
-    // ---- prologue: K(0), V(0) (and K(1)) by LDS-DMA; scores of tile 0 with C = 0, then made relative to their exact row maximum
+    // ---- prologue: K(0), V(0) (and K(1)) by LDS-DMA; scores of tile 0 with C = 0, then made relative to their exact row maximum (NM: to the bound)
     dma_tile_builtin(Kbytes, dma_off, sK);
     dma_tile_builtin(Vbytes, dma_off + 4, sV);
     if (nt > 1) dma_tile_builtin(Kbytes + k_tile(1u) * k_tile_bytes, dma_off, sK + KVB * HD);
@@ -354,14 +370,18 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     __syncthreads();  // K(0)'s slot is the destination of the first LDS-DMA of the tile loop (K(2)): every wave must be done reading it
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        float ma = max3(SA[h][0][0], SA[h][0][1], SA[h][0][2]);
-        float mb2 = max3(SA[h][1][0], SA[h][1][1], SA[h][1][2]);
+        if constexpr (NM) {
+            m_run[h] = bound;
+        } else {
+            float ma = max3(SA[h][0][0], SA[h][0][1], SA[h][0][2]);
+            float mb2 = max3(SA[h][1][0], SA[h][1][1], SA[h][1][2]);
 #pragma unroll
-        for (int r = 3; r < 15; r += 2) {
-            ma = max3(ma, SA[h][0][r], SA[h][0][r + 1]);
-            mb2 = max3(mb2, SA[h][1][r], SA[h][1][r + 1]);
+            for (int r = 3; r < 15; r += 2) {
+                ma = max3(ma, SA[h][0][r], SA[h][0][r + 1]);
+                mb2 = max3(mb2, SA[h][1][r], SA[h][1][r + 1]);
+            }
+            m_run[h] = xor32_max(max3(ma, mb2, max3(SA[h][0][15], SA[h][1][15], SA[h][1][15])));
         }
-        m_run[h] = xor32_max(max3(ma, mb2, max3(SA[h][0][15], SA[h][1][15], SA[h][1][15])));
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
@@ -370,6 +390,9 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
         for (int r = 0; r < 16; ++r) negm[h][r] = -m_run[h];
         mx_cur[h] = 0.f;
     }
+    // NM: every element of negm is the same wave-uniform constant, which hipcc would otherwise keep in SGPRs and copy into the C operand's VGPRs once
+    // per tile pair (8 v_mov_b64 in the loop): opaque, so that the 32 VGPRs stay resident as they do in the plain kernel
+    if constexpr (NM) asm volatile("" : "+v"(negm[0]), "+v"(negm[1]));
     if (XB && nt > 1) {  // the first six K(1) fragments (slot 1 of the K ring, published by the prologue barrier): tile 0 starts with them in the ring
         constexpr int KS1 = KVB * HD * 2;
         w4b_read_head<KS1, KS1 + 32 * HD * 2, KS1, KS1 + 32 * HD * 2, KS1, KS1 + 32 * HD * 2>(kaddr[0], kaddr[1], kaddr[2]);
@@ -402,7 +425,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
             using N5 = std::integral_constant<int, n0 + 5>;
             w4b_read_head<frag_off(N0{}), frag_off(N1{}), frag_off(N2{}), frag_off(N3{}), frag_off(N4{}), frag_off(N5{})>(frag_addr(N0{}), frag_addr(N2{}), frag_addr(N4{}));
         }
-        if (__any(fmaxf(mx_cur[0], mx_cur[1]) > RESCALE_THR)) {  // rare: some row's maximum grew by more than 2^THR since its last rescale
+        if (!NM && __any(fmaxf(mx_cur[0], mx_cur[1]) > RESCALE_THR)) {  // rare: some row's maximum grew by more than 2^THR since its last rescale
             float alpha[2], delta[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
@@ -513,12 +536,12 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
                 constexpr int hu = (U::value >> 2) & 1, pa = 2 * (I & 1);
                 // row-max work: half 0 pairs 0..7 in steps 2..9 (chain set = step parity, so pairs 0, 1 start the chains), half 1 pairs 0, 1 in
                 // steps 10, 11 (start) and three more per chain set in steps 12, 13
-                constexpr int mxk = !has_next ? 0 : (I < 2 ? 0 : (I == 2 || I == 3 || I == 10 || I == 11) ? 1 : I < 12 ? 2 : 3);
+                constexpr int mxk = (!has_next || NM) ? 0 : (I < 2 ? 0 : (I == 2 || I == 3 || I == 10 || I == 11) ? 1 : I < 12 ? 2 : 3);
                 constexpr int mh = I < 10 ? 0 : 1;
                 constexpr int k0 = I < 2 ? 0 : I < 10 ? I - 2 : I < 12 ? I - 10 : I == 12 ? 2 : 5;  // first pair of the step
                 constexpr int k1i = mxk == 3 ? k0 + 1 : k0, k2i = mxk == 3 ? k0 + 2 : k0;
                 using H = std::integral_constant<int, mh>;
-#define W4B_SN(mb, r) (has_next ? sn(H{}, std::integral_constant<int, mb>{}, std::integral_constant<int, (r)>{}) : 0.f)
+#define W4B_SN(mb, r) ((has_next && !NM) ? sn(H{}, std::integral_constant<int, mb>{}, std::integral_constant<int, (r)>{}) : 0.f)
                 if constexpr (XB && has_next && I == 10) {
                     // every wave has issued its last read of V^T(t) (step 9) and of K(t+1) (region A): drain this wave's LDS-DMA and publish
                     // K(t+2) / V^T(t+1). No operands: the statement shares no register with its neighbours (no pad).
@@ -533,7 +556,14 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
 #undef W4B_SN
                 if constexpr (unit) uput(U{}, k1);
             });
-            if constexpr (has_next) {
+            if constexpr (has_next && NM) {  // no chains to fold: bare P.V steps that keep the read-ahead of K(t+2)'s fragments
+                using N14 = std::integral_constant<int, 16 + 14 + D>;
+                using N15 = std::integral_constant<int, 16 + 15 + D>;
+                float d0 = 0.f, d1 = 0.f;
+                uint32_t kd = 0;
+                w4b_step_pv<14, rd_off(N14{}), true, D, false, 0>(rd_addr(N14{}), pb[0][3], pb[1][3], 0.f, 0.f, kd, d0, d1, d0, d1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, d0, d1);
+                w4b_step_pv<15, rd_off(N15{}), true, D, false, 0>(rd_addr(N15{}), pb[0][3], pb[1][3], 0.f, 0.f, kd, d0, d1, d0, d1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, d0, d1);
+            } else if constexpr (has_next) {
                 if constexpr (XB) {
                     using N14 = std::integral_constant<int, 16 + 14 + D>;
                     using N15 = std::integral_constant<int, 16 + 15 + D>;

@@ -40,6 +40,29 @@ _FUSE_QKV_EPILOGUE = __import__("os").environ.get("G3_FUSE_QKV_EPILOGUE", "0") !
 _V_OPERAND_SWAP = __import__("os").environ.get("G3_V_OPERAND_SWAP", "1") != "0"
 
 
+# True (default): the single-GPU self-attention hands the kernel a bound on its logits (ops.self_attn_bounded), computed per block from the weights
+# of the q / k RMSNorms by _pack() - "fa_bound", see _qk_logit_bounds. The one-wave-per-SIMD kernel then runs without a running row maximum; a block whose
+# bound is beyond the kernel's range (max|w_q| * max|w_k| above ~3.6), and every launch that takes another kernel, runs as before. False: ops.flash_attn (A/B, tests).
+_SELF_ATTN_LOGIT_BOUND = True
+# margin on the bound for the four bf16 roundings of q and k between the norm and the MFMA (norm output, RoPE output, the softmax scale folded into Q):
+# each is within 2^-8 relative; a CPU emulation with unit weights and aligned q / k rows reached 16.35 (log2 domain) against 16.81
+_LOGIT_BOUND_MARGIN = 1.03
+
+
+def _qk_logit_bounds(qn_weights, kn_weights, head_dim: int = 128) -> list:
+    """Per block, a bound on |q . k| / sqrt(head_dim) for q, k behind per-head RMSNorm (y = x * rsqrt(mean x^2 + eps) * w, so
+    |y|_2 <= sqrt(head_dim) * max|w|) and RoPE (a rotation of the pairs (d, d + head_dim / 2): norm-preserving): by Cauchy-Schwarz
+    head_dim * max|w_q| * max|w_k| / sqrt(head_dim), times _LOGIT_BOUND_MARGIN. One device -> host read for the whole weight set: once per
+    _pack(), i.e. once per weight set - except for a weight set of inference tensors, which _pack() cannot cache and re-fuses on every forward;
+    that one pays 2 small reductions per block and this read per forward as well (a bound cached on the storage address alone could be stale
+    after an in-place update, and an understated bound is not an error the kernel survives)."""
+    if not qn_weights:
+        return []
+    mq = torch.stack([w.detach().abs().max().float() for w in qn_weights])
+    mk = torch.stack([w.detach().abs().max().float() for w in kn_weights])
+    return [float(v) * head_dim / math.sqrt(head_dim) * _LOGIT_BOUND_MARGIN for v in (mq * mk).tolist()]
+
+
 def _v_by_operand_swap(S: int) -> bool:
     """True when the self-attention V projection of an S-token forward runs with the operands swapped (_V_OPERAND_SWAP): the switch is on
     and S, the swapped GEMM's N, is a multiple of 4."""
@@ -380,6 +403,8 @@ class VideoExtendGeneralDIT(nn.Module):
                 w1=P[f"{mlp}.block.layer1.weight"], w2=P[f"{mlp}.block.layer2.weight"],
                 ada=[(P[f"{pre}.{j}.adaLN_modulation.1.weight"], P[f"{pre}.{j}.adaLN_modulation.2.weight"]) for j in range(3)],
             ))
+        for blk, fb in zip(blocks, _qk_logit_bounds([b["fa_qn"] for b in blocks], [b["fa_kn"] for b in blocks])):
+            blk["fa_bound"] = fb  # self-attention logit bound of the block (natural units), once per weight set
         if self.linear_precision == "mxfp8":  # quantised copies of the six block linears' weights, rebuilt with the rest of the set
             for blk in blocks:
                 blk["mx"] = {n: ops.quant_mxfp8(blk[n]) for n in MXFP8_LINEARS}
@@ -609,7 +634,10 @@ class VideoExtendGeneralDIT(nn.Module):
                     ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)  # one pass over q | k
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
-                o = ops.flash_attn(q, k, vt, S, S, B, nH)
+                if _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
+                    o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"])
+                else:
+                    o = ops.flash_attn(q, k, vt, S, S, B, nH)
             self._linear(o, blk, "fa_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- cross attention (unmasked over all M context tokens, general_dit.py:407-410)
             shift, scale, gate = self._modulation(emb, blk["ada"][1], adaln_lora, 3)

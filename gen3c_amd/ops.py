@@ -434,8 +434,50 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv:
     if timer is not None:
         timer.stop()
         # the kernel the launcher picked for THIS launch (per-call variant, else the library option in force)
-        _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial,
-                                                      kernel=lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode()), timer))
+        _record_attn_timer(timer, Sq, Skv, B, H, partial, lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())
+    return (o_part, lse) if partial else out
+
+
+def _record_attn_timer(timer, Sq: int, Skv: int, B: int, H: int, partial: bool, kernel: str):
+    """The timer entry of a self-attention launch: ONE place for the name and the meta keys bench.py finds the launches by (flash_attn, self_attn_bounded)."""
+    _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, kernel=kernel), timer))
+
+
+def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int, logit_bound: float,
+                      out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False):
+    """flash_attn (plain 4-D V^T; operands, `out`, `variant` and `partial` as there) for callers that guarantee
+    |q . k| * softmax_scale <= logit_bound for every query / key pair, e.g. q and k behind a per-head RMSNorm:
+    |q . k| / sqrt(128) <= sqrt(128) * max|w_q| * max|w_k|. Where the one-wave-per-SIMD kernel (variant 11) is the choice and
+    0 < logit_bound * log2(e) <= 60 it runs without its running row maximum (g3_self_attn_fwd_bounded_bf16); every other call is flash_attn's."""
+    qr, qw, ldq = _rowmajor2d(q, "q")
+    kr, kw, ldk = _rowmajor2d(k, "k")
+    assert qr == Sq * B and kr == Skv * B and qw == H * 128 and kw == H * 128
+    assert vt.is_contiguous() and vt.dim() == 4 and tuple(vt.shape[:3]) == (B, H, 128)
+    ldvt = vt.shape[-1]
+    o_part = lse = None
+    if partial:
+        assert out is None
+        o_part = torch.empty((Sq * B, H * 128), dtype=torch.float32, device=q.device)
+        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
+        ldo = o_part.stride(0)
+    else:
+        if out is None:
+            out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=q.device)
+        ldo = out.stride(0)
+    if softmax_scale is None:
+        softmax_scale = 1.0 / math.sqrt(128)
+    lib = _lib.load()
+    timer = None
+    if _KERNEL_TIMERS is not None:
+        timer = HipTimer()
+        timer.start()
+    _lib.check(lib.g3_self_attn_fwd_bounded_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt, 128 * ldvt,
+                                                 0, 0, 0 if partial else _dev(out, "out"), _dev(o_part, "o_part", torch.float32) if partial else 0,
+                                                 _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128,
+                                                 float(softmax_scale), float(logit_bound), int(variant), _stream()), "g3_self_attn_fwd_bounded_bf16")
+    if timer is not None:
+        timer.stop()
+        _record_attn_timer(timer, Sq, Skv, B, H, partial, lib.g3_self_attn_kernel_name(Sq, Skv, B, H, float(logit_bound), int(variant)).decode())
     return (o_part, lse) if partial else out
 
 

@@ -154,6 +154,20 @@ int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q_batch, int
                               int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant, void* stream);
 const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant);
 
+/* g3_flash_attn_fwd_ex_bf16 for callers that can BOUND the logits: logit_bound >= |q . k| * softmax_scale (natural units) for every query / key
+ * pair of the call - e.g. per-head RMSNorm of q and k (RoPE keeps the norm): |q . k| / sqrt(128) <= sqrt(128) * max|w_q| * max|w_k|. Where the
+ * resolved variant is 11, V^T is not segmented and 0 < logit_bound * log2(e) <= 60, the one-wave-per-SIMD kernel then runs without its running
+ * row maximum (the bound is the softmax's constant reference point; the same function, fewer instructions per tile). In every other case - bound 0,
+ * bound above the limit, another kernel - the call IS g3_flash_attn_fwd_ex_bf16. An understated bound is a caller error (rows may overflow).
+ * g3_self_attn_kernel_name reports the kernel such a call launches with PLAIN V^T (vt_seg_len == 0) and operands the 32-bit-offset kernels can
+ * address; like g3_flash_attn_kernel_name_ex it sees shapes only: a call with segments runs what g3_flash_attn_fwd_ex_bf16 runs, and a V^T leading
+ * dimension below ceil64(S_kv) or operands spanning more than 4 GiB demote either entry to the 64-bit-addressing kernel, whatever the name says. */
+int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                  int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
+                                  int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
+                                  int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant, void* stream);
+const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant);
+
 /* Carry-in form of g3_flash_attn_fwd_ex_bf16: a row's keys in a CHAIN of launches with no merge pass - the context-parallel schedule that
  * TransformerEngine's CP attention runs behind attn_op.set_context_parallel_group (general_dit.py:536-541, module/attention.py:282-297) keeps
  * a running softmax state per row; here each launch can resume from one.

@@ -27,6 +27,15 @@ def regs(tok):
     return {int(m.group(1))} if m else set()
 
 
+def _back_branch(v, hdr):
+    """Last branch to the label of the loop header at line hdr: the end of a tile loop that is ONE basic block (no "in Loop: Header" line marks its
+    extent - the no-max w4b kernel, whose tile pair has no branch inside); hdr itself when there is none."""
+    m = re.match(r"^(\.LBB\d+_\d+):", v[hdr])
+    if not m:
+        return hdr
+    return max([i for i in range(hdr, len(v)) if re.search(r"\bs_c?branch\w*\s+" + re.escape(m.group(1)) + r"\b", v[i])] + [hdr])
+
+
 def audit(asm_text: str):
     funcs, cur, name_full = {}, None, {}
     for ln in asm_text.split("\n"):
@@ -48,7 +57,8 @@ def audit(asm_text: str):
         owned_limit = 256 if "w4b" in name_full.get(name, "") else 192  # w4b also owns the fragment ring a[192:255]
         hdr0 = [i for i, l in enumerate(v) if "Inner Loop Header" in l]
         loop_lo = hdr0[0] if hdr0 else len(v)
-        loop_hi = max([i for i, l in enumerate(v) if "in Loop: Header" in l] + [0]) + 400
+        loop_end = max([i for i, l in enumerate(v) if "in Loop: Header" in l] + [_back_branch(v, hdr0[0]) if hdr0 else 0])
+        loop_hi = loop_end + 400
         last_trans = None  # (dst register, line) of a compiler-generated transcendental with no instruction after it yet
         for i, l in enumerate(v):
             t = l.strip()
@@ -97,7 +107,7 @@ def audit(asm_text: str):
                 findings.append(f"{name}: line {i}: scratch access in a kernel with asm-owned AGPRs: `{t}`")
         hdr = [i for i, l in enumerate(v) if "Inner Loop Header" in l]
         if hdr and n_asm_reads:
-            end = max(i for i, l in enumerate(v) if "in Loop: Header" in l)
+            end = loop_end
             for i in range(hdr[0], end + 12):
                 if "scratch_load" in v[i]:  # performance, not correctness: reported, does not fail the audit
                     print(f"note: {name}: line {i}: scratch reload inside the tile loop: `{v[i].strip()}`")
