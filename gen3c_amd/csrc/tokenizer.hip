@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
 }
 
 // Normalise (+ swish) given finished statistics. A thread keeps ONE 8-channel column for the whole launch (the grid stride is a multiple of the chunks per
-// row: 256 threads, C / 8 <= 64 chunks): gamma / beta are loaded once and the row index advances by a constant - no 64-bit division per chunk (round 4; the
+// row: 256 threads, C / 8 = 1 .. 256 chunks, a divisor of 256): gamma / beta are loaded once and the row index advances by a constant - no 64-bit division per chunk (round 4; the
 // first form recomputed row = chunk / (C / 8) and reloaded gamma / beta for every chunk: 4.0-5.0 TB/s; this form 5.4-5.7). Four rows in flight per iteration.
 template <bool SWISH>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict__ x, int64_t ld, const bf16_t* __restrict__ gamma,
@@ -50,7 +50,10 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
     const double n = (double)rows_per_frame * C;
     const double mean_d = stats[frame * 2] / n;
     const double var_d = stats[frame * 2 + 1] / n - mean_d * mean_d;
+    // The mean as two floats: x - mean cancels where a frame sits far from 0 (mean 6, std 0.25: pixels within 1e-4 of the mean), and the 2^-25 |mean|
+    // that one float drops is then several bf16 ulps of the result (3.4 measured). x - mean_hi is exact there; mean_lo restores what the rounding took.
     const float mean = (float)mean_d;
+    const float mean_lo = (float)(mean_d - (double)mean);
     const float rstd = rsqrtf((float)(var_d > 0 ? var_d : 0) + eps);
     const int cpr = C >> 3;                                   // chunks per row; divides 256 (host-checked)
     const int t = blockIdx.x * 256 + threadIdx.x;
@@ -67,7 +70,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float y = ((float)v[e] - mean) * rstd * gf[e] + bfv[e];
+            float y = (((float)v[e] - mean) - mean_lo) * rstd * gf[e] + bfv[e];
             if (SWISH) y = y * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -1.44269504088896340736f));  // y * sigmoid(y)
             o[e] = f32_to_bf16(y);
         }
@@ -489,6 +492,7 @@ __global__ __launch_bounds__(256) void gn_apply_generic_kernel(const bf16_t* __r
     const double mean_d = stats[frame * 2] / n;
     const double var_d = stats[frame * 2 + 1] / n - mean_d * mean_d;
     const float mean = (float)mean_d;
+    const float mean_lo = (float)(mean_d - (double)mean);  // see gn_apply_kernel
     const float rstd = rsqrtf((float)(var_d > 0 ? var_d : 0) + eps);
     const int cpr = C >> 3;
     const int64_t nchunks = (int64_t)rows_per_frame * cpr;
@@ -502,7 +506,7 @@ __global__ __launch_bounds__(256) void gn_apply_generic_kernel(const bf16_t* __r
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-            float y = ((float)v[e] - mean) * rstd * (float)g[e] + (float)b[e];
+            float y = (((float)v[e] - mean) - mean_lo) * rstd * (float)g[e] + (float)b[e];
             if (swish) y = y * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(y * -1.44269504088896340736f));
             o[e] = f32_to_bf16(y);
         }
