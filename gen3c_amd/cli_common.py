@@ -49,12 +49,13 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--fps", type=int, default=24)
     p.add_argument("--seed", type=int, default=1)
     p.add_argument("--num_gpus", type=int, default=1, help="context-parallel ranks (launch with torchrun --nproc_per_node=N)")
-    p.add_argument("--dit_precision", choices=("bf16", "mxfp8"), default="bf16",
-                   help="precision of the DiT's six per-block linears: bf16 (default, the parity path) or mxfp8 (opt-in MXFP8 matrix cores; "
-                        "outside the parity statement, DESIGN.md section 10)")
+    p.add_argument("--dit_precision", choices=("bf16", "mxfp8", "mxfp6"), default="bf16",
+                   help="precision of the DiT's six per-block linears: bf16 (default, the parity path), mxfp8 (opt-in MXFP8 matrix cores) or mxfp6 "
+                        "(opt-in MXFP6 e2m3 operands on the same matrix cores at twice the rate); both outside the parity statement, DESIGN.md "
+                        "sections 10 and 10.2")
     p.add_argument("--dit_mxfp8_producers", choices=("separate", "fused"), default="separate",
                    help="with --dit_precision mxfp8: separate (default) quantises every linear's input in a pass of its own; fused lets the LayerNorm "
-                        "passes and the MLP-up GEMM emit MXFP8 directly (same output bit for bit). No effect with bf16")
+                        "passes and the MLP-up GEMM emit MXFP8 directly (same output bit for bit). No effect with bf16; accepted and inert with mxfp6, which has no fused producers")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -193,9 +194,9 @@ class Session:
             net.enable_context_parallel(self.cp_group)
         if getattr(args, "dit_precision", "bf16") != "bf16":
             net.set_linear_precision(args.dit_precision)
-            print(f"[gen3c_amd] --dit_precision {args.dit_precision}: the DiT block linears run on MXFP8 operands; this mode is outside the bf16 "
-                  "parity statement (DESIGN.md section 10)")
-        net.set_mxfp8_producers(getattr(args, "dit_mxfp8_producers", "separate"))  # inert under bf16
+            print(f"[gen3c_amd] --dit_precision {args.dit_precision}: the DiT block linears run on {args.dit_precision.upper()} operands; this mode is "
+                  f"outside the bf16 parity statement (DESIGN.md section {'10' if args.dit_precision == 'mxfp8' else '10.2'})")
+        net.set_mxfp8_producers(getattr(args, "dit_mxfp8_producers", "separate"))  # inert under bf16 and mxfp6
         self.net, self.tokenizer = net, tk
         self.model = DiffusionGen3CModel(net, tk, latent_shape=(16, tk.get_latent_num_frames(self.chunk), H // 8, W // 8))
         self.pipe = Gen3cPipeline(self.model, guidance=args.guidance, num_steps=args.num_steps, height=H, width=W, fps=args.fps,

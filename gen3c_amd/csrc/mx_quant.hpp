@@ -43,3 +43,54 @@ G3_DEVICE u32x2 mx_quant_quad(const float (&f)[8], int& X) {
     }
     return o;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// MXFP6 (OCP MX v1.0, e2m3 elements: 1 sign, 2 exponent, 3 mantissa bits, bias 1; subnormals m/8, normals 2^(e-1)(1 + m/8), maximum 7.5, no Inf or
+// NaN codes; format notes in the MXFP6 part of gemm_mx.hip). The e4m3 routines above are left as they are.
+// ---------------------------------------------------------------------------------------------------------------
+
+// e2m3 code of RNE(y), |y| <= 7.5 (the caller clamps, so 7.75 never reaches the tie to 8). With e = max(floor(log2|y|), 0) the step is 2^(e-3) and
+// q = |y| / 2^(e-3) in [0, 16]; code = 8 e + q covers subnormals (e = 0, q < 8), normals and the carry of q = 16 into the next exponent. The
+// sign bit (0x20) is the input's, so a negative value that rounds to zero gives 0x20 (-0), as e4m3_rne gives 0x80.
+G3_DEVICE uint32_t e2m3_rne(float y) {
+    const uint32_t b = __float_as_uint(y);
+    int e = (int)((b >> 23) & 0xff) - 127;
+    e = e < 0 ? 0 : e;
+    const float q = rintf(ldexpf(fabsf(y), 3 - e));
+    return ((b >> 26) & 0x20) | (uint32_t)(e * 8 + (int)q);
+}
+
+// Shared exponent X of an MXFP6 block: floor(log2(amax)) - 2, so amax / 2^X lies in [4, 8) (E8M0 byte = X + 127).
+G3_DEVICE int mx6_block_exponent(float amax) {
+    if (amax == 0.0f) return 0;
+    int X = (int)((__float_as_uint(amax) >> 23) & 0xff) - 127 - 2;  // subnormal amax: exponent field 0 -> X = -129, clamped
+    return X < -127 ? -127 : (X > 127 ? 127 : X);
+}
+
+// 8 consecutive elements of a block (already divided by 2^X) as 48 bits: element i at bits [6 i, 6 i + 6). lo = bits 0..31, hi = bits 32..47.
+G3_DEVICE void mx6_pack8(const float (&y)[8], uint32_t& lo, uint32_t& hi) {
+    uint64_t v = 0;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v |= (uint64_t)e2m3_rne(fminf(fmaxf(y[e], -7.5f), 7.5f)) << (6 * e);
+    lo = (uint32_t)v;
+    hi = (uint32_t)(v >> 32);
+}
+
+// The lane quad j = lane & 3 holds the four 48-bit pieces of one 24-byte block. Returns the 8 bytes [8 j, 8 j + 8) of the block for j < 3
+// (lane 3 of the quad stores nothing), gathered from this lane and its right neighbour. EVERY lane of the wave has to call this (the shuffles).
+G3_DEVICE u32x2 mx6_gather_quad(uint32_t lo, uint32_t hi, int j) {
+    const uint32_t nlo = (uint32_t)__shfl_down((int)lo, 1, 64);
+    const uint32_t nhi = (uint32_t)__shfl_down((int)hi, 1, 64);
+    u32x2 o;
+    if (j == 0) {         // bytes 0..7: own 48 bits, then the neighbour's low 16
+        o[0] = lo;
+        o[1] = hi | (nlo << 16);
+    } else if (j == 1) {  // bytes 8..15: own bits 16..47, then the neighbour's low 32
+        o[0] = (lo >> 16) | (hi << 16);
+        o[1] = nlo;
+    } else {              // j == 2, bytes 16..23: own bits 32..47, then the neighbour's 48
+        o[0] = hi | (nlo << 16);
+        o[1] = (nlo >> 16) | (nhi << 16);
+    }
+    return o;
+}

@@ -78,9 +78,10 @@ _CROSS_Q_NORM_IN_ATTENTION = __import__("os").environ.get("G3_CROSS_Q_NORM_IN_AT
 def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total, hq=None, wq=None):
     """a @ w^T with per-head RMSNorm (+ RoPE) on the first n_q (weight norm_q) and the next n_k (norm_k) output features; the rest plain.
     Same rounding points either way (tested): the fused GEMM epilogue, or the plain GEMM followed by the in-place norm passes.
-    hq / wq: MXFP8 (q, scales) of h and of w (linear_precision "mxfp8"): the block-scaled GEMM, then the same in-place norm passes."""
+    hq / wq: MX (q, scales) of h and (q, scales, format) of w (linear_precision "mxfp8" / "mxfp6"): the block-scaled GEMM, then the same
+    in-place norm passes."""
     if wq is not None:
-        y = ops.gemm_mxfp8_nt(hq[0], hq[1], wq[0], wq[1])
+        y = _mx_gemm(wq[2])(hq[0], hq[1], wq[0], wq[1])
     elif _FUSE_QKV_EPILOGUE:
         return ops.gemm_qk_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B)
     else:
@@ -94,15 +95,26 @@ def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total,
     return y
 
 
-LINEAR_PRECISIONS = ("bf16", "mxfp8")
+LINEAR_PRECISIONS = ("bf16", "mxfp8", "mxfp6")
 MXFP8_PRODUCERS = ("separate", "fused")
-MXFP8_LINEARS = ("fa_qkv", "fa_out", "ca_q", "ca_out", "w1", "w2")  # the packed-weight names of the linears the mxfp8 mode quantises
+MXFP8_LINEARS = ("fa_qkv", "fa_out", "ca_q", "ca_out", "w1", "w2")  # the packed-weight names of the linears the mxfp8 / mxfp6 modes quantise
+
+
+# The one place the low-precision format of a packed block ("mx_fmt": "mxfp8" or "mxfp6") turns into ops; looked up per call, by name.
+def _mx_quant(fmt: str):
+    """The activation / weight quantiser of the format: ops.quant_mxfp8 or ops.quant_mxfp6."""
+    return getattr(ops, "quant_" + fmt)
+
+
+def _mx_gemm(fmt: str):
+    """The block-scaled GEMM of the format: ops.gemm_mxfp8_nt or ops.gemm_mxfp6_nt."""
+    return getattr(ops, "gemm_" + fmt + "_nt")
 
 
 def _mx_rows(blk: dict, name: str, rows: slice):
-    """MXFP8 (q, scales) of rows `rows` of a packed weight, or None in the bf16 mode."""
+    """MX (q, scales, format) of rows `rows` of a packed weight, or None in the bf16 mode."""
     mx = blk.get("mx")
-    return None if mx is None else (mx[name][0][rows], mx[name][1][rows])
+    return None if mx is None else (mx[name][0][rows], mx[name][1][rows], blk["mx_fmt"])
 
 
 class DataType(Enum):
@@ -330,10 +342,11 @@ class VideoExtendGeneralDIT(nn.Module):
         return out
 
     def set_linear_precision(self, precision: str) -> None:
-        """"bf16" (default, the parity path) or "mxfp8": the six per-block linears (self-attention QKV and out-projection, cross-attention Q
-        and out-projection, MLP up and down) run on MXFP8 operands (OCP MX, e4m3 + a power-of-two scale per 32 k; g3_gemm_mxfp8_nt) with their
-        activations quantised per call. Patch embed, final layer, cross-attention K / V, adaLN and attention stay bf16. The mxfp8 mode is
-        outside the bf16 parity statement (DESIGN.md section 10 gives its measured quality)."""
+        """"bf16" (default, the parity path), "mxfp8" or "mxfp6": the six per-block linears (self-attention QKV and out-projection,
+        cross-attention Q and out-projection, MLP up and down) run on MXFP8 operands (OCP MX, e4m3 + a power-of-two scale per 32 k;
+        g3_gemm_mxfp8_nt) or on MXFP6 operands (e2m3, the same scales; g3_gemm_mxfp6_nt, twice the matrix-core rate) with their activations
+        quantised per call. Patch embed, final layer, cross-attention K / V, adaLN and attention stay bf16. Both modes are outside the bf16
+        parity statement (DESIGN.md sections 10 and 10.2 give their measured quality)."""
         if precision not in LINEAR_PRECISIONS:
             raise ValueError(f"linear_precision must be one of {LINEAR_PRECISIONS}, got {precision!r}")
         if precision != self.linear_precision:
@@ -341,7 +354,8 @@ class VideoExtendGeneralDIT(nn.Module):
         self.linear_precision = precision
 
     def set_mxfp8_producers(self, producers: str) -> None:
-        """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16".
+        """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16". Under "mxfp6" the setting is
+        accepted and inert: there are no fused MXFP6 producers, every activation takes the separate g3_quant_mxfp6_bf16 pass.
         "separate" (default): every producer writes bf16 and g3_quant_mxfp8_bf16 makes one more pass over it.
         "fused": the kernels we own that feed a block linear quantise their output in registers - the three LayerNorm + AdaLN passes
         (g3_layernorm_modulate_mxfp8, g3_posemb_layernorm_modulate_mxfp8) and the MLP-up GEMM's GELU epilogue (g3_gemm_mxfp8_nt_mxout) - so four
@@ -353,16 +367,17 @@ class VideoExtendGeneralDIT(nn.Module):
         self.mxfp8_producers = producers
 
     def _linear(self, a, blk: dict, name: str, out_mx: bool = False, **kw):
-        """One of the six block linears: the bf16 GEMM, or under "mxfp8" the activation quantised and the block-scaled GEMM.
+        """One of the six block linears: the bf16 GEMM, or under "mxfp8" / "mxfp6" the activation quantised and the block-scaled GEMM.
         a: the bf16 activation, or (mxfp8 only) the (q, scales) pair a fused producer already made of it. out_mx (mxfp8 only): the output
         leaves as such a pair for the next linear."""
         mx = blk.get("mx")
         if mx is None:
             return ops.gemm_nt(a, blk[name], **kw)
-        aq, as_ = a if isinstance(a, tuple) else ops.quant_mxfp8(a)
+        fmt = blk["mx_fmt"]
+        aq, as_ = a if isinstance(a, tuple) else _mx_quant(fmt)(a)
         if out_mx:
             kw["out_mx"] = True
-        return ops.gemm_mxfp8_nt(aq, as_, mx[name][0], mx[name][1], **kw)
+        return _mx_gemm(fmt)(aq, as_, mx[name][0], mx[name][1], **kw)
 
     def _ln(self, xs: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, fused: bool):
         """LayerNorm + AdaLN modulate of the residual stream: bf16, or (fused mxfp8 producers) the MXFP8 pair the next linear consumes."""
@@ -405,9 +420,10 @@ class VideoExtendGeneralDIT(nn.Module):
             ))
         for blk, fb in zip(blocks, _qk_logit_bounds([b["fa_qn"] for b in blocks], [b["fa_kn"] for b in blocks])):
             blk["fa_bound"] = fb  # self-attention logit bound of the block (natural units), once per weight set
-        if self.linear_precision == "mxfp8":  # quantised copies of the six block linears' weights, rebuilt with the rest of the set
+        if self.linear_precision != "bf16":  # quantised copies of the six block linears' weights, rebuilt with the rest of the set
             for blk in blocks:
-                blk["mx"] = {n: ops.quant_mxfp8(blk[n]) for n in MXFP8_LINEARS}
+                blk["mx_fmt"] = self.linear_precision
+                blk["mx"] = {n: _mx_quant(self.linear_precision)(blk[n]) for n in MXFP8_LINEARS}
         self._packed = dict(blocks=blocks, P=P, key=key, versioned=cacheable(*P.values()), precision=self.linear_precision)
         return self._packed
 
@@ -584,12 +600,13 @@ class VideoExtendGeneralDIT(nn.Module):
                 pe_sum = (pos["pe_t"][:, None, None, :] + pos["pe_h"][None, :, None, :]) + pos["pe_w"][None, None, :, :]
                 pos["full"] = (pe_sum / pos["norm"].reshape(Tp, Hp, Wp, 1)).reshape(S, D).contiguous()
                 del pe_sum
-            fused = "mx" in blk and self.mxfp8_producers == "fused"  # the LayerNorms and w1 hand MXFP8 (q, scales) pairs to their linears
+            # the LayerNorms and w1 hand MXFP8 (q, scales) pairs to their linears (mxfp8 only: the setting is inert under mxfp6)
+            fused = blk.get("mx_fmt") == "mxfp8" and self.mxfp8_producers == "fused"
             if fused:
                 h, hq = None, ops.posemb_layernorm_modulate_mxfp8(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
             else:
                 h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
-                hq = ops.quant_mxfp8(h) if "mx" in blk else None
+                hq = _mx_quant(blk["mx_fmt"])(h) if "mx" in blk else None
             if self._cp_fused_qkv():
                 # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
                 # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
@@ -610,8 +627,8 @@ class VideoExtendGeneralDIT(nn.Module):
                                        wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
                 o = self._cp_attn.finish(q, pending)
             else:
-                if hq is not None:  # mxfp8: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
-                    qkv = ops.gemm_mxfp8_nt(hq[0], hq[1], *blk["mx"]["fa_qkv"])
+                if hq is not None:  # mxfp8 / mxfp6: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
+                    qkv = _mx_gemm(blk["mx_fmt"])(hq[0], hq[1], *blk["mx"]["fa_qkv"])
                     ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
@@ -646,7 +663,7 @@ class VideoExtendGeneralDIT(nn.Module):
             if _CROSS_Q_NORM_IN_ATTENTION:  # plain projection; to_q[1]'s per-head RMSNorm runs in the attention kernel's Q load (no RoPE in cross-attention)
                 o = ops.flash_attn(self._linear(h, blk, "ca_q"), k, vt, S, M, B, nH, kv_dense=ca_dense, q_norm_weight=blk["ca_qn"])
             else:
-                hq = h if fused else (ops.quant_mxfp8(h) if "mx" in blk else None)
+                hq = h if fused else (_mx_quant(blk["mx_fmt"])(h) if "mx" in blk else None)
                 q = _project_norm_rope(h, blk["ca_q"], D, 0, blk["ca_qn"], None, None, None, S, B, nH, hq=hq, wq=_mx_rows(blk, "ca_q", slice(None)))
                 o = ops.flash_attn(q, k, vt, S, M, B, nH, kv_dense=ca_dense)
             self._linear(o, blk, "ca_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)

@@ -151,6 +151,63 @@ def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: tor
     return out
 
 
+def quant_mxfp6(x: torch.Tensor, out=None):
+    """MXFP6 (OCP MX, e2m3) of a bf16 [M, K] matrix: (q [M, 3K/4] torch.uint8 - 32 six-bit codes per 24 bytes -, scales [M, K/32] torch.uint8
+    E8M0). out: an optional (q, scales) pair to write into. See g3_quant_mxfp6_bf16 for the rounding rule and the packing."""
+    M, K, ldx = _rowmajor2d(x, "x")
+    if out is None:
+        out = (torch.empty((M, K // 4 * 3), dtype=torch.uint8, device=x.device), torch.empty((M, K // 32), dtype=torch.uint8, device=x.device))
+    q, s = out
+    Mq, Kq, ldq = _rowmajor2d(q, "q")
+    Ms, Ks, lds = _rowmajor2d(s, "scales")
+    if K % 32 or (Mq, Kq) != (M, K // 4 * 3) or (Ms, Ks) != (M, K // 32):
+        raise _lib.Gen3cHipError(f"quant_mxfp6: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match x {tuple(x.shape)}")
+    lib = _lib.load()
+    _lib.check(lib.g3_quant_mxfp6_bf16(_dev(x, "x"), ldx, _dev(q, "q", torch.uint8), ldq, _dev(s, "scales", torch.uint8), lds, M, K,
+                                       _stream()), "g3_quant_mxfp6_bf16")
+    return q, s
+
+
+def gemm_mxfp6_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  epilogue: int = EPI_NONE, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None):
+    """out[M,N] = epi(dequant(aq, as_) @ dequant(wq, ws)^T) on the block-scaled matrix cores at the MXFP6 rate; operands as quant_mxfp6
+    returns them. Same epilogues and rounding points as gemm_nt (NONE, GELU, GATED_RESIDUAL; out may be the residual)."""
+    M, Kb, lda = _rowmajor2d(aq, "aq")
+    N, Kwb, ldw = _rowmajor2d(wq, "wq")
+    if Kb != Kwb or Kb % 24:
+        raise _lib.Gen3cHipError(f"gemm_mxfp6_nt: packed row bytes {Kb} vs {Kwb} (must be equal and a multiple of 24)")
+    K = Kb // 3 * 4
+    Ma, Ka, ldas = _rowmajor2d(as_, "as_")
+    Nw, Kws, ldws = _rowmajor2d(ws, "ws")
+    if (Ma, Nw) != (M, N) or Ka * 32 != K or Kws * 32 != K:
+        raise _lib.Gen3cHipError(f"gemm_mxfp6_nt: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
+    Mo, No, ldc = _rowmajor2d(out, "out")
+    assert (Mo, No) == (M, N)
+    gp, grows, ldg, rp, ldr = 0, 1, 0, 0, 0
+    if gate is not None:
+        grows, gn, ldg = _rowmajor2d(gate, "gate")
+        assert gn == N
+        gp = _dev(gate, "gate")
+    if residual is not None:
+        rm, rn, ldr = _rowmajor2d(residual, "residual")
+        assert (rm, rn) == (M, N)
+        rp = _dev(residual, "residual")
+    lib = _lib.load()
+    timer = None
+    if _KERNEL_TIMERS is not None and M >= 4096:
+        timer = HipTimer()
+        timer.start()
+    u8 = torch.uint8
+    _lib.check(lib.g3_gemm_mxfp6_nt(_dev(aq, "aq", u8), lda, _dev(as_, "as_", u8), ldas, _dev(wq, "wq", u8), ldw, _dev(ws, "ws", u8), ldws,
+                                    _dev(out, "out"), ldc, M, N, K, epilogue, gp, grows, ldg, rp, ldr, _stream()), "g3_gemm_mxfp6_nt")
+    if timer is not None:
+        timer.stop()
+        _KERNEL_TIMERS.append(("gemm_mxfp6_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    return out
+
+
 def _mx_out_pair(out, M: int, K: int, device, what: str):
     """The (q, scales) pair an MXFP8-producing op writes: allocated, or the caller's, checked against [M, K]. -> q, s, ldq, lds"""
     if out is None or out is True:

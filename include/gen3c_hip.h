@@ -96,6 +96,27 @@ int g3_gemm_mxfp8_nt_mxout(const void* aq, int64_t lda, const void* as, int64_t 
 /* Name of the instantiation g3_gemm_mxfp8_nt_mxout launches ("gemm_mxfp8_nt_kernel<256 + epilogue>"), or NULL where it refuses: tools only. */
 const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int epilogue);
 
+/* MXFP6 (OCP MX v1.0, e2m3 elements: 1 sign, 2 exponent, 3 mantissa bits, bias 1, maximum 7.5, no Inf / NaN) of a bf16 matrix:
+ * x [M][ldx] bf16 -> q [M][ldq] packed 6-bit codes + scales [M][lds] E8M0 bytes, one per 32 consecutive k of a row:
+ *   X = floor(log2(amax of the block)) - 2, byte X + 127 clamped to 0..254; code = RNE(clamp(x / 2^X, -7.5, 7.5)) with the sign bit of x;
+ *   an all-zero block gets byte 127 and zero codes. Block b of a row is the 24 bytes [24 b, 24 b + 24) of q's row, element i of the block
+ *   the 6 bits [6 i, 6 i + 6) of that 192-bit little-endian string. Needs K % 32 == 0, ldx >= K and ldq >= 3K/4 multiples of 8,
+ *   lds >= K/32; x 16-byte, q 8-byte aligned. */
+int g3_quant_mxfp6_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream);
+
+/* g3_gemm_mxfp8_nt on MXFP6 operands as g3_quant_mxfp6_bf16 writes them (the same matrix-core instruction at twice the MXFP8 rate):
+ * C[M,N] = epi( sum_k (aq[m][k] 2^as[m][k/32]) (wq[n][k] 2^ws[n][k/32]) ), the same epilogues and rounding points (C may alias the
+ * residual). Needs N % 256 == 0, K % 128 == 0, lda / ldw >= 3K/4 multiples of 16 with 16-byte aligned operands, scale strides >= K/32
+ * multiples of 4 with 4-byte aligned scales, ldc (ldg, ldr) multiples of 8 with 16-byte aligned rows, ldr >= N and ldg >= N when
+ * gate_rows > 1; anything else is refused with G3_ERR_ARG before any launch. */
+int g3_gemm_mxfp6_nt(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws,
+                     void* c, int64_t ldc, int M, int N, int K, int epilogue, const void* gate, int gate_rows, int64_t ldg,
+                     const void* residual, int64_t ldr, void* stream);
+
+/* Name of the kernel instantiation g3_gemm_mxfp6_nt launches for this shape and epilogue ("gemm_mxfp6_nt_kernel<epilogue>"), or NULL where it
+ * refuses the shape or epilogue: profilers / tools only. */
+const char* g3_gemm_mxfp6_kernel_name(int M, int N, int K, int epilogue);
+
 /* out[M<=8][N] = (act_in(a) . w^T) (+ add): TimestepEmbedding (blocks.py:60-80) and adaLN_modulation
  * (blocks.py:411-415, 442-447; FinalLayer blocks.py:212-216, 230). act_in: 0 none, 1 SiLU. */
 int g3_gemv_bf16(const void* a, int64_t lda, const void* w, int64_t ldw, const void* add, int64_t ldadd, void* out,

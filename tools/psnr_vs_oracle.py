@@ -8,7 +8,7 @@ or `--random_init` weights - generate ONE chunk three ways from the same rendere
 
 and report, per frame, PSNR(hip, fp32), PSNR(ref, fp32) and their difference. Exit status 1 if any frame of the HIP video is more than
 `--threshold_db` (0.1) dB WORSE than the reference-precision chain's frame (being closer to fp32 than the reference's arithmetic is never a failure).
-With `--dit_precision mxfp8` the HIP chain runs the opt-in MXFP8 block linears; it is reported next to the bf16 HIP chain on the same inputs and
+With `--dit_precision mxfp8` (or `mxfp6`) the HIP chain runs the opt-in MXFP8 (MXFP6) block linears; it is reported next to the bf16 HIP chain on the same inputs and
 the threshold is not applied (the mode is outside the parity statement).
 The rendered buffers are shared by the three chains: the renderer's masks / indices are bit-exact against the reference on their own
 (tests/test_render_gpu.py), so this isolates the tokenizer + DiT + sampler numerics the 0.1 dB is about.
