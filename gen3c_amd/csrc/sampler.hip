@@ -5,7 +5,12 @@
 // Here each side of the two network calls is ONE pass: (1) build the network input, (2) CFG + conditioning-frame
 // replacement + Euler update. bf16 roundings are placed exactly where the reference's dtype promotion puts them
 // (comments name the torch expression each rounding belongs to); scalar coefficients are computed by the host in
-// the dtypes the reference uses and arrive as floats.
+// the dtypes the reference uses and arrive as floats. "Where the reference puts them" includes WHERE each operand lives:
+// the model's sigma is a bf16 0-dim tensor on the device, the scheduler's scalars are fp32 0-dim tensors on the CPU, and
+// torch's device kernels take a CPU 0-dim operand as an fp32 scalar argument - unrounded in a product with a bf16 tensor,
+// and as its host-computed reciprocal in a division. tests/sampler_ref.py is the statement of this dtype chain;
+// tests/test_sampler_kernels_gpu.py holds both kernels to it bit for bit (built with -ffp-contract=off: no FMA where
+// torch runs a multiply and an add as two kernels).
 #include "common.hpp"
 
 namespace {
@@ -54,6 +59,7 @@ struct StepArgs {
     float c_skip_bf16, c_out_bf16;  // _reverse_precondition_output coefficients, evaluated in bf16 (sigma bf16 tensor)
     float c_skip, c_out;            // scheduler.precondition_outputs coefficients (fp32 sigma)
     float sigma, sigma_next;        // fp32
+    float inv_sigma;                // fp32 1 / sigma, divided on the host
 };
 
 __global__ __launch_bounds__(256) void edm_step_kernel(StepArgs a) {
@@ -70,9 +76,10 @@ __global__ __launch_bounds__(256) void edm_step_kernel(StepArgs a) {
             // new_output = indicator * latent_unscaled + (1 - indicator) * net_output   (bf16, :147)
             no = rbf(rbf(ind * lu) + rbf(rbf(1.f - ind) * no));
         }
-        // EDMEulerScheduler.step: sample upcast to fp32; c_out * model_output is a bf16 product
+        // EDMEulerScheduler.step: sample upcast to fp32; c_out * model_output is a bf16 product whose fp32 CPU 0-dim factor is not rounded
         const float x0 = a.c_skip * x + rbf(a.c_out * no);
-        const float deriv = (x - x0) / a.sigma;
+        // (sample - x0) / sigma_hat with a CPU 0-dim divisor: torch's device kernel multiplies by the reciprocal taken on the host
+        const float deriv = (x - x0) * a.inv_sigma;
         a.xt_next[i] = f32_to_bf16(x + deriv * (a.sigma_next - a.sigma));  // prev_sample.to(model_output.dtype)
     }
 }
@@ -100,12 +107,13 @@ extern "C" int g3_edm_prepare_input_bf16(const void* xt, const void* gt_latent, 
 extern "C" int g3_edm_cfg_euler_step_bf16(const void* out_cond, const void* out_uncond, const void* new_xt,
                                           const void* gt_latent, const float* indicator, void* xt_next, int64_t n,
                                           int T, int hw, float guidance, float c_skip_bf16, float c_out_bf16,
-                                          float c_skip, float c_out, float sigma, float sigma_next, void* stream) {
+                                          float c_skip, float c_out, float sigma, float inv_sigma, float sigma_next,
+                                          void* stream) {
     if (!out_cond || !out_uncond || !new_xt || !gt_latent || !indicator || !xt_next)
         return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_euler_step_bf16: null operand");
-    if (n <= 0 || T <= 0 || hw <= 0 || sigma <= 0.f) return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_euler_step_bf16: bad argument");
+    if (n <= 0 || T <= 0 || hw <= 0 || sigma <= 0.f || !(inv_sigma > 0.f)) return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_euler_step_bf16: bad argument");
     StepArgs a{(const bf16_t*)out_cond, (const bf16_t*)out_uncond, (const bf16_t*)new_xt, (const bf16_t*)gt_latent,
-               indicator, (bf16_t*)xt_next, n, T, hw, guidance, c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next};
+               indicator, (bf16_t*)xt_next, n, T, hw, guidance, c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next, inv_sigma};
     hipLaunchKernelGGL(edm_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a);
     return g3_check_launch("g3_edm_cfg_euler_step_bf16");
 }

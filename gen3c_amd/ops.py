@@ -679,7 +679,8 @@ def edm_prepare_input(xt, gt_latent, noise, indicator, T: int, hw: int, augment_
 
 
 def edm_cfg_euler_step(out_cond, out_uncond, new_xt, gt_latent, indicator, T: int, hw: int, guidance: float,
-                       c_skip_bf16: float, c_out_bf16: float, c_skip: float, c_out: float, sigma: float, sigma_next: float):
+                       c_skip_bf16: float, c_out_bf16: float, c_skip: float, c_out: float, sigma: float, inv_sigma: float,
+                       sigma_next: float):
     """-> xt_next (bf16). See g3_edm_cfg_euler_step_bf16."""
     for t in (out_cond, out_uncond, new_xt, gt_latent, indicator):
         assert t.is_contiguous()
@@ -689,7 +690,7 @@ def edm_cfg_euler_step(out_cond, out_uncond, new_xt, gt_latent, indicator, T: in
     _lib.check(lib.g3_edm_cfg_euler_step_bf16(_dev(out_cond, "out_cond"), _dev(out_uncond, "out_uncond"), _dev(new_xt, "new_xt"),
                                               _dev(gt_latent, "gt_latent"), _dev(indicator, "indicator", torch.float32),
                                               _dev(xt_next, "xt_next"), new_xt.numel(), T, hw, guidance, c_skip_bf16, c_out_bf16,
-                                              c_skip, c_out, sigma, sigma_next, _stream()), "g3_edm_cfg_euler_step_bf16")
+                                              c_skip, c_out, sigma, inv_sigma, sigma_next, _stream()), "g3_edm_cfg_euler_step_bf16")
     return xt_next
 
 

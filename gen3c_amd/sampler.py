@@ -10,7 +10,10 @@ Mirrors (same names, argument meaning, CP behaviour):
 
 Per step the only device work outside the two network calls is two fused HIP kernels (csrc/sampler.hip). Scalar
 coefficients are evaluated here on the host with 0-dim torch tensors in the SAME dtypes the reference's expressions
-produce (several of them are bf16 because the loop's `sigma` is cast with `.to(**tensor_kwargs)`).
+produce (several of them are bf16 because the loop's `sigma` is cast with `.to(**tensor_kwargs)`). The reference evaluates the
+bf16 ones on the device; tests/test_sampler_kernels_gpu.py checks that the host gives the same numbers at every step.
+tests/sampler_ref.py states the whole dtype chain - which operand is bf16 or fp32, on the device or a CPU 0-dim scalar - and
+the kernels plus these scalars are held to it bit for bit.
 """
 from __future__ import annotations
 
@@ -126,9 +129,15 @@ class Gen3CDenoiser:
         c_skip = sd ** 2 / (sigma32 ** 2 + sd ** 2)                        # scheduler.precondition_outputs
         c_out = sigma32 * sd / (sigma32 ** 2 + sd ** 2) ** 0.5
         c_in_aug = 1 / ((augment_sigma ** 2 + sd ** 2) ** 0.5)             # python floats
+        # scheduler.step divides an fp32 device tensor by its fp32 CPU 0-dim sigma: torch's device kernel takes the reciprocal of a CPU
+        # scalar divisor on the host, in fp32, and multiplies (measured: bitwise that, and not the true quotient)
+        inv_sigma = torch.ones((), dtype=torch.float32) / sigma32
+        # `if augment_sigma >= sigma` (model_v2w.py:229) compares a Python float with the bf16 0-dim tensor: torch rounds the float to
+        # bf16 first, so an augment sigma just under the step's bf16 sigma compares equal and switches the condition region off
+        indicator_off = bool(augment_sigma >= s_bf)
         return dict(c_in_bf16=float(c_in_bf16), c_skip_bf16=float(c_skip_bf16), c_out_bf16=float(c_out_bf16),
                     c_in_step=float(c_in_step), c_skip=float(c_skip), c_out=float(c_out), c_in_aug=float(c_in_aug),
-                    sigma=float(sigma32), sigma_next=float(sigma_next32), indicator_off=bool(augment_sigma >= float(s_bf)))
+                    sigma=float(sigma32), inv_sigma=float(inv_sigma), sigma_next=float(sigma_next32), indicator_off=indicator_off)
 
     @staticmethod
     def _fused_cond_uncond_kwargs(condition: "VideoExtendCondition", uncondition: "VideoExtendCondition", B: int) -> Optional[dict]:
@@ -221,7 +230,7 @@ class Gen3CDenoiser:
             out_c = self.net(x=new_xt_scaled, timesteps=t, **condition.to_dict())
             out_u = self.net(x=new_xt_scaled, timesteps=t, **uncondition.to_dict())
         return ops.edm_cfg_euler_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"],
-                                      co["c_skip"], co["c_out"], co["sigma"], co["sigma_next"])
+                                      co["c_skip"], co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"])
 
     @torch.no_grad()
     def generate_samples_from_batch(self, condition: VideoExtendCondition, uncondition: VideoExtendCondition,

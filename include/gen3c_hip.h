@@ -291,14 +291,16 @@ int g3_timestep_embedding_bf16(const float* timesteps, const void* norm_weight, 
  * elements (hw = H*W, indicator = f32 [T], 1 on conditioning frames). Scalar coefficients are evaluated by the host
  * in the dtypes the reference uses (see gen3c_amd/sampler.py) and passed as floats.
  *   prepare: new_xt = bf16(ind*((gt+noise*aug)*c_in_aug/c_in_bf16) + (1-ind)*xt); new_xt_scaled = bf16(new_xt*c_in_step)
- *   step   : net = cond + g*(cond-uncond); replace conditioning frames by the (un-preconditioned) latent; Euler update. */
+ *   step   : net = cond + g*(cond-uncond); replace conditioning frames by the (un-preconditioned) latent; Euler update
+ *            x + (x - x0) * inv_sigma * (sigma_next - sigma), inv_sigma = fp32 1 / sigma from the host (what torch's device
+ *            division by a CPU 0-dim tensor computes). */
 int g3_edm_prepare_input_bf16(const void* xt, const void* gt_latent, const float* noise, const float* indicator,
                               void* new_xt, void* new_xt_scaled, int64_t n, int T, int hw, float augment_sigma,
                               float c_in_aug, float c_in_bf16, float c_in_step, void* stream);
 int g3_edm_cfg_euler_step_bf16(const void* out_cond, const void* out_uncond, const void* new_xt, const void* gt_latent,
                                const float* indicator, void* xt_next, int64_t n, int T, int hw, float guidance,
                                float c_skip_bf16, float c_out_bf16, float c_skip, float c_out, float sigma,
-                               float sigma_next, void* stream);
+                               float inv_sigma, float sigma_next, void* stream);
 
 /* ---- 3D-cache renderer (all f32; n "items" = (target frame, cache buffer) pairs, each h x w) -----------------------
  * Replaces forward_warp(depth1=None, world_points1=...) + bilinear_splatting + the mesh-occlusion branch

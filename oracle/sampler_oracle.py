@@ -10,6 +10,7 @@ from the published algorithm
 scale_model_input = x / sqrt(sigma^2 + sigma_data^2), step: x0 = c_skip*x + c_out*eps_out, Euler update with dt =
 sigma_next - sigma). The loop body follows the reference's own call sites: model_v2w.py:130-149 and 201-259.
 All math here is fp32 (no bf16 rounding points) - the HIP path is compared within a stated bf16 tolerance.
+The rounding points themselves - which operand is bf16 or fp32, on the device or a CPU scalar - are stated in tests/sampler_ref.py.
 """
 from __future__ import annotations
 
