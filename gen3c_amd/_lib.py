@@ -55,6 +55,8 @@ SIGNATURES = {
     "g3_self_attn_kernel_name": [i32, i32, i32, i32, f32, i32],
     "g3_attn_merge_partials_bf16": [vp, vp, i32, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, vp],
     "g3_transpose_v_bf16": [vp, i64, vp, i64, i32, i32, i32, i32, vp],
+    "g3_cp_scatter_heads_bf16": [vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp],
+    "g3_cp_gather_heads_bf16": [vp, vp, i64, i64, i32, i32, i32, i32, vp],
     "g3_layernorm_modulate_bf16": [vp, i64, vp, vp, i64, i32, vp, i64, i32, i32, f32, vp],
     "g3_posemb_layernorm_modulate_bf16": [vp, i64, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, i64, i32, vp, i64, i32, f32, vp],
     "g3_layernorm_modulate_mxfp8": [vp, i64, vp, vp, i64, i32, vp, i64, vp, i64, i32, i32, f32, vp],

@@ -437,7 +437,7 @@ class VideoExtendGeneralDIT(nn.Module):
         # fastest or within 2 % of the fastest at cp = 2 / 4 / 8, it never waits for the first exchange, and with it the QKV projection stays ONE launch
         # (forward()). The class default stays gather_first (bitwise equal to the single-rank attention).
         self._cp_attn = ContextParallelAttention(cp_group, head_groups=4, schedule="local_first")
-        # G3_CP_CONFIG="<head groups>,<auto|w4b|wave8>,<gather_first|local_first>": the configuration `python bench.py --gpus N` measured fastest on
+        # G3_CP_CONFIG="<head groups>,<auto|w4b|wave8>,<gather_first|local_first|local_carry|head_parallel>": the configuration `python bench.py --gpus N` measured fastest on
         # this node (its `cp.chosen`), for the entry points that do not tune themselves (gen3c_single_image.py --num_gpus N, ...)
         cfg = __import__("os").environ.get("G3_CP_CONFIG")
         if cfg:
@@ -446,9 +446,10 @@ class VideoExtendGeneralDIT(nn.Module):
         self._tables.clear()
 
     def _cp_fused_qkv(self) -> bool:
-        """Context parallel with a schedule whose first phase runs on this rank's own K / V shard (local_first, local_carry): Q, K and V come
-        from ONE fused projection. gather_first projects K | V ahead of Q so that their exchange flies under the Q projection."""
-        return self._cp_attn is not None and self._cp_attn.schedule in ("local_first", "local_carry")
+        """Context parallel with a schedule whose first phase runs on this rank's own K / V shard (local_first, local_carry), or that sends q with
+        k and v (head_parallel): Q, K and V come from ONE fused projection. gather_first projects K | V ahead of Q so that their exchange flies
+        under the Q projection."""
+        return self._cp_attn is not None and self._cp_attn.schedule in ("local_first", "local_carry", "head_parallel")
 
     def disable_context_parallel(self):
         self.cp_group = None
@@ -615,7 +616,8 @@ class VideoExtendGeneralDIT(nn.Module):
                 qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
                                          wq=_mx_rows(blk, "fa_qkv", slice(None)))
                 pending = self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
-                o = self._cp_attn.finish(qkv[:, :D], pending)
+                # (the bound is read by head_parallel only: its launches see all keys of their heads at once, as the single-GPU call below)
+                o = self._cp_attn.finish(qkv[:, :D], pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)
             elif self._cp_attn is not None:
                 # K / V first, so their exchange is in flight while Q is still being projected (same fused weight, sliced;
                 # every output element sees the same K order, so this is bit-identical to the single fused GEMM)

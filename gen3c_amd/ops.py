@@ -428,6 +428,44 @@ def transpose_v(v: torch.Tensor, S: int, B: int, H: int, out: Optional[torch.Ten
     return out
 
 
+def cp_scatter_heads(q: Optional[torch.Tensor], k: Optional[torch.Tensor], v: Optional[torch.Tensor], H: int, n_dest: int, head0: int, Hg: int,
+                     out=None):
+    """Send layout of the head-parallel exchange (g3_cp_scatter_heads_bf16). q, k, v: [rows, H*128] column views of ONE buffer (the same row
+    stride; any of them None) -> per given tensor a contiguous [n_dest, rows, Hg*128]: destination d's block holds the heads
+    d * (H / n_dest) + head0 .. + Hg of every row. Returns (q_out, k_out, v_out), None where the input is None. out: the same triple to write into."""
+    given = [t for t in (q, k, v) if t is not None]
+    if not given:
+        raise _lib.Gen3cHipError("cp_scatter_heads: q, k and v are all None")
+    rows, width, ld = _rowmajor2d(given[0], "q/k/v")
+    for t in given:
+        if _rowmajor2d(t, "q/k/v") != (rows, width, ld) or t.device != given[0].device:
+            raise _lib.Gen3cHipError("cp_scatter_heads: q, k and v must be column views of one buffer (same shape, row stride and device)")
+    if width != H * 128:
+        raise _lib.Gen3cHipError(f"cp_scatter_heads: expected {H * 128} columns, got {width}")
+    if out is None:
+        out = tuple(None if t is None else torch.empty((n_dest, rows, Hg * 128), dtype=torch.bfloat16, device=t.device) for t in (q, k, v))
+    for t, o in zip((q, k, v), out):
+        if t is not None and (o is None or tuple(o.shape) != (n_dest, rows, Hg * 128) or not o.is_contiguous()):
+            raise _lib.Gen3cHipError(f"cp_scatter_heads: every output must be a contiguous {(n_dest, rows, Hg * 128)} tensor")
+    ptr = lambda t, name: 0 if t is None else _dev(t, name)
+    _lib.check(_lib.load().g3_cp_scatter_heads_bf16(ptr(q, "q"), ptr(k, "k"), ptr(v, "v"), ld, *(ptr(o if t is not None else None, "out") for t, o in zip((q, k, v), out)),
+                                                    rows, H, n_dest, head0, Hg, _stream()), "g3_cp_scatter_heads_bf16")
+    return tuple(o if t is not None else None for t, o in zip((q, k, v), out))
+
+
+def cp_gather_heads(x: torch.Tensor, out: torch.Tensor, H: int, head0: int) -> torch.Tensor:
+    """Inverse of cp_scatter_heads for one tensor (g3_cp_gather_heads_bf16): x [n_src, rows, Hg*128] contiguous, as the returning all-to-all
+    delivers it, into the columns (s * (H / n_src) + head0) * 128 .. of out [rows, H*128] (a view with any row stride); other columns stay."""
+    if x.dim() != 3 or not x.is_contiguous() or x.shape[2] % 128:
+        raise _lib.Gen3cHipError(f"cp_gather_heads: expected a contiguous [n_src, rows, Hg*128] tensor, got {tuple(x.shape)} strides {x.stride()}")
+    n_src, rows, W = x.shape
+    orows, width, ld = _rowmajor2d(out, "out")
+    if (orows, width) != (rows, H * 128):
+        raise _lib.Gen3cHipError(f"cp_gather_heads: out must be [{rows}, {H * 128}], got {tuple(out.shape)}")
+    _lib.check(_lib.load().g3_cp_gather_heads_bf16(_dev(x, "x"), _dev(out, "out"), ld, rows, H, n_src, head0, W // 128, _stream()), "g3_cp_gather_heads_bf16")
+    return out
+
+
 def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int,
                out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False, kv_dense: int = 0,
                q_norm_weight: Optional[torch.Tensor] = None, q_norm_eps: float = 1e-6, carry=None, kv_skip=None):

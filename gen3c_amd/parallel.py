@@ -7,7 +7,8 @@ Mirrors the reference surface
 but NOT its communication pattern. The reference lets TransformerEngine run a P2P *ring* over the CP ranks
 (general_dit.py:540-541), which on xGMI's point-to-point mesh is bound by a single ~153 GB/s link. Here every rank's
 K / V shard is exchanged with a direct all-gather (all 7 links busy at once), split into head groups so that the
-attention kernel of group g runs on the compute stream while RCCL is still gathering group g+1.
+attention kernel of group g runs on the compute stream while RCCL is still gathering group g+1. An opt-in schedule, "head_parallel",
+exchanges heads for tokens with two all-to-alls instead (ContextParallelAttention below).
 
 Token layout: rows are (s, b) pairs with b fastest and the latent frames sharded contiguously over ranks, so a
 rank-major all-gather of row blocks IS the global (s, b) order - no re-sort after the collective.
@@ -180,7 +181,7 @@ def run_jobs_round_robin(jobs: List[Callable[[], torch.Tensor]], group, shape, d
 # context-parallel self-attention
 # ------------------------------------------------------------------------------------------------------------------
 ATTN_KERNELS = {"auto": None, "w4b": 11, "wave8": 4}  # per-call kernel choice of g3_flash_attn_fwd_ex_bf16 ("auto": the even-fill rule below)
-CP_SCHEDULES = ("gather_first", "local_first", "local_carry")
+CP_SCHEDULES = ("gather_first", "local_first", "local_carry", "head_parallel")
 
 
 def _default_backend():
@@ -193,8 +194,24 @@ def _default_backend():
         merge=lambda parts, Sq, B, H, out: ops.attn_merge(parts, Sq, B, H, out=out),
         attention_carry=lambda q, k, vt, Sq, Skv, B, H, out=None, carry=None, kv_skip=None, partial=False, variant=0: ops.flash_attn(
             q, k, vt, Sq, Skv, B, H, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
+        scatter_heads=lambda q, k, v, H, n_dest, head0, Hg: ops.cp_scatter_heads(q, k, v, H, n_dest, head0, Hg),
+        gather_heads=lambda x, out, H, head0: ops.cp_gather_heads(x, out, H, head0),
+        attention_bounded=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out, variant=0: ops.self_attn_bounded(
+            q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant),
         timer=ops.HipTimer,
     )
+
+
+class _HostStagedWork:
+    """Work of a collective that ran on host copies of device tensors: wait() also enqueues the copy of the result back to the device."""
+
+    def __init__(self, work, host: torch.Tensor, dev: torch.Tensor):
+        self.work, self.host, self.dev = work, host, dev
+
+    def wait(self):
+        self.work.wait()
+        self.dev.copy_(self.host)
+        return True
 
 
 class ContextParallelAttention:
@@ -213,6 +230,12 @@ class ContextParallelAttention:
     remote key - an interior rank skips its own block inside the gathered buffers (g3_flash_attn_fwd_carry_bf16's kv_skip) - that carries the
     phase-1 state in and writes bf16 straight into the group's columns of the output: two launches per group, no merge pass. Needs a backend with
     "attention_carry", segmented V^T and world > 1; otherwise it runs as "local_first" (and `effective` says so).
+    schedule "head_parallel" (DeepSpeed-Ulysses): HEADS are sharded instead of keys. Per head group one g3_cp_scatter_heads_bf16 launch packs q, k and
+    v by destination rank, three all-to-alls hand this rank ALL tokens of its H / world heads of the group, the ordinary full-length self-attention
+    runs on them (Sq = Skv = S_all, plain V^T: with `logit_bound` the no-running-max kernel applies), a fourth all-to-all returns the output and
+    g3_cp_gather_heads_bf16 writes it into the group's columns. No partials, no merge, a quarter of the exchanged bytes at cp = 8; the first group's
+    exchange and the last group's return hide behind nothing. Needs H % world == 0 and a backend with "scatter_heads", "gather_heads" and
+    "attention_bounded"; otherwise it runs as "local_first" (and `effective` says so). Runs at world 1 too (a self-exchange).
 
     kernel: "auto" (the one-wave-per-SIMD kernel when the groups' workgroups together fill the 256 CUs evenly, else the 8-wave kernel), "w4b",
     "wave8" - passed PER CALL through the C ABI; no process-wide option is touched (launches go out on two streams).
@@ -252,8 +275,12 @@ class ContextParallelAttention:
 
         V is transposed LOCALLY (this rank's S_local keys) and the V^T shards are gathered rank-major; the attention kernel reads
         them as key segments, so no rank re-transposes the full-length V (needs S_local % 64 == 0, true for the 3 520-token
-        latent frames; otherwise V is gathered row-major and transposed after the exchange)."""
+        latent frames; otherwise V is gathered row-major and transposed after the exchange).
+        "head_parallel" sends q together with k and v, so nothing goes out here: k and v are kept for finish()."""
         be = self.backend or _default_backend()
+        if self.schedule == "head_parallel" and H % self.world == 0 and all(n in be for n in ("scatter_heads", "gather_heads", "attention_bounded")):
+            # nothing can go out before q exists: one scatter launch fills the q, k and v send buffers of a head group (finish())
+            return dict(head_parallel=True, k=k, v=v, S_local=S_local, B=B, H=H, rows=S_local * B, be=be)
         G = self.head_groups
         while H % G != 0:
             G -= 1
@@ -301,7 +328,86 @@ class ContextParallelAttention:
             tm.stop()
             self.stats.append(("wait", g, tm))
 
-    def finish(self, q: torch.Tensor, pending: dict) -> torch.Tensor:
+    def _all_to_all(self, recv: torch.Tensor, send: torch.Tensor):
+        """Async single-tensor all-to-all of equal chunks (send / recv: contiguous [world, ...]) -> a Work. Device tensors on a gloo group (tests
+        and tools/cp_check.py with several ranks on one GPU; the product path is RCCL) are staged through host memory: only the single-tensor
+        all-to-all on CPU tensors is relied on with gloo."""
+        if send.is_cuda and dist.get_backend(self.group) == "gloo":
+            host = torch.empty(recv.shape, dtype=recv.dtype)
+            return _HostStagedWork(dist.all_to_all_single(host, send.cpu(), group=self.group, async_op=True), host, recv)
+        return dist.all_to_all_single(recv, send, group=self.group, async_op=True)
+
+    def _finish_head_parallel(self, q: torch.Tensor, pending: dict, logit_bound: float) -> torch.Tensor:
+        be, B, S_local, H, rows, k, v = (pending[n] for n in ("be", "B", "S_local", "H", "rows", "k", "v"))
+        P = self.world
+        Hl = H // P
+        G = max(1, min(self.head_groups, Hl))
+        while Hl % G != 0:
+            G -= 1
+        Hg = Hl // G
+        S_all = S_local * P
+        # the launches' own shape - all tokens as queries - with the heads of ALL groups: as for the other schedules the groups run back to back on two
+        # streams and the chip sees their sum. (Per group the even-fill rule picks the 8-wave kernel at cp = 8 with G >= 2, and loses the
+        # no-running-max kernel with it: 478.8 against 425.7 ms per emulated step, profiles/cp_head_parallel_emulated.txt.)
+        variant = self._variant(S_all, S_all, B, Hl) if q.is_cuda else 0
+        self.effective = dict(schedule="head_parallel", kernel={11: "w4b", 4: "wave8"}.get(variant, str(variant)), head_groups=G)
+        out = torch.empty((rows, H * 128), dtype=q.dtype, device=q.device)
+        two_streams = q.is_cuda and G >= 2
+        main = side = q_ready = None
+        if two_streams:
+            main = torch.cuda.current_stream(q.device)
+            side = self._side_stream(q.device)
+            q_ready = main.record_event()  # q, k, v (and `out`) were produced / allocated on the main stream
+
+        def on_stream(g):
+            return torch.cuda.stream(main if g % 2 == 0 else side) if two_streams else _NullCtx()
+
+        # Lifetime contract (as in finish()): every send / receive buffer is read or written by the collective's own stream and by HIP kernels launched
+        # through ctypes; `keep` references all of them until the last consumer - the gather of the last group - is enqueued.
+        keep = []
+        try:
+            for g in range(G):
+                with on_stream(g):
+                    if two_streams and g % 2 == 1:
+                        side.wait_event(q_ready)
+                    qs, ks, vs = be["scatter_heads"](q, k, v, H, P, g * Hg, Hg)  # [P, rows, Hg*128] each: chunk p goes to rank p
+                    kr, vr, qr = torch.empty_like(ks), torch.empty_like(vs), torch.empty_like(qs)  # rank-major = the global (s, b) row order
+                    works = [self._all_to_all(kr, ks), self._all_to_all(vr, vs), self._all_to_all(qr, qs)]
+                    self.bytes_gathered += 3 * (P - 1) * ks[0].numel() * ks.element_size()
+                    keep.append([works, (qs, ks, vs), (qr, kr, vr)])
+            for g in range(G):
+                with on_stream(g):
+                    (wk, wv, wq), _sent, (qr, kr, vr) = keep[g]
+                    self._wait(be, g, wv)
+                    vt = be["transpose_v"](vr.view(S_all * B, Hg * 128), S_all, B, Hg)  # plain V^T over all keys
+                    self._wait(be, g, wk)
+                    self._wait(be, g, wq)
+                    ob = torch.empty_like(qr)  # [S_all*B, Hg*128] in row blocks of `rows`: already one chunk per destination rank
+                    qa, ka, oa = (t.view(S_all * B, Hg * 128) for t in (qr, kr, ob))
+                    if logit_bound > 0:
+                        be["attention_bounded"](qa, ka, vt, S_all, S_all, B, Hg, logit_bound, oa, variant=variant)
+                    else:
+                        be["attention"](qa, ka, vt, S_all, S_all, B, Hg, oa, variant=variant)
+                    orecv = torch.empty_like(ob)
+                    wo = self._all_to_all(orecv, ob)
+                    self.bytes_gathered += (P - 1) * ob[0].numel() * ob.element_size()
+                    keep[g] += [vt, ob, orecv, wo]
+            for g in range(G):
+                with on_stream(g):
+                    orecv, wo = keep[g][-2:]
+                    self._wait(be, g, wo)
+                    be["gather_heads"](orecv, out, H, g * Hg)  # chunk p: heads p * Hl + g * Hg .. of this rank's rows
+        finally:
+            if two_streams:
+                main.wait_stream(side)
+        del keep
+        return out
+
+    def finish(self, q: torch.Tensor, pending: dict, logit_bound: float = 0.0) -> torch.Tensor:
+        """logit_bound > 0 (a caller's bound on |q . k| * softmax_scale, see ops.self_attn_bounded) is used by "head_parallel" only: the other
+        schedules shard a row's keys over launches, which the no-running-max kernel does not take."""
+        if pending.get("head_parallel"):
+            return self._finish_head_parallel(q, pending, logit_bound)
         be, W, Hg, B, S_local = pending["be"], pending["W"], pending["Hg"], pending["B"], pending["S_local"]
         S_all = S_local * self.world
         out = torch.empty((pending["rows"], pending["H"] * 128), dtype=q.dtype, device=q.device)
@@ -315,7 +421,8 @@ class ContextParallelAttention:
         variant = self._variant(S_local, S_all, B, pending["H"]) if q.is_cuda else 0
         split = pending["segmented"] and self.world > 1
         local_carry = self.schedule == "local_carry" and split and "attention_carry" in be
-        local_first = not local_carry and self.schedule in ("local_first", "local_carry") and split and "attention_partial" in be
+        # (a "head_parallel" request that start() could not honour - H % world != 0, a backend without the exchange callables - runs as local_first)
+        local_first = not local_carry and self.schedule in ("local_first", "local_carry", "head_parallel") and split and "attention_partial" in be
         # what this layer actually runs (a requested "local_first" needs segmented V^T and a split-KV backend; a forced one-wave kernel needs
         # S_all % 64 == 0): read by bench.py so that its autotune table and `cp.chosen` never label a fallback with the requested name
         self.effective = dict(schedule="local_carry" if local_carry else "local_first" if local_first else "gather_first",
@@ -398,8 +505,8 @@ class ContextParallelAttention:
             st = self._side = torch.cuda.Stream(device=device)
         return st
 
-    def __call__(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, S_local: int, B: int, H: int) -> torch.Tensor:
-        return self.finish(q, self.start(k, v, S_local, B, H))
+    def __call__(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, S_local: int, B: int, H: int, logit_bound: float = 0.0) -> torch.Tensor:
+        return self.finish(q, self.start(k, v, S_local, B, H), logit_bound)
 
 
 class _NullCtx:

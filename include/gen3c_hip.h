@@ -216,6 +216,20 @@ int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const floa
 int g3_transpose_v_bf16(const void* v, int64_t ld_in, void* vt, int64_t ldvt, int S, int B, int H, int head_dim,
                         void* stream);
 
+/* Head-parallel context parallelism: the layout passes around an all-to-all that trades a rank's tokens of ALL heads for all tokens of H / n
+ * heads, in place of the K / V ring TransformerEngine runs behind attn_op.set_context_parallel_group (general_dit.py:536-541) and next to
+ * split_inputs_cp / cat_outputs_cp (module/parallel.py:25-87), which shard the same rows.
+ * scatter: for each non-NULL x of q, k, v (column views [rows][H * 128] of one buffer with row stride ld_in; any of them may be NULL, not all):
+ *   x_out[d][r][j] = x[r][(d * (H / n_dest) + head0) * 128 + j],  d < n_dest, r < rows, j < Hg * 128;
+ *   x_out is contiguous [n_dest][rows][Hg * 128]: one contiguous chunk per destination rank, what a single-tensor all-to-all sends.
+ * gather (the inverse, after the returning all-to-all): in [n_src][rows][Hg * 128] contiguous ->
+ *   out[r][(s * (H / n_src) + head0) * 128 + j] = in[s][r][j],  out rows of stride ld_out; the other columns of out are not touched.
+ * 16-byte loads and stores, 64-bit offsets. G3_ERR_ARG before any launch: H % n != 0, head0 + Hg > H / n (or head0 < 0, Hg <= 0), rows <= 0,
+ * a leading dimension below H * 128 or not a multiple of 8, a pointer that is not 16-byte aligned, an input without its output. */
+int g3_cp_scatter_heads_bf16(const void* q, const void* k, const void* v, int64_t ld_in, void* q_out, void* k_out, void* v_out, int64_t rows,
+                             int H, int n_dest, int head0, int Hg, void* stream);
+int g3_cp_gather_heads_bf16(const void* in, void* out, int64_t ld_out, int64_t rows, int H, int n_src, int head0, int Hg, void* stream);
+
 /* ---- norms -----------------------------------------------------------------------------------------------------
  * out = LayerNorm(x; no affine, eps) * (1 + scale[row % mod_rows]) + shift[row % mod_rows]
  * replaces DITBuildingBlock.norm_state + adaln_norm_state (blocks.py:339-341, 408) and FinalLayer (blocks.py:204, 239). */

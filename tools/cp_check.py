@@ -53,7 +53,8 @@ def main():
     # both collective schedules of ContextParallelAttention, 2 head groups (alternating streams): "gather_first" = one launch per head group over
     # the gathered keys (same arithmetic per row as the non-CP call); "local_first" = own shard first, remote segments after the exchange,
     # fp32 partials merged (one extra rounding pattern: not bitwise, same tolerance)
-    # G3_CP_CHECK_SCHEDULES="local_carry" (tests/test_cp_carry_gpu.py): other schedules, same bar; the schedule that actually ran is printed
+    # G3_CP_CHECK_SCHEDULES="local_carry" (tests/test_cp_carry_gpu.py) or "head_parallel" (tests/test_cp_exchange_gpu.py; needs 4 % ranks == 0): other
+    # schedules, same bar; the schedule that actually ran is printed
     for sched in os.environ.get("G3_CP_CHECK_SCHEDULES", "gather_first,local_first").split(","):
         net._cp_attn.configure(head_groups=2, schedule=sched)
         part = den.denoise_step(split_inputs_cp(xt, 2, net.cp_group), 5, c, u, 1.0, 0.001, 1)

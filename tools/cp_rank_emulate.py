@@ -1,7 +1,7 @@
 """One GPU plays ONE RANK of a context-parallel run of the full-size denoise step: the PRODUCT code path - Gen3CDenoiser.denoise_step ->
 VideoExtendGeneralDIT.forward with context parallelism enabled -> parallel.ContextParallelAttention, every kernel at the per-rank shapes of cp = 1 / 2 / 4 / 8
-(M = 2 x S_local rows, attention Sq = S_local against all 56 320 keys in head groups on two streams) - with torch.distributed's three calls the path makes
-(get_world_size / get_rank / all_gather_into_tensor) replaced by an in-process stand-in that plays rank `--rank` of `cp` ranks: the "exchange" is a
+(M = 2 x S_local rows, attention Sq = S_local against all 56 320 keys in head groups on two streams) - with the torch.distributed calls the path makes
+(get_world_size / get_rank / get_backend / all_gather_into_tensor / all_to_all_single) replaced by an in-process stand-in that plays rank `--rank` of `cp` ranks: the "exchange" is a
 device copy of this rank's shard into every slot of the gathered buffer on a separate stream (the bytes a real exchange would deliver into HBM; the values of the
 other ranks' keys are this rank's own - irrelevant for timing). What this measures: the COMPUTE side of a rank's step with today's kernels, launch gaps included.
 What it cannot: the xGMI exchange itself - the model printed at the end adds it under stated assumptions.
@@ -9,7 +9,8 @@ What it cannot: the xGMI exchange itself - the model printed at the end adds it 
   python tools/cp_rank_emulate.py [--cps 1,2,4,8] [--steps 3] [--blocks 28] [--configs 4,auto,gather_first;4,w4b,gather_first;...] [--out gpurun_out/r6_cp_rank_shapes.json]
 
 Schedules (the third field of a config): gather_first, local_first, local_carry (own-shard partial, then ONE carry launch per head group over every remote
-key - no merge pass). The exchange model below replays each of them.
+key - no merge pass), head_parallel (heads sharded by two all-to-alls around the ordinary full-length attention; the stand-in's all-to-all is a device
+copy of the same size). The exchange model below replays each of them.
 """
 import argparse
 import json
@@ -39,7 +40,7 @@ class _Work:
 
 
 class FakeRank:
-    """Stand-in for the three torch.distributed calls on the CP path: plays rank `rank` of `world`."""
+    """Stand-in for the torch.distributed calls on the CP path: plays rank `rank` of `world`."""
 
     def __init__(self, world, rank, dev):
         self.world, self.rank = world, rank
@@ -48,11 +49,13 @@ class FakeRank:
         self._orig = {}
 
     def __enter__(self):
-        for name in ("get_world_size", "get_rank", "all_gather_into_tensor"):
+        for name in ("get_world_size", "get_rank", "get_backend", "all_gather_into_tensor", "all_to_all_single"):
             self._orig[name] = getattr(dist, name)
         dist.get_world_size = lambda group=None: self.world
         dist.get_rank = lambda group=None: self.rank
+        dist.get_backend = lambda group=None: "nccl"
         dist.all_gather_into_tensor = self._all_gather
+        dist.all_to_all_single = self._all_to_all
         return self
 
     def __exit__(self, *exc):
@@ -67,6 +70,20 @@ class FakeRank:
             out.view(self.world, -1).copy_(inp.reshape(1, -1).expand(self.world, -1))
             ev = self.comm.record_event()
         self.bytes += (self.world - 1) * inp.numel() * inp.element_size()
+        w = _Work(ev)
+        if not async_op:
+            w.wait()
+        return w
+
+
+    def _all_to_all(self, out, inp, group=None, async_op=False):
+        """A device copy of the same size on the stand-in's stream: 1 / world of it stays on the rank, the rest is what a real exchange would deliver."""
+        cur = torch.cuda.current_stream()
+        self.comm.wait_stream(cur)
+        with torch.cuda.stream(self.comm):
+            out.copy_(inp)
+            ev = self.comm.record_event()
+        self.bytes += (self.world - 1) * (inp.numel() // self.world) * inp.element_size()
         w = _Work(ev)
         if not async_op:
             w.wait()
@@ -224,6 +241,8 @@ def main():
         # once its exchange has landed, the merge pass folded into that launch's epilogue - its saving is inside the measured attention time). Attention wall time per layer = this run's step time minus its GEMM time minus the HBM-bound rest (the
         # cp = 1 rest scaled by 1 / cp) - launches on two streams overlap, so their summed durations overstate it. RCCL's own CU use while a collective is in flight is
         # NOT modelled (no second GPU here); the driver's --gpus 8 run measures all of it (bench.py `cp` object).
+        # head_parallel: per layer and head group four all-to-alls of one size (k, v, q out, o back). Nothing runs before the first group's k, v and q have landed
+        # and nothing hides the last group's o: those four are counted as exposed, every other exchange as hidden under the groups' attention.
         base_attn = sum(c["ms_per_step"] for c in base["classes"] if c["kind"] == "attn")
         base_gemm = sum(c["ms_per_step"] for c in base["classes"] if c["kind"] == "gemm")
         base_rest = base["ms_per_step"] - base_attn - base_gemm
@@ -238,6 +257,7 @@ def main():
             gemm = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm")
             cross = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "attn" and c["Skv"] <= 2048)
             attn_layer = max(0.0, r["ms_per_step"] - gemm - cross - base_rest / cp) / layers
+            r["self_attention_and_cp_ms_per_layer"] = round(attn_layer, 3)
             q_ms = 0.0
             if sched == "gather_first":  # the self-attention Q projection: one of the two plain N = 4096 launches per block (the other is the cross-attention Q)
                 q_ms = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm" and c["N"] == 4096 and c["K"] == 4096 and c["epilogue"] == 0) / 2 / layers
@@ -253,6 +273,8 @@ def main():
                     for g_ in range(G):
                         t = max(t, (g_ + 1) * ex_g) + attn_layer * (cp - 1) / cp / G
                     exposed = t - attn_layer
+                elif sched == "head_parallel":
+                    exposed = ex_g  # 3 of the first group's 4 tensors + 1 of the last group's 4 = one group's exchange
                 else:
                     raise ValueError(f"exchange model: unknown schedule {sched}")
                 pred = r["ms_per_step"] + layers * exposed
@@ -265,6 +287,17 @@ def main():
             lines.append(f"cp={cp} @ {bw:.0f} GB/s: best {r['effective']}: compute {r['ms_per_step']:.1f} ms/step (measured, one GPU as rank {r['rank']}); exchange "
                          f"{r['gathered_bytes_per_step'] / 1e9:.1f} GB/step = {ex_layer:.2f} ms/layer vs attention {attn_layer:.2f} ms/layer (+ Q {q_ms:.2f}) -> exposed {exposed:.2f} ms/layer; "
                          f"predicted {pred:.1f} ms/step = {base['ms_per_step'] / pred:.2f} x (compute only: {base['ms_per_step'] / r['ms_per_step']:.2f} x)")
+        lines.append("")
+        lines.append("per run (compute measured on one GPU as one rank; predicted = compute + exposed exchange at 250 / 375 / 500 GB/s into the rank):")
+        lines.append(f"{'cp':>3} {'requested':<24} {'effective':<24} {'self-attn + CP ms/layer':>24} {'compute ms/step':>16} {'received GB/step':>17}  predicted ms/step")
+        for r in allres:
+            if r["cp"] == 1 or "predicted" not in r:
+                continue
+            c, e = r["config"], r["effective"] or {}
+            pr = r["predicted"]
+            lines.append(f"{r['cp']:>3} {'%d,%s,%s' % (c['head_groups'], c['kernel'], c['schedule']):<24} "
+                         f"{'%s,%s,%s' % (e.get('head_groups'), e.get('kernel'), e.get('schedule')):<24} {r['self_attention_and_cp_ms_per_layer']:>24.2f} {r['ms_per_step']:>16.1f} "
+                         f"{r['gathered_bytes_per_step'] / 1e9:>17.2f}  {pr['250']['ms_per_step']:.1f} / {pr['375']['ms_per_step']:.1f} / {pr['500']['ms_per_step']:.1f}")
     text = "\n".join(lines)
     print(text)
     out = Path(args.out)
