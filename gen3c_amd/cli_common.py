@@ -56,6 +56,9 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--dit_mxfp8_producers", choices=("separate", "fused"), default="separate",
                    help="with --dit_precision mxfp8: separate (default) quantises every linear's input in a pass of its own; fused lets the LayerNorm "
                         "passes and the MLP-up GEMM emit MXFP8 directly (same output bit for bit). No effect with bf16; accepted and inert with mxfp6, which has no fused producers")
+    p.add_argument("--cp_logit_bound", action="store_true",
+                   help="with --num_gpus > 1: the key-sharding context-parallel schedules run self-attention without a running row maximum, on the "
+                        "blocks' QK-norm logit bound (opt-in, default off; same as G3_CP_LOGIT_BOUND=1)")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -192,6 +195,8 @@ class Session:
         if args.num_gpus > 1:
             self.cp_group = parallel_state.get_context_parallel_group()
             net.enable_context_parallel(self.cp_group)
+            if getattr(args, "cp_logit_bound", False):
+                net._cp_attn.configure(bounded=True)
         if getattr(args, "dit_precision", "bf16") != "bf16":
             net.set_linear_precision(args.dit_precision)
             print(f"[gen3c_amd] --dit_precision {args.dit_precision}: the DiT block linears run on {args.dit_precision.upper()} operands; this mode is "

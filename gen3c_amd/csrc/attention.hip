@@ -73,8 +73,8 @@ struct AttnParams {
     const float* carry_lse;
     int kv_skip_begin, kv_skip_len;
     uint32_t kv_skip_vt_bytes;
-    // no-max form (flash_attn_fwd_w4b_nm_kernel; g3_self_attn_fwd_bounded_bf16): the caller's bound on |q.k| * scale_log2, the constant reference point of
-    // the softmax. No other kernel reads it.
+    // no-max form (flash_attn_fwd_w4b_nm_kernel, flash_attn_fwd_w4b_nm_carry_kernel; g3_self_attn_fwd_bounded_bf16, g3_self_attn_fwd_bounded_cp_bf16): the
+    // caller's bound on |q.k| * scale_log2, the constant reference point of the softmax. No other kernel reads it.
     float logit_bound_log2;
 };
 
@@ -1017,6 +1017,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 #define W4B_CP 0
 #define W4B_NM 1
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_kernel: the same kernel without the running row maximum (bounded logits)
+#undef W4B_CP
+#define W4B_CP 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_carry_kernel: the no-max form with the CP form (g3_self_attn_fwd_bounded_cp_bf16)
 #undef W4B_NM
 #undef W4B_CP
 
@@ -1064,13 +1067,31 @@ extern "C" const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, f
     return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, variant);
 }
 
+// The kernel g3_flash_attn_fwd_carry_bf16 launches where the plain entry points launch the one named by g3_flash_attn_kernel_name_ex
+static const char* attn_carry_kernel_name(int Sq, int Skv, int B, int H, int variant_req) {
+    switch (attn_resolve_variant(Sq, Skv, B, H, variant_req)) {
+        case 11: return "flash_attn_fwd_w4b_carry_kernel<true>";
+        case 4: return Skv > 2048 ? "flash_attn_fwd_v3_kernel<2, 6, 8, true>" : "flash_attn_fwd_v3_kernel<3, 6, 8, false>";
+        default: return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, variant_req);  // (refused by the entry point)
+    }
+}
+
+// Skv: the attended keys (a skipped range not counted); segmented: V^T in key segments (the name does not depend on it: both forms run the same
+// kernels); cp_form: a carry-in state, or a skipped range strictly inside the keys (0 < kv_skip_begin < S_kv, kv_skip_len > 0)
+extern "C" const char* g3_self_attn_cp_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant, int segmented, int cp_form) {
+    (void)segmented;
+    if (attn_resolve_variant(Sq, Skv, B, H, variant) == 11 && attn_bound_usable(attn_bound_log2(logit_bound)))
+        return cp_form ? "flash_attn_fwd_w4b_nm_carry_kernel<true>" : "flash_attn_fwd_w4b_nm_kernel<true>";
+    return attn_carry_kernel_name(Sq, Skv, B, H, variant);
+}
+
 static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
                              int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                              int64_t vt_seg_stride, void* o, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H,
                              int head_dim, float softmax_scale, void* stream, int variant_req = 0, float* o_partial = nullptr, float* lse = nullptr, int kv_dense = 0,
                              const void* q_norm_w = nullptr, float q_norm_eps = 0.f, bool cp_form = false, const float* carry_o = nullptr,
                              const float* carry_lse = nullptr, int kv_skip_begin = 0, int kv_skip_len = 0, uint32_t kv_skip_vt_bytes = 0,
-                             float logit_bound = 0.f) {
+                             float logit_bound = 0.f, bool bounded_cp = false) {
     if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: null operand");
     if ((o_partial != nullptr) != (lse != nullptr)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial and lse go together");
     if (o_partial && (((uintptr_t)o_partial & 15) || ((uintptr_t)lse & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: misaligned o_partial / lse");
@@ -1152,7 +1173,8 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     {
       std::lock_guard<std::mutex> attr_lock(attr_mu);
       if (!attr_set[dev_id]) {
-        const void* fns[20] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_kernel<true>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
+        const void* fns[21] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_carry_kernel<true>),
+                               reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_kernel<true>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<2, 6, 8, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<3, 6, 8, false>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<false>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_kernel<1>),
@@ -1162,7 +1184,7 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false, true>),
                                reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<1>)};
-        for (int i = 0; i < 20; ++i) {
+        for (int i = 0; i < 21; ++i) {
             hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
             if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
         }
@@ -1177,9 +1199,13 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
         p.grid_q = (int)grid4.x; p.n_hb = H * B; p.n_heads = H;
         p.xcd_heads = (g3_opt_attn_xcd_heads && (H * B) % 8 == 0) ? 1 : 0;
         if (p.xcd_heads) grid4 = dim3(grid4.x * H * B, 1, 1);
-        // bounded logits (g3_self_attn_fwd_bounded_bf16): the no-max form, for the plain XB kernel's problems only; everything else runs as it always did
-        const bool no_max = variant == 11 && !cp_form && vt_seg_len == 0 && !p.kv_dense && attn_bound_usable(p.logit_bound_log2);
-        if (no_max) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        // bounded logits: the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems only. g3_self_attn_fwd_bounded_cp_bf16
+        // (bounded_cp): also with segmented V^T, and - flash_attn_fwd_w4b_nm_carry_kernel - with a carry-in state or a skipped key range (the entry
+        // point has normalised a skip at either end away). Everything else runs as it always did.
+        const bool bound_ok = variant == 11 && !p.kv_dense && attn_bound_usable(p.logit_bound_log2);
+        const bool no_max = bound_ok && (bounded_cp || (!cp_form && vt_seg_len == 0));
+        if (no_max && cp_form && (carry_o || kv_skip_len > 0)) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
+        else if (no_max) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else if (cp_form) hipLaunchKernelGGL(flash_attn_fwd_w4b_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else if (variant == 11) hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
         else hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<false>, grid4, dim3(W4_THREADS), smem, st, p);
@@ -1262,12 +1288,13 @@ extern "C" int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64
 }
 
 /* ---- carry-in state + skipped key range (context parallelism without a merge pass) --------------------------------------------------------- */
-extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
-                                            int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
-                                            int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
-                                            const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
-                                            int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
-                                            void* stream) {
+// (logit_bound / bounded_cp: g3_self_attn_fwd_bounded_cp_bf16 - the same checks in the same order, so that what it cannot run bounded IS this entry)
+static int flash_attn_carry_entry(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                  int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                  int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                  const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
+                                  int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
+                                  void* stream, float logit_bound, bool bounded_cp) {
     const char* fn = "g3_flash_attn_fwd_carry_bf16";
     if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "%s: variant %d out of range", fn, variant);
     if (o && o_partial) return g3_set_error(G3_ERR_ARG, "%s: pass either o (bf16 result) or o_partial + lse, not both", fn);
@@ -1298,7 +1325,30 @@ extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_
     if (vt_jump_bytes > 0xFFFFFFFFll) return g3_set_error(G3_ERR_ARG, "%s: the skipped V^T range exceeds the kernel's 32-bit byte offsets", fn);
     return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
                              o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse, 0, nullptr, 0.f, true, carry_o,
-                             carry_lse, kv_skip_begin, kv_skip_len, (uint32_t)vt_jump_bytes);
+                             carry_lse, kv_skip_begin, kv_skip_len, (uint32_t)vt_jump_bytes, logit_bound, bounded_cp);
+}
+
+extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                            int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                            int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                            const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
+                                            int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
+                                            void* stream) {
+    return flash_attn_carry_entry(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, kv_skip_begin,
+                                  kv_skip_len, carry_o, carry_lse, o, o_partial, lse, o_row, o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, variant, stream,
+                                  0.f, false);
+}
+
+/* ---- the same with bounded logits: the no-max kernels under key sharding (segmented V^T, carry-in, skipped key range), else exactly the entry above ------ */
+extern "C" int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                                int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                                int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                                const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
+                                                int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, float logit_bound,
+                                                int variant, void* stream) {
+    return flash_attn_carry_entry(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, kv_skip_begin,
+                                  kv_skip_len, carry_o, carry_lse, o, o_partial, lse, o_row, o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, variant, stream,
+                                  logit_bound, true);
 }
 
 namespace {

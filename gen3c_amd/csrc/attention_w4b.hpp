@@ -1,6 +1,6 @@
-// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace - three times: W4B_CP 0 defines the helpers and
+// Included by attention.hip after attention_w4.hpp, inside the same anonymous namespace - four times: W4B_CP 0 defines the helpers and
 // flash_attn_fwd_w4b_kernel, W4B_CP 1 flash_attn_fwd_w4b_carry_kernel (the CP form, see below; the plain kernel compiles without it),
-// W4B_NM 1 flash_attn_fwd_w4b_nm_kernel (the no-max form, see below).
+// W4B_NM 1 flash_attn_fwd_w4b_nm_kernel (the no-max form, see below), W4B_NM 1 + W4B_CP 1 flash_attn_fwd_w4b_nm_carry_kernel (both).
 //
 // w4b: the one-wave-per-SIMD self-attention kernel (see attention_w4.hpp for the why) with the issue stream of a tile trimmed to what the
 // SIMD can hide under its MFMAs (MI355X_MICROARCH.md: <= 5 single-issue instructions per 32-cycle MFMA gap at one wave per SIMD; the w4
@@ -30,6 +30,9 @@
 // constant instead of a running row maximum: every P = exp2(s - bound) lies in [2^(-2 bound), 1], nothing is ever rescaled, and the tile
 // loses the 32 v_max3 of the chains, the fold / lane exchange of steps 14, 15 (bare P.V steps that keep the read-ahead) and the rescale test
 // with the branch behind it. Softmax does not depend on its reference point; the epilogues (LSE = m_run - log2(1 / l)) are the plain kernel's.
+// NM + CP (flash_attn_fwd_w4b_nm_carry_kernel, g3_self_attn_fwd_bounded_cp_bf16 only): the no-max tile loop over the CP form's key addressing, with
+// the CP form's carry-in epilogue (m_run = the bound). Every launch of a row uses the same reference point, so a key's P does not depend on how
+// the row's keys were split over launches; the parts' (normalised O, LSE) pairs are what the merge kernel and the carry epilogue consume.
 
 #ifndef G3_ATTENTION_W4B_HELPERS
 #define G3_ATTENTION_W4B_HELPERS
@@ -210,7 +213,9 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 // starts with its operands in the ring; the four pair units that covered the head reads move into region A as half units.
 #endif  // G3_ATTENTION_W4B_HELPERS
 
-#if W4B_NM
+#if W4B_NM && W4B_CP
+#define W4B_KERNEL flash_attn_fwd_w4b_nm_carry_kernel
+#elif W4B_NM
 #define W4B_KERNEL flash_attn_fwd_w4b_nm_kernel
 #elif W4B_CP
 #define W4B_KERNEL flash_attn_fwd_w4b_carry_kernel
@@ -221,7 +226,7 @@ template <bool XB>
 __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     constexpr bool CP = W4B_CP;
     constexpr bool NM = W4B_NM;
-    static_assert(!NM || (XB && !CP), "the no-max form exists for the plain XB kernel only");
+    static_assert(!NM || XB, "the no-max form exists for the XB kernels only");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
     bf16_t* sV = sK + 2 * KVB * HD;                     // [2][128][64]

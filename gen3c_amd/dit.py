@@ -443,6 +443,10 @@ class VideoExtendGeneralDIT(nn.Module):
         if cfg:
             g_, kern_, sched_ = (c.strip() for c in cfg.split(","))
             self._cp_attn.configure(head_groups=int(g_), kernel=kern_, schedule=sched_)
+        # G3_CP_LOGIT_BOUND=1 (opt-in, default off; --cp_logit_bound on the command lines): the key-sharding schedules hand the blocks' QK-norm logit bound to
+        # their attention launches too - the no-running-max kernels of g3_self_attn_fwd_bounded_cp_bf16 (ContextParallelAttention's `bounded`)
+        if __import__("os").environ.get("G3_CP_LOGIT_BOUND", "0").strip() not in ("", "0"):
+            self._cp_attn.configure(bounded=True)
         self._tables.clear()
 
     def _cp_fused_qkv(self) -> bool:
@@ -616,7 +620,8 @@ class VideoExtendGeneralDIT(nn.Module):
                 qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
                                          wq=_mx_rows(blk, "fa_qkv", slice(None)))
                 pending = self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
-                # (the bound is read by head_parallel only: its launches see all keys of their heads at once, as the single-GPU call below)
+                # (the bound is read by head_parallel, whose launches see all keys of their heads at once as the single-GPU call below, and by the other
+                # schedules when ContextParallelAttention's `bounded` switch is on)
                 o = self._cp_attn.finish(qkv[:, :D], pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)
             elif self._cp_attn is not None:
                 # K / V first, so their exchange is in flight while Q is still being projected (same fused weight, sliced;
@@ -627,7 +632,7 @@ class VideoExtendGeneralDIT(nn.Module):
                 pending = self._cp_attn.start(kv[:, :D], kv[:, D:], S, B, nH)
                 q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH, hq=hq,
                                        wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
-                o = self._cp_attn.finish(q, pending)
+                o = self._cp_attn.finish(q, pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)  # (read with `bounded` only)
             else:
                 if hq is not None:  # mxfp8 / mxfp6: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
                     qkv = _mx_gemm(blk["mx_fmt"])(hq[0], hq[1], *blk["mx"]["fa_qkv"])

@@ -539,11 +539,15 @@ def _record_attn_timer(timer, Sq: int, Skv: int, B: int, H: int, partial: bool, 
 
 
 def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int, logit_bound: float,
-                      out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False):
-    """flash_attn (plain 4-D V^T; operands, `out`, `variant` and `partial` as there) for callers that guarantee
+                      out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False, carry=None, kv_skip=None):
+    """flash_attn (operands, `out`, `variant` and `partial` as there) for callers that guarantee
     |q . k| * softmax_scale <= logit_bound for every query / key pair, e.g. q and k behind a per-head RMSNorm:
     |q . k| / sqrt(128) <= sqrt(128) * max|w_q| * max|w_k|. Where the one-wave-per-SIMD kernel (variant 11) is the choice and
-    0 < logit_bound * log2(e) <= 60 it runs without its running row maximum (g3_self_attn_fwd_bounded_bf16); every other call is flash_attn's."""
+    0 < logit_bound * log2(e) <= 60 it runs without its running row maximum (g3_self_attn_fwd_bounded_bf16); every other call is flash_attn's.
+    The key-sharded forms of flash_attn - 5-D segmented V^T, carry=, kv_skip=, partial=True with `out` - go to g3_self_attn_fwd_bounded_cp_bf16:
+    the no-max kernels where they apply (variant 11, the bound in range), else exactly flash_attn's carry call (variant 0, 4 or 11 only)."""
+    if vt.dim() == 5 or carry is not None or kv_skip is not None or (partial and out is not None):
+        return _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip, logit_bound=float(logit_bound))
     qr, qw, ldq = _rowmajor2d(q, "q")
     kr, kw, ldk = _rowmajor2d(k, "k")
     assert qr == Sq * B and kr == Skv * B and qw == H * 128 and kw == H * 128
@@ -583,7 +587,8 @@ def _carry_kernel_name(plain: str) -> str:
             "flash_attn_fwd_v3_kernel<1, 6, 8, false>": "flash_attn_fwd_v3_kernel<3, 6, 8, false>"}.get(plain, plain)
 
 
-def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip):
+def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip, logit_bound=None):
+    """logit_bound None: g3_flash_attn_fwd_carry_bf16 (flash_attn); a float: g3_self_attn_fwd_bounded_cp_bf16 (self_attn_bounded)."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
     skv_all = Skv + skip_len
     qr, qw, ldq = _rowmajor2d(q, "q")
@@ -620,15 +625,22 @@ def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
     if _KERNEL_TIMERS is not None:
         timer = HipTimer()
         timer.start()
-    _lib.check(lib.g3_flash_attn_fwd_carry_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt,
-                                                128 * ldvt, skv_all // n_seg if n_seg else 0, B * H * 128 * ldvt if n_seg else 0, skip_begin, skip_len, co, cl,
-                                                0 if partial else _dev(out, "out"), _dev(out, "o_part", torch.float32) if partial else 0,
-                                                _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128,
-                                                float(softmax_scale), int(variant), _stream()), "g3_flash_attn_fwd_carry_bf16")
+    head = (_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt,
+            128 * ldvt, skv_all // n_seg if n_seg else 0, B * H * 128 * ldvt if n_seg else 0, skip_begin, skip_len, co, cl,
+            0 if partial else _dev(out, "out"), _dev(out, "o_part", torch.float32) if partial else 0,
+            _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128, float(softmax_scale))
+    if logit_bound is None:
+        _lib.check(lib.g3_flash_attn_fwd_carry_bf16(*head, int(variant), _stream()), "g3_flash_attn_fwd_carry_bf16")
+    else:
+        _lib.check(lib.g3_self_attn_fwd_bounded_cp_bf16(*head, logit_bound, int(variant), _stream()), "g3_self_attn_fwd_bounded_cp_bf16")
     if timer is not None:
         timer.stop()
-        _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, carry=carry is not None, kv_skip=skip_len,
-                                                      kernel=_carry_kernel_name(lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())), timer))
+        if logit_bound is None:
+            kernel = _carry_kernel_name(lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())
+        else:  # (the C entry point turns a skip at either end into a base offset: no CP form then)
+            cp_form = carry is not None or (skip_len > 0 and 0 < skip_begin < Skv)
+            kernel = lib.g3_self_attn_cp_kernel_name(Sq, Skv, B, H, logit_bound, int(variant), int(bool(n_seg)), int(cp_form)).decode()
+        _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, carry=carry is not None, kv_skip=skip_len, kernel=kernel), timer))
     return (out, lse) if partial else out
 
 

@@ -198,6 +198,9 @@ def _default_backend():
         gather_heads=lambda x, out, H, head0: ops.cp_gather_heads(x, out, H, head0),
         attention_bounded=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out, variant=0: ops.self_attn_bounded(
             q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant),
+        # the key-sharded forms with a logit bound (g3_self_attn_fwd_bounded_cp_bf16): what "attention", "attention_partial" and "attention_carry" take
+        attention_bounded_cp=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out=None, carry=None, kv_skip=None, partial=False, variant=0: ops.self_attn_bounded(
+            q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
         timer=ops.HipTimer,
     )
 
@@ -237,6 +240,11 @@ class ContextParallelAttention:
     exchange and the last group's return hide behind nothing. Needs H % world == 0 and a backend with "scatter_heads", "gather_heads" and
     "attention_bounded"; otherwise it runs as "local_first" (and `effective` says so). Runs at world 1 too (a self-exchange).
 
+    bounded (opt-in, default off): with a caller's `logit_bound` > 0 the three key-sharding schedules run every attention launch through the backend's
+    "attention_bounded_cp" - the no-running-max forms of the one-wave-per-SIMD kernel, g3_self_attn_fwd_bounded_cp_bf16 - where the layer's kernel is
+    that kernel (variant 11). The bound is the same constant reference point in every launch of a row, so parts merge and carry exactly as the
+    max form's do. `effective_bounded` says whether the last finish() did; off, or where it does not apply, the launches are exactly the ones above.
+
     kernel: "auto" (the one-wave-per-SIMD kernel when the groups' workgroups together fill the 256 CUs evenly, else the 8-wave kernel), "w4b",
     "wave8" - passed PER CALL through the C ABI; no process-wide option is touched (launches go out on two streams).
 
@@ -245,7 +253,8 @@ class ContextParallelAttention:
     stream stalled for that exchange - read by bench.py.
     """
 
-    def __init__(self, cp_group, head_groups: int = 4, backend: Optional[dict] = None, schedule: str = "gather_first", kernel: str = "auto"):
+    def __init__(self, cp_group, head_groups: int = 4, backend: Optional[dict] = None, schedule: str = "gather_first", kernel: str = "auto",
+                 bounded: bool = False):
         assert schedule in CP_SCHEDULES and kernel in ATTN_KERNELS
         self.group = cp_group
         self.world = dist.get_world_size(cp_group)
@@ -254,11 +263,13 @@ class ContextParallelAttention:
         self.backend = backend
         self.schedule = schedule
         self.kernel = kernel
+        self.bounded = bool(bounded)
         self.stats = None
         self.effective = None  # set by finish(): dict(schedule, kernel, head_groups) of the configuration that actually ran
+        self.effective_bounded = False  # set by finish(): the key-sharding schedules' launches went through "attention_bounded_cp" (see `bounded`)
         self.bytes_gathered = 0  # received from the other ranks since construction / the last reset (bench.py's "cp" object)
 
-    def configure(self, head_groups: Optional[int] = None, schedule: Optional[str] = None, kernel: Optional[str] = None):
+    def configure(self, head_groups: Optional[int] = None, schedule: Optional[str] = None, kernel: Optional[str] = None, bounded: Optional[bool] = None):
         if head_groups is not None:
             self.head_groups = int(head_groups)
         if schedule is not None:
@@ -267,6 +278,8 @@ class ContextParallelAttention:
         if kernel is not None:
             assert kernel in ATTN_KERNELS
             self.kernel = kernel
+        if bounded is not None:
+            self.bounded = bool(bounded)
         return self
 
     def start(self, k: torch.Tensor, v: torch.Tensor, S_local: int, B: int, H: int):
@@ -404,8 +417,12 @@ class ContextParallelAttention:
         return out
 
     def finish(self, q: torch.Tensor, pending: dict, logit_bound: float = 0.0) -> torch.Tensor:
-        """logit_bound > 0 (a caller's bound on |q . k| * softmax_scale, see ops.self_attn_bounded) is used by "head_parallel" only: the other
-        schedules shard a row's keys over launches, which the no-running-max kernel does not take."""
+        """logit_bound > 0 (a caller's bound on |q . k| * softmax_scale, see ops.self_attn_bounded) is always used by "head_parallel". The other
+        schedules shard a row's keys over launches; they use it when `bounded` is set, the layer's kernel is the one-wave-per-SIMD kernel (variant 11;
+        a stub backend on CPU has no kernel choice) and the backend offers "attention_bounded_cp": then EVERY attention launch - gather_first's one,
+        local_first's own-shard partial and both remote partials ahead of the unchanged merge, local_carry's own-shard partial and its carry launch
+        with the skip - goes through that callable, and `effective_bounded` is True. Otherwise the launches are the unbounded ones, unchanged."""
+        self.effective_bounded = False
         if pending.get("head_parallel"):
             return self._finish_head_parallel(q, pending, logit_bound)
         be, W, Hg, B, S_local = pending["be"], pending["W"], pending["Hg"], pending["B"], pending["S_local"]
@@ -420,6 +437,16 @@ class ContextParallelAttention:
         works = pending["works"]
         variant = self._variant(S_local, S_all, B, pending["H"]) if q.is_cuda else 0
         split = pending["segmented"] and self.world > 1
+        use_bound = self.bounded and logit_bound > 0 and "attention_bounded_cp" in be and (variant == 11 or not q.is_cuda)
+        self.effective_bounded = bool(use_bound)
+        if use_bound:  # the same launches with the bound: one callable stands in for the three unbounded ones
+            bcp = be["attention_bounded_cp"]
+            attention = lambda q_, k_, vt_, Sq, Skv, B_, H_, out_, variant=0: bcp(q_, k_, vt_, Sq, Skv, B_, H_, logit_bound, out=out_, variant=variant)
+            attention_partial = lambda q_, k_, vt_, Sq, Skv, B_, H_, variant=0: bcp(q_, k_, vt_, Sq, Skv, B_, H_, logit_bound, partial=True, variant=variant)
+            attention_carry = lambda q_, k_, vt_, Sq, Skv, B_, H_, out=None, carry=None, kv_skip=None, partial=False, variant=0: bcp(
+                q_, k_, vt_, Sq, Skv, B_, H_, logit_bound, out=out, carry=carry, kv_skip=kv_skip, partial=partial, variant=variant)
+        else:
+            attention, attention_partial, attention_carry = be["attention"], be.get("attention_partial"), be.get("attention_carry")
         local_carry = self.schedule == "local_carry" and split and "attention_carry" in be
         # (a "head_parallel" request that start() could not honour - H % world != 0, a backend without the exchange callables - runs as local_first)
         local_first = not local_carry and self.schedule in ("local_first", "local_carry", "head_parallel") and split and "attention_partial" in be
@@ -452,7 +479,7 @@ class ContextParallelAttention:
                     with ctx:
                         if two_streams and st is side:
                             st.wait_event(q_ready)
-                        local_parts[g] = be["attention_carry"](q[:, g * W:(g + 1) * W], ks, vs.reshape(1, B, Hg, 128, -1), S_local, S_local, B, Hg,
+                        local_parts[g] = attention_carry(q[:, g * W:(g + 1) * W], ks, vs.reshape(1, B, Hg, 128, -1), S_local, S_local, B, Hg,
                                                                out=o32[:, g * W:(g + 1) * W], partial=True, variant=variant)
             elif local_first:
                 # phase 1: every group over this rank's own shard - the packed K columns and the local V^T that were SENT (w[4], w[5]); no wait
@@ -461,7 +488,7 @@ class ContextParallelAttention:
                     with ctx:
                         if two_streams and st is side:
                             st.wait_event(q_ready)  # q (and `out`) were produced / allocated on the main stream
-                        local_parts[g] = be["attention_partial"](q[:, g * W:(g + 1) * W], ks, vs.reshape(1, B, Hg, 128, -1), S_local, S_local, B, Hg, variant=variant)
+                        local_parts[g] = attention_partial(q[:, g * W:(g + 1) * W], ks, vs.reshape(1, B, Hg, 128, -1), S_local, S_local, B, Hg, variant=variant)
             for g, (wk, wv, kf, vf, _ks, _vs) in enumerate(works):
                 st, ctx = on_stream(g)
                 with ctx:
@@ -481,7 +508,7 @@ class ContextParallelAttention:
                             kk, vv, skip = kf[:r * rows], vseg[:r], None
                         else:
                             kk, vv, skip = kf, vseg, (r * S_local, S_local)
-                        be["attention_carry"](qg, kk, vv, S_local, S_rem, B, Hg, out=og, carry=local_parts[g], kv_skip=skip, variant=variant)
+                        attention_carry(qg, kk, vv, S_local, S_rem, B, Hg, out=og, carry=local_parts[g], kv_skip=skip, variant=variant)
                     elif local_first:
                         # phase 2: the other ranks' keys = the row blocks / V^T segments before and after this rank's in the gathered buffers
                         parts = [local_parts[g]]
@@ -489,11 +516,11 @@ class ContextParallelAttention:
                         rows = pending["rows"]
                         for (r0, r1) in ((0, self.rank), (self.rank + 1, self.world)):
                             if r1 > r0:
-                                parts.append(be["attention_partial"](qg, kf[r0 * rows:r1 * rows], vseg[r0:r1], S_local, (r1 - r0) * S_local, B, Hg, variant=variant))
+                                parts.append(attention_partial(qg, kf[r0 * rows:r1 * rows], vseg[r0:r1], S_local, (r1 - r0) * S_local, B, Hg, variant=variant))
                         be["merge"](parts, S_local, B, Hg, og)
                     else:
                         vt = vf.view(self.world, B, Hg, 128, -1) if pending["segmented"] else be["transpose_v"](vf, S_all, B, Hg)
-                        be["attention"](qg, kf, vt, S_local, S_all, B, Hg, og, variant=variant)
+                        attention(qg, kf, vt, S_local, S_all, B, Hg, og, variant=variant)
         finally:
             if two_streams:
                 main.wait_stream(side)  # everything enqueued on the main stream from here on (out-projection, buffer reuse) follows both streams

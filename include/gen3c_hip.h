@@ -177,7 +177,7 @@ const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int vari
 
 /* g3_flash_attn_fwd_ex_bf16 for callers that can BOUND the logits: logit_bound >= |q . k| * softmax_scale (natural units) for every query / key
  * pair of the call - e.g. per-head RMSNorm of q and k (RoPE keeps the norm): |q . k| / sqrt(128) <= sqrt(128) * max|w_q| * max|w_k|. Where the
- * resolved variant is 11, V^T is not segmented and 0 < logit_bound * log2(e) <= 60, the one-wave-per-SIMD kernel then runs without its running
+ * resolved variant is 11, V^T is not segmented (with segments: g3_self_attn_fwd_bounded_cp_bf16) and 0 < logit_bound * log2(e) <= 60, the one-wave-per-SIMD kernel then runs without its running
  * row maximum (the bound is the softmax's constant reference point; the same function, fewer instructions per tile). In every other case - bound 0,
  * bound above the limit, another kernel - the call IS g3_flash_attn_fwd_ex_bf16. An understated bound is a caller error (rows may overflow).
  * g3_self_attn_kernel_name reports the kernel such a call launches with PLAIN V^T (vt_seg_len == 0) and operands the 32-bit-offset kernels can
@@ -208,6 +208,23 @@ int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, 
                                  int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o, const float* carry_lse,
                                  void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B,
                                  int H, int head_dim, float softmax_scale, int variant, void* stream);
+/* g3_flash_attn_fwd_carry_bf16 for callers that can BOUND the logits (logit_bound as for g3_self_attn_fwd_bounded_bf16): the no-running-max kernels
+ * under key sharding. A constant reference point suits a row whose keys are spread over launches: every launch uses the same one, so a key's
+ * P = exp2(s - bound) does not depend on the split, and a launch's (normalised o, lse = bound + log2 l) is what the merge kernel and the carry-in
+ * epilogue consume - bounded and max-form parts of the same rows mix freely. Where the resolved variant is 11, 0 < logit_bound * log2(e) <= 60
+ * and the 32-bit-offset kernels can address the operands:
+ *   no carry-in state and no skipped range inside the keys -> flash_attn_fwd_w4b_nm_kernel<true>, with plain or segmented V^T;
+ *   a carry-in state or a skipped range                    -> flash_attn_fwd_w4b_nm_carry_kernel<true>.
+ * In every other case - bound 0, negative or above the limit, variant 4 - the call IS g3_flash_attn_fwd_carry_bf16: the same output bit for bit,
+ * the same refusals (G3_ERR_ARG, nothing launched). g3_self_attn_fwd_bounded_bf16 keeps its own contract: a segmented call through it runs the max form.
+ * g3_self_attn_cp_kernel_name: the kernel such a call launches, from shapes only (Skv = attended keys; cp_form != 0: a carry-in state, or a skip
+ * with 0 < kv_skip_begin < S_kv and kv_skip_len > 0; segmented is informational - both V^T forms run the same kernels). */
+int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                     int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
+                                     int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o, const float* carry_lse,
+                                     void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B,
+                                     int H, int head_dim, float softmax_scale, float logit_bound, int variant, void* stream);
+const char* g3_self_attn_cp_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant, int segmented, int cp_form);
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);

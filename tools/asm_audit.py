@@ -36,6 +36,10 @@ def _back_branch(v, hdr):
     return max([i for i in range(hdr, len(v)) if re.search(r"\bs_c?branch\w*\s+" + re.escape(m.group(1)) + r"\b", v[i])] + [hdr])
 
 
+# the one-wave-per-SIMD instantiations attention.hip launches: each must be in the assembly (and is then audited like every flash_attn_fwd kernel found there)
+W4B_KERNELS = ("w4b_kernel<Lb0E>", "w4b_kernel<Lb1E>", "w4b_carry_kernel<Lb1E>", "w4b_nm_kernel<Lb1E>", "w4b_nm_carry_kernel<Lb1E>")  # (names as audit() forms them)
+
+
 def audit(asm_text: str):
     funcs, cur, name_full = {}, None, {}
     for ln in asm_text.split("\n"):
@@ -48,7 +52,7 @@ def audit(asm_text: str):
             funcs[cur].append(ln)
             if ln.startswith(".Lfunc_end"):
                 cur = None
-    findings = []
+    findings = [f"{k}: not found in the assembly of attention.hip" for k in W4B_KERNELS if k not in funcs]
     for name, v in funcs.items():
         n_asm_reads = 0
         pending = {}

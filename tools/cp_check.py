@@ -55,16 +55,21 @@ def main():
     # fp32 partials merged (one extra rounding pattern: not bitwise, same tolerance)
     # G3_CP_CHECK_SCHEDULES="local_carry" (tests/test_cp_carry_gpu.py) or "head_parallel" (tests/test_cp_exchange_gpu.py; needs 4 % ranks == 0): other
     # schedules, same bar; the schedule that actually ran is printed
+    # G3_CP_CHECK_KERNEL=w4b forces the one-wave-per-SIMD kernel (S_all = 384 x ranks is below the 2048 keys at which "auto" picks it) and
+    # G3_CP_CHECK_BOUNDED=1 turns the logit-bound switch on (tests/test_cp_bounded_gpu.py): the no-running-max kernels under key sharding, same bar;
+    # whether they actually ran is printed, and a fallback fails the check
+    kern = os.environ.get("G3_CP_CHECK_KERNEL", "auto")
+    bounded = os.environ.get("G3_CP_CHECK_BOUNDED", "0") not in ("", "0")
     for sched in os.environ.get("G3_CP_CHECK_SCHEDULES", "gather_first,local_first").split(","):
-        net._cp_attn.configure(head_groups=2, schedule=sched)
+        net._cp_attn.configure(head_groups=2, schedule=sched, kernel=kern, bounded=bounded)
         part = den.denoise_step(split_inputs_cp(xt, 2, net.cp_group), 5, c, u, 1.0, 0.001, 1)
         torch.cuda.synchronize()
         rel = float((part.float() - ref).norm() / ref.norm())
         mx = float((part.float() - ref).abs().max())
         print(f"[cp_check] rank {rank}/{world}: CP ({sched}) vs non-CP denoise step rel_l2={rel:.3e} max_abs={mx:.3e} "
-              f"effective={net._cp_attn.effective['schedule']}", flush=True)
-        good = good and rel < 5e-3 and np.isfinite(rel)
-    net._cp_attn.configure(head_groups=4, schedule="gather_first")
+              f"effective={net._cp_attn.effective['schedule']}" + (f" effective_bounded={net._cp_attn.effective_bounded}" if bounded else ""), flush=True)
+        good = good and rel < 5e-3 and np.isfinite(rel) and (net._cp_attn.effective_bounded or not bounded)
+    net._cp_attn.configure(head_groups=4, schedule="gather_first", kernel="auto", bounded=False)
 
     # ---- the chunk's other stages, sharded over the same group: render item pairs and tokenizer encodes with the real
     # kernels must be bit-identical to the replicated computation on every rank

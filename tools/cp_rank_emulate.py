@@ -11,6 +11,12 @@ What it cannot: the xGMI exchange itself - the model printed at the end adds it 
 Schedules (the third field of a config): gather_first, local_first, local_carry (own-shard partial, then ONE carry launch per head group over every remote
 key - no merge pass), head_parallel (heads sharded by two all-to-alls around the ordinary full-length attention; the stand-in's all-to-all is a device
 copy of the same size). The exchange model below replays each of them.
+
+  python tools/cp_rank_emulate.py --ab_bounded 3 [--cps 1,2,4,8] [--steps 2] [--configs "4,auto,local_first;4,auto,gather_first;4,auto,local_carry"] [--out ...]
+The logit-bound switch of the key-sharding schedules (ContextParallelAttention's `bounded`) off and on, ALTERNATING in one process after both arms are warm:
+per configuration `--ab_bounded` rounds of (off, on), each `--steps` untimed-by-events steps; then one step per arm with the kernel timers on for the per-class
+table. The off arm is the behaviour without the switch. Then, launch by launch on one stream, the partial / carry / kvseg launches at each cp's rank shapes
+(Sq = S_local, 8 heads, B = 2), max form and bounded form alternating.
 """
 import argparse
 import json
@@ -182,8 +188,173 @@ def run_cp(cp, rank, configs, steps, blocks, dev, net):
     return results
 
 
+def _steps_ms(den, xt, cond, uncond, steps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        xt = den.denoise_step(xt, 1 + i, cond, uncond, 1.0, 0.001, 1)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(xt.float()).all())
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def run_ab_bounded(cp, rank, configs, steps, rounds, blocks, dev, net, base_rest):
+    """Switch off / on alternating (see the module docstring) -> one dict per configuration."""
+    T, Hl, Wl = 16, 88, 160
+    rs = np.random.RandomState(1)
+    normal = lambda shape, std: torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32)).to(torch.bfloat16).to(dev)
+    den = Gen3CDenoiser(net, state_shape=(16, T, Hl, Wl))
+    den.scheduler.set_timesteps(35)
+    xt_full = normal((1, 16, T, Hl, Wl), den.scheduler.init_noise_sigma)
+    gt, pose, ctx = normal((1, 16, T, Hl, Wl), 0.5), normal((1, 64, T, Hl, Wl), 0.5), normal((1, 512, 1024), 0.2)
+    ctx[:, 64:] = 0
+    pad = torch.zeros(1, 1, 8 * Hl, 8 * Wl, device=dev, dtype=torch.bfloat16)
+    fps = torch.tensor([24.0], device=dev)
+
+    def make_cond(p):
+        c = VideoExtendCondition(crossattn_emb=ctx, crossattn_mask=None, padding_mask=pad, fps=fps, video_cond_bool=True, condition_video_pose=p)
+        return add_condition_video_indicator_and_video_input_mask(gt, c, 1)
+
+    cond, uncond = make_cond(pose), make_cond(torch.zeros_like(pose))
+    results = []
+    with FakeRank(cp, rank, dev):
+        net.enable_context_parallel("fake-cp-group")
+        from gen3c_amd.parallel import split_inputs_cp
+        xt0 = split_inputs_cp(xt_full, 2, net.cp_group)
+        for (G, kern, sched) in configs:
+            arms = {False: [], True: []}
+            eff = {}
+            for on in (False, True):  # warm-up of both arms
+                net._cp_attn.configure(head_groups=G, kernel=kern, schedule=sched, bounded=on)
+                den.denoise_step(xt0, 0, cond, uncond, 1.0, 0.001, 1)
+                eff[on] = (dict(net._cp_attn.effective), net._cp_attn.effective_bounded)
+            for _ in range(rounds):
+                for on in (False, True):
+                    net._cp_attn.configure(bounded=on)
+                    arms[on].append(_steps_ms(den, xt0, cond, uncond, steps))
+            tables = {}
+            for on in (False, True):  # one step per arm with the kernel timers on: the per-class table (event pairs around every launch: not part of the timing above)
+                net._cp_attn.configure(bounded=on)
+                ops.enable_kernel_timers(True)
+                den.denoise_step(xt0, 1, cond, uncond, 1.0, 0.001, 1)
+                torch.cuda.synchronize()
+                cls = {}
+                for name, meta, tm in ops.collected_kernel_timers():
+                    if name == "gemm_nt":
+                        key = ("gemm", meta["M"], meta["N"], meta["K"], "")
+                    elif name == "flash_attn_fwd":
+                        key = ("attn", meta["Sq"], meta["Skv"], meta["H"], meta.get("kernel", "?") + (" partial" if meta.get("partial") else "") + (" carry" if meta.get("carry") else ""))
+                    else:
+                        continue
+                    c = cls.setdefault(key, [0, 0.0])
+                    c[0] += 1
+                    c[1] += tm.elapsed_ms()
+                ops.enable_kernel_timers(False)
+                tables[on] = cls
+            net._cp_attn.configure(bounded=False)
+            res = dict(cp=cp, rank=rank, config=dict(head_groups=G, kernel=kern, schedule=sched), steps=steps, rounds=rounds)
+            for on in (False, True):
+                a = arms[on]
+                gemm = sum(v[1] for k_, v in tables[on].items() if k_[0] == "gemm")
+                cross = sum(v[1] for k_, v in tables[on].items() if k_[0] == "attn" and k_[2] <= 2048)
+                mean = sum(a) / len(a)
+                res["on" if on else "off"] = dict(
+                    effective=eff[on][0], effective_bounded=eff[on][1], ms_per_step_rounds=[round(x, 2) for x in a], ms_per_step=round(mean, 2),
+                    spread_pct=round((max(a) - min(a)) / mean * 100, 2),
+                    self_attention_and_cp_ms_per_layer=None if base_rest is None else round((mean - gemm - cross - base_rest / cp) / blocks, 3),
+                    self_attention_launches=[dict(Sq=k_[1], Skv=k_[2], H=k_[3], kernel=k_[4], launches=v[0], ms_sum=round(v[1], 3))
+                                             for k_, v in sorted(tables[on].items()) if k_[0] == "attn" and k_[2] > 2048])
+            res["on_over_off"] = round(res["on"]["ms_per_step"] / res["off"]["ms_per_step"], 4)
+            results.append(res)
+            print(f"cp={cp} rank={rank} {G},{kern},{sched}: off {res['off']['ms_per_step_rounds']} on {res['on']['ms_per_step_rounds']} ms/step -> on / off {res['on_over_off']}"
+                  f" (bounded ran: {eff[True][1]})", flush=True)
+    net.disable_context_parallel()
+    return results
+
+
+def run_launches(cp, rank, dev, rounds, iters):
+    """The self-attention launches of one head group at cp's rank shapes (Sq = S_local, 8 heads, B = 2), alone on one stream: max form and bounded form
+    alternating, `rounds` x `iters` launches each. q, k RMS-normalised per head (unit weights), as behind the DiT's QK-norm."""
+    import math
+    S_all, B, H = 56320, 2, 8
+    Sl = S_all // cp
+    g = torch.Generator(device=dev).manual_seed(cp)
+    rms = lambda x: (x.view(x.shape[0], H, 128) * torch.rsqrt(x.view(x.shape[0], H, 128).pow(2).mean(-1, keepdim=True))).reshape(x.shape[0], H * 128)
+    q = rms(torch.randn(Sl * B, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    k = rms(torch.randn(S_all * B, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    vseg = torch.randn(cp, B, H, 128, Sl, device=dev, generator=g).to(torch.bfloat16)
+    bound = 128 / math.sqrt(128) * 1.03
+    own_k, own_v = k[rank * Sl * B:(rank + 1) * Sl * B], vseg[rank:rank + 1]
+    own = ops.flash_attn(q, own_k, own_v, Sl, Sl, B, H, partial=True, variant=11)
+    skip = (rank * Sl, Sl) if 0 < rank < cp - 1 else None
+    out = torch.empty_like(q)
+    forms = {
+        "partial (own shard, Skv = S_local)": lambda at: at(q, own_k, own_v, Sl, Sl, B, H, partial=True),
+        "carry (remote keys, own block skipped)": lambda at: at(q, k, vseg, Sl, S_all - Sl, B, H, out=out, carry=own, kv_skip=skip),
+        "kvseg (gather_first, all keys)": lambda at: at(q, k, vseg, Sl, S_all, B, H, out=out),
+    }
+    arms = {"max": lambda *a, **kw: ops.flash_attn(*a, variant=11, **kw), "bounded": lambda *a, **kw: ops.self_attn_bounded(*a, bound, variant=11, **kw)}
+    rows = []
+    for what, call in forms.items():
+        ms = {"max": [], "bounded": []}
+        for arm in arms:
+            call(arms[arm])  # warm-up
+        for _ in range(rounds):
+            for arm in arms:
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _i in range(iters):
+                    call(arms[arm])
+                e1.record()
+                torch.cuda.synchronize()
+                ms[arm].append(e0.elapsed_time(e1) / iters)
+        mean = {a: sum(v) / len(v) for a, v in ms.items()}
+        rows.append(dict(cp=cp, rank=rank, launch=what, Sq=Sl, max_ms=[round(x, 4) for x in ms["max"]], bounded_ms=[round(x, 4) for x in ms["bounded"]],
+                         bounded_over_max=round(mean["bounded"] / mean["max"], 4),
+                         spread_pct={a: round((max(v) - min(v)) / mean[a] * 100, 2) for a, v in ms.items()}))
+        print(f"cp={cp} launch {what}: max {rows[-1]['max_ms']} bounded {rows[-1]['bounded_ms']} ms -> bounded / max {rows[-1]['bounded_over_max']}", flush=True)
+    return rows
+
+
+def main_ab(args, dev, configs, net):
+    configs = [c for c in configs if c[2] in ("gather_first", "local_first", "local_carry")]
+    cps = [int(c) for c in args.cps.split(",")]
+    base_rest = None
+    if 1 in cps:
+        base = run_cp(1, 0, configs, args.steps, args.blocks, dev, net)[0]
+        base_rest = base["ms_per_step"] - sum(c["ms_per_step"] for c in base["classes"] if c["kind"] in ("attn", "gemm"))
+    runs, launches = [], []
+    for cp in cps:
+        if cp > 1:
+            runs += run_ab_bounded(cp, cp // 2 if args.rank < 0 else args.rank, configs, args.steps, args.ab_bounded, args.blocks, dev, net, base_rest)
+    for cp in cps:
+        if cp > 1 and args.launch_iters > 0:
+            launches += run_launches(cp, cp // 2 if args.rank < 0 else args.rank, dev, args.ab_bounded, args.launch_iters)
+    lines = [f"{'cp':>3} {'config':<22} {'off ms/step (rounds)':<34} {'on ms/step (rounds)':<34} {'on/off':>7} {'spread off/on %':>16} {'self-attn + CP ms/layer off -> on':>34}"]
+    for r in runs:
+        c = r["config"]
+        lines.append(f"{r['cp']:>3} {'%d,%s,%s' % (c['head_groups'], c['kernel'], c['schedule']):<22} {str(r['off']['ms_per_step_rounds']):<34} {str(r['on']['ms_per_step_rounds']):<34} "
+                     f"{r['on_over_off']:>7.4f} {'%.2f / %.2f' % (r['off']['spread_pct'], r['on']['spread_pct']):>16} "
+                     f"{'%s -> %s' % (r['off']['self_attention_and_cp_ms_per_layer'], r['on']['self_attention_and_cp_ms_per_layer']):>34}"
+                     + ("" if r["on"]["effective_bounded"] else "   (the bound was NOT used)"))
+    lines.append("")
+    lines.append(f"{'cp':>3} {'launch (8 heads, B = 2, one stream)':<42} {'Sq':>6} {'max form ms (rounds)':<30} {'bounded ms (rounds)':<30} {'bounded/max':>11} {'spread max/bounded %':>21}")
+    for r in launches:
+        lines.append(f"{r['cp']:>3} {r['launch']:<42} {r['Sq']:>6} {str(r['max_ms']):<30} {str(r['bounded_ms']):<30} {r['bounded_over_max']:>11.4f} "
+                     f"{'%.2f / %.2f' % (r['spread_pct']['max'], r['spread_pct']['bounded']):>21}")
+    text = "\n".join(lines)
+    print(text)
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(dict(runs=runs, launches=launches, summary_text=text), indent=1))
+    out.with_suffix(".txt").write_text(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ab_bounded", type=int, default=0, help="> 0: the logit-bound switch off / on alternating, this many rounds (see the module docstring)")
+    ap.add_argument("--launch_iters", type=int, default=5, help="with --ab_bounded: launches per round of the launch-by-launch table (0: skip it)")
     ap.add_argument("--cps", default="1,2,4,8")
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=28)
@@ -198,6 +369,8 @@ def main():
     net = VideoExtendGeneralDIT(in_channels=16 + 16 * 4 + 1, rope_t_extrapolation_ratio=2.0, num_blocks=args.blocks, device=dev, init_weights=False)
     net.initialize_weights(randomize_adaln=True, seed=1234)
     net.cross_attention_skip_zero_context = False  # the dense workload bench.py times (the record profiles/r6_cp_rank_shapes.* was taken with the product default, ~17 / cp ms less per step)
+    if args.ab_bounded > 0:
+        return main_ab(args, dev, configs, net)
     allres = []
     for cp in [int(c) for c in args.cps.split(",")]:
         rank = (cp // 2 if args.rank < 0 else args.rank) if cp > 1 else 0

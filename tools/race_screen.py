@@ -2,7 +2,8 @@
 product library against the same sources built with -DG3_AB_JITTER=<n> (pseudo-random waves sleep n*64 cycles at tile / phase
 boundaries) and demands BITWISE equal outputs.
   build (here, before gpurun):  python tools/race_screen.py --build [n]
-  run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]"""
+  run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]
+                                                            [--bounded-cp-only: the no-max key-sharded attention section alone]"""
 import ctypes as C
 import math
 import os
@@ -35,7 +36,8 @@ dev = torch.device("cuda:0")
 st = torch.cuda.current_stream().cuda_stream
 g = torch.Generator(device=dev).manual_seed(3)
 bad = 0
-ONLY_MX = "--mxfp8-producers-only" in sys.argv  # run only the last section (the launches that emit MXFP8)
+ONLY_BCP = "--bounded-cp-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded_cp_bf16
+ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP  # run only the last section (the launches that emit MXFP8)
 
 
 def both(fn):
@@ -125,6 +127,39 @@ for (Sl, nseg, rank, H) in [] if ONLY_MX else [(7040, 8, 3, 4), (256, 3, 1, 2), 
                 return torch.cat([o32.flatten(), lse.flatten()]) if partial else o
             a, b = both(run)
             report(f"carry-in form S_local={Sl} segs={nseg} rank={rank} H={H} variant={variant} {'fp32 partial' if partial else 'bf16'}", a, b)
+    del q, k, v, vt
+
+# ---- no-max forms under key sharding (g3_self_attn_fwd_bounded_cp_bf16): flash_attn_fwd_w4b_nm_kernel over segmented V^T (every key, no carry) and
+# flash_attn_fwd_w4b_nm_carry_kernel (an interior rank's remote keys, own block skipped, the own block's bounded partial carried in); q, k RMS-normalised
+# per head so that the bound holds; bf16 and fp32-partial outputs
+for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)] if (ONLY_BCP or not ONLY_MX) else []:
+    Skv = Sl * nseg
+    rms = lambda x: (x.view(x.shape[0], H, 128) * torch.rsqrt(x.view(x.shape[0], H, 128).pow(2).mean(-1, keepdim=True))).reshape(x.shape[0], H * 128)
+    q = rms(torch.randn(Sl, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    k = rms(torch.randn(Skv, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    vt = torch.stack([ops.transpose_v(v[i * Sl:(i + 1) * Sl], Sl, 1, H) for i in range(nseg)]).contiguous()
+    ld = vt.shape[-1]
+    bound = 128 / math.sqrt(128) * 1.03
+    own_o, own_l = ops.self_attn_bounded(q, k[rank * Sl:(rank + 1) * Sl].contiguous(), vt[rank:rank + 1].contiguous(), Sl, Sl, 1, H, bound, partial=True, variant=11)
+    torch.cuda.synchronize()
+    for cp_form in (False, True):
+        name = base.g3_self_attn_cp_kernel_name(Sl, Skv - Sl if cp_form else Skv, 1, H, bound, 11, 1, int(cp_form)).decode()
+        assert name == ("flash_attn_fwd_w4b_nm_carry_kernel<true>" if cp_form else "flash_attn_fwd_w4b_nm_kernel<true>"), name
+        for partial in (False, True):
+            def run(lib):
+                o = torch.empty_like(q)
+                o32 = torch.empty(Sl, H * 128, device=dev, dtype=torch.float32)
+                lse = torch.empty(1, H, Sl, device=dev, dtype=torch.float32)
+                rc = lib.g3_self_attn_fwd_bounded_cp_bf16(q.data_ptr(), H * 128, H * 128, 128, k.data_ptr(), H * 128, H * 128, 128, vt.data_ptr(), ld, H * 128 * ld, 128 * ld,
+                                                          Sl, H * 128 * ld, rank * Sl if cp_form else 0, Sl if cp_form else 0, own_o.data_ptr() if cp_form else None,
+                                                          own_l.data_ptr() if cp_form else None, None if partial else o.data_ptr(),
+                                                          o32.data_ptr() if partial else None, lse.data_ptr() if partial else None, H * 128, H * 128, 128,
+                                                          Sl, Skv - Sl if cp_form else Skv, 1, H, 128, 1.0 / math.sqrt(128), bound, 11, st)
+                assert rc == 0, lib.g3_last_error()
+                return torch.cat([o32.flatten(), lse.flatten()]) if partial else o
+            a, b = both(run)
+            report(f"bounded {'carry-in + skip' if cp_form else 'segmented V^T'} form ({name}) S_local={Sl} segs={nseg} rank={rank} H={H} {'fp32 partial' if partial else 'bf16'}", a, b)
     del q, k, v, vt
 
 # ---- GEMM: every K-loop structure x epilogues x ragged shapes
@@ -221,7 +256,7 @@ if "--no-tokenizer" not in sys.argv and not ONLY_MX:
 # ---- the producers that emit MXFP8 from their registers (mxfp8_producers = "fused"): the GEMM with MXFP8 output (its K loop carries the jitter; the epilogue
 # transposes through each wave's own LDS slice and quantises across lane quads) and the two LayerNorm forms, plain and with the position embedding
 LN_WAVE_START = int(os.environ.get("G3_LN_WAVE_ROWS", "0"))  # what both libraries start with (csrc/api.hip); restored after each case
-for (M, N, K, epi) in [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
+for (M, N, K, epi) in [] if ONLY_BCP else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
     aq, as_ = ops.quant_mxfp8(torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16))
     wq, ws = ops.quant_mxfp8((torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16))
 
@@ -235,7 +270,7 @@ for (M, N, K, epi) in [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 102
     a, b = both(run)
     report(f"gemm_mxfp8 with MXFP8 output {M}x{N}x{K} epi{epi}", a, b)
     del aq, as_, wq, ws
-for (T_, Hp, Wp, B_, D_, wave) in [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
+for (T_, Hp, Wp, B_, D_, wave) in [] if ONLY_BCP else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
     rows = T_ * Hp * Wp * B_
     x_ = torch.randn(rows, D_, device=dev, generator=g).to(torch.bfloat16)
     pe = (0.3 * torch.randn(T_ * Hp * Wp, D_, device=dev, generator=g)).to(torch.bfloat16)
