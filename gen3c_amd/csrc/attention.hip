@@ -1025,8 +1025,50 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 }  // namespace
 
-// requested: the per-call kernel choice of the *_ex entry points (0 = the process-wide "attn_variant" option, whose 0 = automatic)
-static int attn_resolve_variant(int Sq, int Skv, int B, int H, int requested = 0) {
+/* ---- host side: every public entry point fills ONE call record (AttnCall); attn_plan turns it into a refusal or into the kernel's parameters, its
+ * row of the ONE kernel table and the grid; attn_launch launches that. g3_attn_plan_bf16 and the *_kernel_name functions ask the same code. ---------- */
+#include "gen3c_hip.h"  // enum g3_attn_entry
+
+struct AttnOperand { const void* ptr = nullptr; int64_t row = 0, batch = 0, head = 0; };  // element strides
+struct AttnCall {
+    int entry = G3_ATTN_ENTRY_FWD;  // the public entry point called: it decides which checks run and whose name a refusal carries
+    AttnOperand q, k, vt, o;        // o.ptr: the bf16 result; o's strides also address o_partial and carry_o
+    int vt_seg_len = 0; int64_t vt_seg_stride = 0;
+    float* o_partial = nullptr; float* lse = nullptr;
+    int Sq = 0, Skv = 0, B = 0, H = 0, head_dim = 0;
+    float softmax_scale = 0.f;
+    int variant = 0;  // the per-call kernel choice (0 = the process-wide "attn_variant" option, whose 0 = automatic)
+    int kv_dense = 0; const void* q_norm_w = nullptr; float q_norm_eps = 0.f;
+    const float* carry_o = nullptr; const float* carry_lse = nullptr; int kv_skip_begin = 0, kv_skip_len = 0;
+    float logit_bound = 0.f;
+    void* stream = nullptr;
+};
+
+// The kernel table: one row per instantiation. The reported name, the hipFuncSetAttribute pass and the launch all come from here.
+struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_rows; };
+#define G3_ATTN_KERNELS(X) \
+    X(AK_V1_L, NTHREADS, BQ, flash_attn_fwd_kernel<0>) X(AK_V1_S, NTHREADS, BQ, flash_attn_fwd_kernel<1>) \
+    X(AK_V2_L, NTHREADS, BQ, flash_attn_fwd_v2_kernel<0>) X(AK_V2_S, NTHREADS, BQ, flash_attn_fwd_v2_kernel<1>) \
+    X(AK_V3_L, NTHREADS, BQ, flash_attn_fwd_v3_kernel<0, 6, 8, false>) X(AK_V3_S, NTHREADS, BQ, flash_attn_fwd_v3_kernel<1, 6, 8, false>) \
+    X(AK_V3F_L, NTHREADS, BQ, flash_attn_fwd_v3_kernel<0, 6, 8, true>) X(AK_V3F_S, NTHREADS, BQ, flash_attn_fwd_v3_kernel<1, 6, 8, true>) \
+    X(AK_V3FM_L, NTHREADS, BQ, flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>) X(AK_V3FM_S, NTHREADS, BQ, flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>) \
+    X(AK_V3M_L, NTHREADS, BQ, flash_attn_fwd_v3_kernel<0, 6, 8, false, true>) X(AK_V3M_S, NTHREADS, BQ, flash_attn_fwd_v3_kernel<1, 6, 8, false, true>) \
+    X(AK_V3F_CARRY_L, NTHREADS, BQ, flash_attn_fwd_v3_kernel<2, 6, 8, true>) X(AK_V3_CARRY_S, NTHREADS, BQ, flash_attn_fwd_v3_kernel<3, 6, 8, false>) \
+    X(AK_W4_L, W4_THREADS, W4_BQ, flash_attn_fwd_w4_kernel<0>) X(AK_W4_S, W4_THREADS, W4_BQ, flash_attn_fwd_w4_kernel<1>) \
+    X(AK_W4B, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_kernel<false>) X(AK_W4BX, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_kernel<true>) \
+    X(AK_W4BX_CARRY, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_carry_kernel<true>) X(AK_W4BX_NM, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_kernel<true>) \
+    X(AK_W4BX_NM_CARRY, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_carry_kernel<true>)
+#define G3_ATTN_ID(ID, THREADS, Q_ROWS, ...) ID,
+#define G3_ATTN_ROW(ID, THREADS, Q_ROWS, ...) {#__VA_ARGS__, &__VA_ARGS__, THREADS, Q_ROWS},
+enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) AK_COUNT };
+static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW)};
+#undef G3_ATTN_ID
+#undef G3_ATTN_ROW
+
+// 0 (default) = automatic: w4b with the cross-barrier prefetch (11) on long contexts made of whole 64-key tiles whose 256-row workgroups fill the chip's 256 CUs evenly,
+// else 4. Explicit values are kept for A/B runs and tests: 1 non-pipelined, 2 software-pipelined, 3 LDS-DMA + pinned interleave,
+// 4 = 3 + folded scale/max on long contexts, 5-8 test forms of 4, 9 = w4 (one wave per SIMD), 10 = w4b, 11 = w4b + cross-barrier prefetch.
+static int attn_resolve_variant(int Sq, int Skv, int B, int H, int requested) {
     int variant = requested ? requested : g3_opt_attn_variant;
     if (variant == 0) {
         const long n_wg = (long)((Sq + 255) / 256) * H * B;
@@ -1038,121 +1080,112 @@ static int attn_resolve_variant(int Sq, int Skv, int B, int H, int requested = 0
     return variant;
 }
 
-extern "C" const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant_req) {
-    const bool long_ctx = Skv > 2048;
-    switch (attn_resolve_variant(Sq, Skv, B, H, variant_req)) {
-        case 1: return long_ctx ? "flash_attn_fwd_kernel<0>" : "flash_attn_fwd_kernel<1>";
-        case 2: return long_ctx ? "flash_attn_fwd_v2_kernel<0>" : "flash_attn_fwd_v2_kernel<1>";
-        case 3: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, false>" : "flash_attn_fwd_v3_kernel<1, 6, 8, false>";
-        case 5: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, true>" : "flash_attn_fwd_v3_kernel<1, 6, 8, true>";
-        case 6: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>" : "flash_attn_fwd_v3_kernel<1, 6, 8, false, true>";
-        case 7: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>" : "flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>";
-        case 8: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, false, true>" : "flash_attn_fwd_v3_kernel<1, 6, 8, false, true>";
-        case 9: return long_ctx ? "flash_attn_fwd_w4_kernel<0>" : "flash_attn_fwd_w4_kernel<1>";
-        case 10: return "flash_attn_fwd_w4b_kernel<false>";
-        case 11: return "flash_attn_fwd_w4b_kernel<true>";
-        default: return long_ctx ? "flash_attn_fwd_v3_kernel<0, 6, 8, true>" : "flash_attn_fwd_v3_kernel<1, 6, 8, false>";
-    }
-}
-
-extern "C" const char* g3_flash_attn_kernel_name(int Sq, int Skv, int B, int H) { return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, 0); }
-
 // The no-max form's range: P >= 2^(-2 bound) must stay a normal fp32 with room to spare (v_exp_f32 and the MFMA flush below 2^-126).
 constexpr float NM_BOUND_LOG2_MAX = 60.0f;
 static float attn_bound_log2(float logit_bound) { return logit_bound * 1.4426950408889634f; }
 static bool attn_bound_usable(float bound_log2) { return bound_log2 > 0.f && bound_log2 <= NM_BOUND_LOG2_MAX; }  // (false for NaN)
 
-extern "C" const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant) {
-    if (attn_resolve_variant(Sq, Skv, B, H, variant) == 11 && attn_bound_usable(attn_bound_log2(logit_bound))) return "flash_attn_fwd_w4b_nm_kernel<true>";
-    return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, variant);
+// The table row of a RESOLVED variant. cp_form: the carry entries (their kernels exist for 4 and 11; every other variant names its plain kernel, which
+// those entries refuse); no_max: bounded logits on 11; carry_or_skip: a carry-in state or a skipped range inside the keys.
+static const AttnKernel& attn_kernel_for(int variant, int Skv, bool cp_form, bool no_max, bool carry_or_skip) {
+    // [variant][short context]. VALU quotas (6, 8) per MFMA measured best of {(4,4), (5,6), (6,8)} (profiles/r1_v5_attn_quota_ab.txt); 4: the fold's
+    // prologue does not pay on short contexts; 5, 7, 8: tests (fold / hand-counted LDS waits at every length); 6: hand-counted LDS waits
+    static const AttnKernelId by_variant[12][2] = {{AK_V3F_L, AK_V3_S}, {AK_V1_L, AK_V1_S}, {AK_V2_L, AK_V2_S}, {AK_V3_L, AK_V3_S}, {AK_V3F_L, AK_V3_S},
+                                                   {AK_V3F_L, AK_V3F_S}, {AK_V3FM_L, AK_V3M_S}, {AK_V3FM_L, AK_V3FM_S}, {AK_V3M_L, AK_V3M_S},
+                                                   {AK_W4_L, AK_W4_S}, {AK_W4B, AK_W4B}, {AK_W4BX, AK_W4BX}};
+    const bool short_ctx = Skv <= 2048;
+    if (variant == 11 && no_max) return attn_kernels[cp_form && carry_or_skip ? AK_W4BX_NM_CARRY : AK_W4BX_NM];
+    if (variant == 11 && cp_form) return attn_kernels[AK_W4BX_CARRY];
+    if (variant == 4 && cp_form) return attn_kernels[short_ctx ? AK_V3_CARRY_S : AK_V3F_CARRY_L];
+    return attn_kernels[by_variant[variant >= 1 && variant <= 11 ? variant : 4][short_ctx]];
 }
 
-// The kernel g3_flash_attn_fwd_carry_bf16 launches where the plain entry points launch the one named by g3_flash_attn_kernel_name_ex
-static const char* attn_carry_kernel_name(int Sq, int Skv, int B, int H, int variant_req) {
-    switch (attn_resolve_variant(Sq, Skv, B, H, variant_req)) {
-        case 11: return "flash_attn_fwd_w4b_carry_kernel<true>";
-        case 4: return Skv > 2048 ? "flash_attn_fwd_v3_kernel<2, 6, 8, true>" : "flash_attn_fwd_v3_kernel<3, 6, 8, false>";
-        default: return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, variant_req);  // (refused by the entry point)
+struct AttnPlan { AttnParams p; const AttnKernel* kernel; dim3 grid; };
+constexpr size_t ATTN_SMEM = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
+
+// Every check, every normalisation and the kernel choice of a call; G3_OK and a filled plan, or the refusal (g3_set_error). No HIP call, and no
+// operand is dereferenced. The carry and bounded-cp entries share their checks and texts: what the latter cannot run bounded IS the former.
+static int attn_plan(const AttnCall& call, AttnPlan& plan) {
+    AttnCall c = call;  // (a skip at the front moves c.k / c.vt)
+    const bool cp_form = c.entry == G3_ATTN_ENTRY_CARRY || c.entry == G3_ATTN_ENTRY_BOUNDED_CP;
+    const char* fn = cp_form ? "g3_flash_attn_fwd_carry_bf16" : c.entry == G3_ATTN_ENTRY_BOUNDED ? "g3_self_attn_fwd_bounded_bf16" : "g3_flash_attn_fwd_ex_bf16";
+    uint32_t kv_skip_vt_bytes = 0;
+    if (c.entry == G3_ATTN_ENTRY_KVSEG && c.vt_seg_len <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: vt_seg_len must be positive");
+    if (c.entry == G3_ATTN_ENTRY_CROSS && c.kv_dense < 0) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense must be >= 0 (0 = every key through the loop)");
+    if (c.entry >= G3_ATTN_ENTRY_EX) {  // the entries with a per-call variant and o_partial / lse
+        if (c.variant < 0 || c.variant > 11) return g3_set_error(G3_ERR_ARG, "%s: variant %d out of range", fn, c.variant);
+        if (c.o.ptr && c.o_partial) return g3_set_error(G3_ERR_ARG, "%s: pass either o (bf16 result) or o_partial + lse, not both", fn);
+        if (!cp_form && c.o_partial && ((c.o.row & 3) || (c.o.batch & 3) || (c.o.head & 3))) return g3_set_error(G3_ERR_ARG, "%s: o_partial strides must be multiples of 4", fn);
     }
-}
-
-// Skv: the attended keys (a skipped range not counted); segmented: V^T in key segments (the name does not depend on it: both forms run the same
-// kernels); cp_form: a carry-in state, or a skipped range strictly inside the keys (0 < kv_skip_begin < S_kv, kv_skip_len > 0)
-extern "C" const char* g3_self_attn_cp_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant, int segmented, int cp_form) {
-    (void)segmented;
-    if (attn_resolve_variant(Sq, Skv, B, H, variant) == 11 && attn_bound_usable(attn_bound_log2(logit_bound)))
-        return cp_form ? "flash_attn_fwd_w4b_nm_carry_kernel<true>" : "flash_attn_fwd_w4b_nm_kernel<true>";
-    return attn_carry_kernel_name(Sq, Skv, B, H, variant);
-}
-
-static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
-                             int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
-                             int64_t vt_seg_stride, void* o, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H,
-                             int head_dim, float softmax_scale, void* stream, int variant_req = 0, float* o_partial = nullptr, float* lse = nullptr, int kv_dense = 0,
-                             const void* q_norm_w = nullptr, float q_norm_eps = 0.f, bool cp_form = false, const float* carry_o = nullptr,
-                             const float* carry_lse = nullptr, int kv_skip_begin = 0, int kv_skip_len = 0, uint32_t kv_skip_vt_bytes = 0,
-                             float logit_bound = 0.f, bool bounded_cp = false) {
-    if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: null operand");
-    if ((o_partial != nullptr) != (lse != nullptr)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial and lse go together");
-    if (o_partial && (((uintptr_t)o_partial & 15) || ((uintptr_t)lse & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: misaligned o_partial / lse");
-    if (head_dim != HD) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: head_dim %d unsupported (128 only)", head_dim);
-    if (Sq <= 0 || Skv <= 0 || B <= 0 || H <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: bad shape");
-    if ((q_row & 7) || (k_row & 7) || (vt_row & 7) || (o_row & 3) || (q_batch & 7) || (k_batch & 7) || (vt_batch & 7) ||
-        (q_head & 7) || (k_head & 7) || (vt_head & 7) || (o_batch & 3) || (o_head & 3))
+    if (cp_form) {
+        if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || (!c.o.ptr && !c.o_partial)) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
+        if ((c.o.row & 3) || (c.o.batch & 3) || (c.o.head & 3)) return g3_set_error(G3_ERR_ARG, "%s: o / o_partial / carry_o strides must be multiples of 4", fn);
+        if ((c.carry_o != nullptr) != (c.carry_lse != nullptr)) return g3_set_error(G3_ERR_ARG, "%s: carry_o and carry_lse go together", fn);
+        if (c.carry_o && (((uintptr_t)c.carry_o & 15) || ((uintptr_t)c.carry_lse & 3))) return g3_set_error(G3_ERR_ARG, "%s: misaligned carry_o (16 B) / carry_lse (4 B)", fn);
+        if (c.Skv <= 0) return g3_set_error(G3_ERR_ARG, "%s: bad shape", fn);
+        if (c.kv_skip_begin < 0 || c.kv_skip_len < 0 || (c.kv_skip_begin % KVB) || (c.kv_skip_len % KVB) || c.kv_skip_begin > c.Skv)
+            return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must be multiples of 64 with 0 <= begin <= S_kv %d", fn, c.kv_skip_begin, c.kv_skip_len, c.Skv);
+        if (c.vt_seg_len > 0 && c.kv_skip_len > 0 && ((c.kv_skip_begin % c.vt_seg_len) || (c.kv_skip_len % c.vt_seg_len)))
+            return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must cover whole V^T segments of %d keys", fn, c.kv_skip_begin, c.kv_skip_len, c.vt_seg_len);
+        if ((int64_t)c.Skv + c.kv_skip_len > 0x7fffffff) return g3_set_error(G3_ERR_ARG, "%s: S_kv + kv_skip_len overflows", fn);
+        if (c.vt_seg_len > 0 && c.vt_seg_stride <= 0) return g3_set_error(G3_ERR_ARG, "%s: vt_seg_stride must be positive", fn);
+        if (c.vt_seg_len == 0 && c.vt.row < ((int64_t)c.Skv + c.kv_skip_len + KVB - 1) / KVB * KVB)  // (the kernels read whole V^T tiles unguarded)
+            return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S_kv + kv_skip_len) forces the 64-bit-addressing kernel, which has no carry form", fn,
+                                (long long)c.vt.row);
+        // a skip at either end is a different base (begin 0) or nothing at all (begin == S_kv): the kernels only ever see 0 < begin < S_kv
+        auto vt_jump = [&] { return c.vt_seg_len > 0 ? (int64_t)(c.kv_skip_len / c.vt_seg_len) * c.vt_seg_stride : (int64_t)c.kv_skip_len; };  // elements
+        if (c.kv_skip_len > 0 && c.kv_skip_begin == 0) {  // (the row stride stays; only the keys addressed inside a row move)
+            c.k.ptr = (const bf16_t*)c.k.ptr + (int64_t)c.kv_skip_len * c.k.row;
+            c.vt.ptr = (const bf16_t*)c.vt.ptr + vt_jump();
+            c.kv_skip_len = 0;
+        }
+        if (c.kv_skip_begin == c.Skv) c.kv_skip_len = 0;
+        if (c.kv_skip_len == 0) c.kv_skip_begin = 0;
+        if (vt_jump() * 2 > 0xFFFFFFFFll) return g3_set_error(G3_ERR_ARG, "%s: the skipped V^T range exceeds the kernel's 32-bit byte offsets", fn);
+        kv_skip_vt_bytes = (uint32_t)(vt_jump() * 2);
+    }
+    if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || (!c.o.ptr && !c.o_partial)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: null operand");
+    if ((c.o_partial != nullptr) != (c.lse != nullptr)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial and lse go together");
+    if (c.o_partial && (((uintptr_t)c.o_partial & 15) || ((uintptr_t)c.lse & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: misaligned o_partial / lse");
+    if (c.head_dim != HD) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: head_dim %d unsupported (128 only)", c.head_dim);
+    if (c.Sq <= 0 || c.Skv <= 0 || c.B <= 0 || c.H <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: bad shape");
+    if ((c.q.row & 7) || (c.k.row & 7) || (c.vt.row & 7) || (c.o.row & 3) || (c.q.batch & 7) || (c.k.batch & 7) || (c.vt.batch & 7) ||
+        (c.q.head & 7) || (c.k.head & 7) || (c.vt.head & 7) || (c.o.batch & 3) || (c.o.head & 3))
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: strides must keep 16-byte (q,k,vt) / 8-byte (o) alignment");
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)vt) & 15) || ((uintptr_t)o & 7))
+    if ((((uintptr_t)c.q.ptr | (uintptr_t)c.k.ptr | (uintptr_t)c.vt.ptr) & 15) || ((uintptr_t)c.o.ptr & 7))
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: misaligned pointer");
-    const int skv_phys = Skv + kv_skip_len;  // keys the operands span (CP form: the skipped range included)
-    const int kv_span = vt_seg_len > 0 ? vt_seg_len : skv_phys;  // keys addressed through one vt_row
-    if (vt_seg_len < 0 || (vt_seg_len > 0 && ((vt_seg_len % KVB) || (skv_phys % vt_seg_len) || (vt_seg_stride & 7) || vt_seg_stride <= 0)))
+    const int skv_phys = c.Skv + c.kv_skip_len;  // keys the operands span (CP form: the skipped range included)
+    const int kv_span = c.vt_seg_len > 0 ? c.vt_seg_len : skv_phys;  // keys addressed through one vt_row
+    if (c.vt_seg_len < 0 || (c.vt_seg_len > 0 && ((c.vt_seg_len % KVB) || (skv_phys % c.vt_seg_len) || (c.vt_seg_stride & 7) || c.vt_seg_stride <= 0)))
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: segments must be a multiple of 64 keys, tile S_kv exactly, 16-byte aligned stride");
-    if (vt_row < ((kv_span + 7) & ~7)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: vt leading dim %lld < keys per row rounded to 8", (long long)vt_row);
-    AttnParams p;
-    p.Q = (const bf16_t*)q; p.q_row = q_row; p.q_batch = q_batch; p.q_head = q_head;
-    p.K = (const bf16_t*)k; p.k_row = k_row; p.k_batch = k_batch; p.k_head = k_head;
-    p.Vt = (const bf16_t*)vt; p.vt_row = vt_row; p.vt_batch = vt_batch; p.vt_head = vt_head;
-    p.O = (bf16_t*)o; p.o_row = o_row; p.o_batch = o_batch; p.o_head = o_head;
-    p.Sq = Sq; p.Skv = Skv;
-    p.scale_log2 = softmax_scale * 1.4426950408889634f;
-    p.vt_seg_len = vt_seg_len; p.vt_seg_stride = vt_seg_stride;
-    p.grid_q = 0; p.n_hb = 0; p.n_heads = H; p.xcd_heads = 0;
-    p.O32 = o_partial; p.LSE = lse;
-    p.kv_dense = 0;
-    if (kv_dense > 0) {
-        const int kd = ((kv_dense + KVB - 1) / KVB) * KVB;  // whole tiles: the keys between kv_dense and the tile end are zero rows like the rest of the tail
-        if (kv_dense > Skv) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense %d > S_kv %d", kv_dense, Skv);
-        if (kd < Skv) p.kv_dense = kd;
+    if (c.vt.row < ((kv_span + 7) & ~7)) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_bf16: vt leading dim %lld < keys per row rounded to 8", (long long)c.vt.row);
+    int kv_dense = 0;
+    if (c.kv_dense > 0) {
+        const int kd = ((c.kv_dense + KVB - 1) / KVB) * KVB;  // whole tiles: the keys between kv_dense and the tile end are zero rows like the rest of the tail
+        if (c.kv_dense > c.Skv) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense %d > S_kv %d", c.kv_dense, c.Skv);
+        if (kd < c.Skv) kv_dense = kd;
     }
-    p.q_norm_w = (const bf16_t*)q_norm_w; p.q_norm_eps = q_norm_eps;
-    p.carry_o = carry_o; p.carry_lse = carry_lse;
-    p.kv_skip_begin = kv_skip_begin; p.kv_skip_len = kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
-    p.logit_bound_log2 = attn_bound_log2(logit_bound);
-    if (q_norm_w && ((uintptr_t)q_norm_w & 15)) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: misaligned q_norm_weight");
-    const size_t smem = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
-    static bool attr_set[64] = {};  // per device: hipFuncSetAttribute applies to the current device only
-    static std::mutex attr_mu;
-    // 0 (default) = automatic: w4b with the cross-barrier prefetch (11) on long contexts made of whole 64-key tiles whose 256-row workgroups fill the chip's 256 CUs evenly,
-    // else 4. Explicit values are kept for A/B runs and tests: 1 non-pipelined, 2 software-pipelined, 3 LDS-DMA + pinned interleave,
-    // 4 = 3 + folded scale/max on long contexts, 5-8 test forms of 4, 9 = w4 (one wave per SIMD), 10 = w4b, 11 = w4b + cross-barrier prefetch.
-    int variant = attn_resolve_variant(Sq, Skv, B, H, variant_req);
+    if (c.q_norm_w && ((uintptr_t)c.q_norm_w & 15)) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: misaligned q_norm_weight");
+    const bool cross = kv_dense || c.q_norm_w;
+    int variant = attn_resolve_variant(c.Sq, c.Skv, c.B, c.H, c.variant);
     if (cp_form && variant != 4 && variant != 11)
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: the carry / key-skip form exists for the 8-wave (4) and one-wave-per-SIMD (11) kernels only "
                                         "(variant %d chosen; 11 needs S_kv %% 64 == 0)", variant);
-    if (o_partial && variant == 9) variant = 4;  // w4 (ragged S_kv) has no partial epilogue: the 8-wave kernel takes ragged tiles too
-    if ((p.kv_dense || p.q_norm_w) && (variant < 3 || variant >= 9)) variant = 4;  // the zero-tail epilogue and the Q norm live in the v3 kernels
-    if (variant >= 3 && vt_row < ((kv_span + KVB - 1) / KVB) * KVB) variant = 2;  // (also 6-8)  // v3 reads the whole last V^T tile unguarded
+    if (c.o_partial && variant == 9) variant = 4;  // w4 (ragged S_kv) has no partial epilogue: the 8-wave kernel takes ragged tiles too
+    if (cross && (variant < 3 || variant >= 9)) variant = 4;  // the zero-tail epilogue and the Q norm live in the v3 kernels
+    if (variant >= 3 && c.vt.row < ((kv_span + KVB - 1) / KVB) * KVB) variant = 2;  // (also 6-8)  // v3 reads the whole last V^T tile unguarded
     if (variant >= 3) {
         // v3 addresses its K / V^T LDS-DMA sources with 32-bit BYTE offsets from the per-(batch, head) base pointers: the largest
         // offsets it forms must stay below 4 GiB, otherwise they wrap silently (e.g. a strided K view of a fused [S*B, 3*4096]
         // QKV buffer at B >= 4). Out-of-range problems run on v2 (64-bit addressing) when V^T is not segmented.
-        const uint64_t k_max = (uint64_t)(skv_phys - 1 + 2 * KVB) * (uint64_t)k_row * 2u + 256u;
-        const uint64_t n_seg = vt_seg_len > 0 ? (uint64_t)(skv_phys / vt_seg_len) : 1u;
-        const uint64_t v_max = (uint64_t)(HD - 1) * (uint64_t)vt_row * 2u + (n_seg - 1) * (uint64_t)vt_seg_stride * 2u + ((uint64_t)kv_span + KVB) * 2u + 256u;
+        const uint64_t k_max = (uint64_t)(skv_phys - 1 + 2 * KVB) * (uint64_t)c.k.row * 2u + 256u;
+        const uint64_t n_seg = c.vt_seg_len > 0 ? (uint64_t)(skv_phys / c.vt_seg_len) : 1u;
+        const uint64_t v_max = (uint64_t)(HD - 1) * (uint64_t)c.vt.row * 2u + (n_seg - 1) * (uint64_t)c.vt_seg_stride * 2u + ((uint64_t)kv_span + KVB) * 2u + 256u;
         if (k_max > 0xFFFFFFFFull || v_max > 0xFFFFFFFFull) {
             if (cp_form)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: K / V^T span (skipped keys included) exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes); "
                                                 "the 64-bit-addressing kernel has no carry form", (unsigned long long)k_max, (unsigned long long)v_max);
-            if (vt_seg_len > 0)
+            if (c.vt_seg_len > 0)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: K / V^T span exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes)",
                                     (unsigned long long)k_max, (unsigned long long)v_max);
             variant = 2;
@@ -1160,75 +1193,60 @@ static int flash_attn_launch(const void* q, int64_t q_row, int64_t q_batch, int6
     }
     if (cp_form && variant < 3)
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: V^T leading dimension %lld below ceil64 of the keys it spans forces the 64-bit-addressing kernel, which has "
-                                        "no carry form", (long long)vt_row);
-    if (vt_seg_len > 0 && variant < 3)
+                                        "no carry form", (long long)c.vt.row);
+    if (c.vt_seg_len > 0 && variant < 3)
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: segmented V^T is implemented by the default (v3) kernel only");
-    if (o_partial && variant < 3)
+    if (c.o_partial && variant < 3)
         return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: split-KV partial outputs are implemented by the v3 / w4b kernels only (variant %d chosen)", variant);
-    if ((p.kv_dense || p.q_norm_w) && variant < 3)  // (a V^T leading dimension or an operand span that forced the 64-bit-addressing kernel above)
+    if (cross && variant < 3)  // (a V^T leading dimension or an operand span that forced the 64-bit-addressing kernel above)
         return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: the Q norm / zero-tail form is implemented by the v3 kernels only (variant %d chosen: V^T leading dimension below "
                                         "ceil64(S_kv), or operands beyond the kernel's 32-bit byte offsets)", variant);
+    AttnParams& p = plan.p;
+    p.Q = (const bf16_t*)c.q.ptr; p.q_row = c.q.row; p.q_batch = c.q.batch; p.q_head = c.q.head;
+    p.K = (const bf16_t*)c.k.ptr; p.k_row = c.k.row; p.k_batch = c.k.batch; p.k_head = c.k.head;
+    p.Vt = (const bf16_t*)c.vt.ptr; p.vt_row = c.vt.row; p.vt_batch = c.vt.batch; p.vt_head = c.vt.head;
+    p.O = (bf16_t*)c.o.ptr; p.o_row = c.o.row; p.o_batch = c.o.batch; p.o_head = c.o.head;
+    p.Sq = c.Sq; p.Skv = c.Skv;
+    p.scale_log2 = c.softmax_scale * 1.4426950408889634f;
+    p.vt_seg_len = c.vt_seg_len; p.vt_seg_stride = c.vt_seg_stride;
+    p.grid_q = 0; p.n_hb = 0; p.n_heads = c.H; p.xcd_heads = 0;
+    p.O32 = c.o_partial; p.LSE = c.lse;
+    p.kv_dense = kv_dense;
+    p.q_norm_w = (const bf16_t*)c.q_norm_w; p.q_norm_eps = c.q_norm_eps;
+    p.carry_o = c.carry_o; p.carry_lse = c.carry_lse;
+    p.kv_skip_begin = c.kv_skip_begin; p.kv_skip_len = c.kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
+    p.logit_bound_log2 = attn_bound_log2(c.logit_bound);
+    // bounded logits (only the two bounded entries carry a bound): the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems
+    // only; g3_self_attn_fwd_bounded_cp_bf16: also with segmented V^T, and with a carry-in state or a skipped key range. Everything else runs as it always did.
+    const bool no_max = attn_bound_usable(p.logit_bound_log2) && (c.entry == G3_ATTN_ENTRY_BOUNDED_CP || (!cp_form && c.vt_seg_len == 0));
+    plan.kernel = &attn_kernel_for(variant, c.Skv, cp_form, no_max, c.carry_o || c.kv_skip_len > 0);
+    plan.grid = dim3((c.Sq + plan.kernel->q_rows - 1) / plan.kernel->q_rows, c.H, c.B);
+    if (variant == 10 || variant == 11) {  // w4b (attention_w4b.hpp): optionally a 1-D grid that gives every XCD its own (batch, head) pairs
+        p.grid_q = (int)plan.grid.x; p.n_hb = c.H * c.B;
+        p.xcd_heads = (g3_opt_attn_xcd_heads && (c.H * c.B) % 8 == 0) ? 1 : 0;
+        if (p.xcd_heads) plan.grid = dim3(plan.grid.x * c.H * c.B, 1, 1);
+    }
+    return G3_OK;
+}
+
+static int attn_launch(const AttnCall& c) {
+    AttnPlan plan;
+    if (int rc = attn_plan(c, plan)) return rc;
+    static bool attr_set[64] = {};  // per device: hipFuncSetAttribute applies to the current device only
+    static std::mutex attr_mu;
     int dev_id = 0;
     if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipGetDevice failed");
     {
-      std::lock_guard<std::mutex> attr_lock(attr_mu);
-      if (!attr_set[dev_id]) {
-        const void* fns[21] = {reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_carry_kernel<true>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_w4b_nm_kernel<true>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_carry_kernel<true>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<2, 6, 8, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<3, 6, 8, false>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<false>), reinterpret_cast<const void*>(&flash_attn_fwd_w4b_kernel<true>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_kernel<1>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v2_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_v2_kernel<1>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, true>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<0, 6, 8, false, true>), reinterpret_cast<const void*>(&flash_attn_fwd_v3_kernel<1, 6, 8, false, true>),
-                               reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<0>), reinterpret_cast<const void*>(&flash_attn_fwd_w4_kernel<1>)};
-        for (int i = 0; i < 21; ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
+        std::lock_guard<std::mutex> attr_lock(attr_mu);
+        if (!attr_set[dev_id]) {
+            for (const AttnKernel& kern : attn_kernels) {
+                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_SMEM);
+                if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
+            }
+            attr_set[dev_id] = true;
         }
-        attr_set[dev_id] = true;
-      }
     }
-    dim3 grid((Sq + BQ - 1) / BQ, H, B);
-    const bool long_ctx = Skv > 2048;
-    hipStream_t st = (hipStream_t)stream;
-    if (variant == 10 || variant == 11) {  // w4 with the trimmed issue stream (attention_w4b.hpp)
-        dim3 grid4((Sq + W4_BQ - 1) / W4_BQ, H, B);
-        p.grid_q = (int)grid4.x; p.n_hb = H * B; p.n_heads = H;
-        p.xcd_heads = (g3_opt_attn_xcd_heads && (H * B) % 8 == 0) ? 1 : 0;
-        if (p.xcd_heads) grid4 = dim3(grid4.x * H * B, 1, 1);
-        // bounded logits: the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems only. g3_self_attn_fwd_bounded_cp_bf16
-        // (bounded_cp): also with segmented V^T, and - flash_attn_fwd_w4b_nm_carry_kernel - with a carry-in state or a skipped key range (the entry
-        // point has normalised a skip at either end away). Everything else runs as it always did.
-        const bool bound_ok = variant == 11 && !p.kv_dense && attn_bound_usable(p.logit_bound_log2);
-        const bool no_max = bound_ok && (bounded_cp || (!cp_form && vt_seg_len == 0));
-        if (no_max && cp_form && (carry_o || kv_skip_len > 0)) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
-        else if (no_max) hipLaunchKernelGGL(flash_attn_fwd_w4b_nm_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
-        else if (cp_form) hipLaunchKernelGGL(flash_attn_fwd_w4b_carry_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
-        else if (variant == 11) hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<true>, grid4, dim3(W4_THREADS), smem, st, p);
-        else hipLaunchKernelGGL(flash_attn_fwd_w4b_kernel<false>, grid4, dim3(W4_THREADS), smem, st, p);
-        return g3_check_launch("g3_flash_attn_fwd_bf16");
-    }
-    if (variant == 9) {  // one wave per SIMD, 64 query rows per wave (attention_w4.hpp)
-        dim3 grid4((Sq + W4_BQ - 1) / W4_BQ, H, B);
-        if (long_ctx) hipLaunchKernelGGL(flash_attn_fwd_w4_kernel<0>, grid4, dim3(W4_THREADS), smem, st, p);
-        else hipLaunchKernelGGL(flash_attn_fwd_w4_kernel<1>, grid4, dim3(W4_THREADS), smem, st, p);
-        return g3_check_launch("g3_flash_attn_fwd_bf16");
-    }
-#define G3_LAUNCH_ATTN(KERNEL0, KERNEL1) do { if (long_ctx) hipLaunchKernelGGL(KERNEL0, grid, dim3(NTHREADS), smem, st, p); else hipLaunchKernelGGL(KERNEL1, grid, dim3(NTHREADS), smem, st, p); } while (0)
-    // VALU quotas (6, 8) per MFMA measured best of {(4,4), (5,6), (6,8)} (profiles/r1_v5_attn_quota_ab.txt)
-    if (cp_form) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<2, 6, 8, true>), (flash_attn_fwd_v3_kernel<3, 6, 8, false>));  // variant 4's kernels
-    else if (variant == 1) G3_LAUNCH_ATTN(flash_attn_fwd_kernel<0>, flash_attn_fwd_kernel<1>);
-    else if (variant == 2) G3_LAUNCH_ATTN(flash_attn_fwd_v2_kernel<0>, flash_attn_fwd_v2_kernel<1>);
-    else if (variant == 3) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, false>), (flash_attn_fwd_v3_kernel<1, 6, 8, false>));
-    else if (variant == 5) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, true>), (flash_attn_fwd_v3_kernel<1, 6, 8, true>));  // tests: folded arithmetic at every length
-    else if (variant == 6) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), (flash_attn_fwd_v3_kernel<1, 6, 8, false, true>));  // hand-counted LDS waits
-    else if (variant == 7) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, true, true, 4, 4>), (flash_attn_fwd_v3_kernel<1, 6, 8, true, true, 4, 4>));   // tests: MW + fold at every length
-    else if (variant == 8) G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, false, true>), (flash_attn_fwd_v3_kernel<1, 6, 8, false, true>)); // tests: MW, unfolded
-    else G3_LAUNCH_ATTN((flash_attn_fwd_v3_kernel<0, 6, 8, true>), (flash_attn_fwd_v3_kernel<1, 6, 8, false>));  // short contexts: the fold's prologue does not pay
-#undef G3_LAUNCH_ATTN
+    hipLaunchKernelGGL(plan.kernel->fn, plan.grid, dim3(plan.kernel->threads), ATTN_SMEM, (hipStream_t)c.stream, plan.p);
     return g3_check_launch("g3_flash_attn_fwd_bf16");
 }
 
@@ -1237,17 +1255,23 @@ extern "C" int g3_flash_attn_fwd_bf16(const void* q, int64_t q_row, int64_t q_ba
                                       int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row, int64_t o_batch,
                                       int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale,
                                       void* stream) {
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, 0, 0, o, o_row, o_batch, o_head,
-                             Sq, Skv, B, H, head_dim, softmax_scale, stream);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_FWD;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 extern "C" int g3_flash_attn_fwd_kvseg_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
                                             int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch,
                                             int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, void* o, int64_t o_row, int64_t o_batch,
                                             int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, void* stream) {
-    if (vt_seg_len <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: vt_seg_len must be positive");
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
-                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_KVSEG;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 /* ---- cross-attention form: optional per-head RMSNorm of Q in the kernel's Q load (AttnParams::q_norm_w) and optional all-zero key tail (AttnParams::kv_dense) ---- */
@@ -1255,9 +1279,12 @@ extern "C" int g3_cross_attn_fwd_bf16(const void* q, int64_t q_row, int64_t q_ba
                                       int64_t k_row, int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o,
                                       int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int kv_dense, int B, int H, int head_dim,
                                       float softmax_scale, void* stream) {
-    if (kv_dense < 0) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense must be >= 0 (0 = every key through the loop)");
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, 0, 0, o, o_row, o_batch, o_head, Sq, Skv, B, H,
-                             head_dim, softmax_scale, stream, 0, nullptr, nullptr, kv_dense, q_norm_weight, q_norm_eps);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_CROSS;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.kv_dense = kv_dense; c.q_norm_w = q_norm_weight; c.q_norm_eps = q_norm_eps;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 /* ---- per-call kernel choice + split-KV partial outputs ------------------------------------------------------------------------------------ */
@@ -1266,11 +1293,12 @@ extern "C" int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q
                                          int vt_seg_len, int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row,
                                          int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale,
                                          int variant, void* stream) {
-    if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: variant %d out of range", variant);
-    if (o && o_partial) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: pass either o (bf16 result) or o_partial + lse, not both");
-    if (o_partial && ((o_row & 3) || (o_batch & 3) || (o_head & 3))) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_ex_bf16: o_partial strides must be multiples of 4");
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
-                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_EX;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; c.o_partial = o_partial; c.lse = lse; c.variant = variant;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 /* ---- self-attention with bounded logits: the no-max form of the one-wave-per-SIMD kernel where it applies, else exactly g3_flash_attn_fwd_ex_bf16 -------- */
@@ -1279,64 +1307,28 @@ extern "C" int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64
                                              int vt_seg_len, int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row,
                                              int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale,
                                              float logit_bound, int variant, void* stream) {
-    if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: variant %d out of range", variant);
-    if (o && o_partial) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: pass either o (bf16 result) or o_partial + lse, not both");
-    if (o_partial && ((o_row & 3) || (o_batch & 3) || (o_head & 3))) return g3_set_error(G3_ERR_ARG, "g3_self_attn_fwd_bounded_bf16: o_partial strides must be multiples of 4");
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
-                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse, 0, nullptr, 0.f, false, nullptr, nullptr, 0, 0, 0u,
-                             logit_bound);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_BOUNDED;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; c.o_partial = o_partial; c.lse = lse; c.variant = variant; c.logit_bound = logit_bound;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 /* ---- carry-in state + skipped key range (context parallelism without a merge pass) --------------------------------------------------------- */
-// (logit_bound / bounded_cp: g3_self_attn_fwd_bounded_cp_bf16 - the same checks in the same order, so that what it cannot run bounded IS this entry)
-static int flash_attn_carry_entry(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
-                                  int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
-                                  int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
-                                  const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
-                                  int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
-                                  void* stream, float logit_bound, bool bounded_cp) {
-    const char* fn = "g3_flash_attn_fwd_carry_bf16";
-    if (variant < 0 || variant > 11) return g3_set_error(G3_ERR_ARG, "%s: variant %d out of range", fn, variant);
-    if (o && o_partial) return g3_set_error(G3_ERR_ARG, "%s: pass either o (bf16 result) or o_partial + lse, not both", fn);
-    if (!q || !k || !vt || (!o && !o_partial)) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
-    if ((o_row & 3) || (o_batch & 3) || (o_head & 3)) return g3_set_error(G3_ERR_ARG, "%s: o / o_partial / carry_o strides must be multiples of 4", fn);
-    if ((carry_o != nullptr) != (carry_lse != nullptr)) return g3_set_error(G3_ERR_ARG, "%s: carry_o and carry_lse go together", fn);
-    if (carry_o && (((uintptr_t)carry_o & 15) || ((uintptr_t)carry_lse & 3))) return g3_set_error(G3_ERR_ARG, "%s: misaligned carry_o (16 B) / carry_lse (4 B)", fn);
-    if (Skv <= 0) return g3_set_error(G3_ERR_ARG, "%s: bad shape", fn);
-    if (kv_skip_begin < 0 || kv_skip_len < 0 || (kv_skip_begin % KVB) || (kv_skip_len % KVB) || kv_skip_begin > Skv)
-        return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must be multiples of 64 with 0 <= begin <= S_kv %d", fn, kv_skip_begin, kv_skip_len, Skv);
-    if (vt_seg_len > 0 && kv_skip_len > 0 && ((kv_skip_begin % vt_seg_len) || (kv_skip_len % vt_seg_len)))
-        return g3_set_error(G3_ERR_ARG, "%s: kv_skip (begin %d, len %d) must cover whole V^T segments of %d keys", fn, kv_skip_begin, kv_skip_len, vt_seg_len);
-    if ((int64_t)Skv + kv_skip_len > 0x7fffffff) return g3_set_error(G3_ERR_ARG, "%s: S_kv + kv_skip_len overflows", fn);
-    const int64_t vt_jump = vt_seg_len > 0 ? (int64_t)(kv_skip_len / vt_seg_len) * vt_seg_stride : (int64_t)kv_skip_len;  // elements
-    if (vt_seg_len > 0 && vt_seg_stride <= 0) return g3_set_error(G3_ERR_ARG, "%s: vt_seg_stride must be positive", fn);
-    // a skip at either end is a different base (begin 0) or nothing at all (begin == S_kv): the kernels only ever see 0 < begin < S_kv
-    if (vt_seg_len == 0 && vt_row < ((int64_t)Skv + kv_skip_len + KVB - 1) / KVB * KVB)  // (the kernels read whole V^T tiles unguarded)
-        return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S_kv + kv_skip_len) forces the 64-bit-addressing kernel, which has no carry form", fn,
-                            (long long)vt_row);
-    if (kv_skip_len > 0 && kv_skip_begin == 0) {  // (the row stride stays; only the keys addressed inside a row move)
-        k = (const bf16_t*)k + (int64_t)kv_skip_len * k_row;
-        vt = (const bf16_t*)vt + vt_jump;
-        kv_skip_len = 0;
-    }
-    if (kv_skip_begin == Skv) kv_skip_len = 0;
-    if (kv_skip_len == 0) kv_skip_begin = 0;
-    const int64_t vt_jump_bytes = (vt_seg_len > 0 ? (int64_t)(kv_skip_len / vt_seg_len) * vt_seg_stride : (int64_t)kv_skip_len) * 2;
-    if (vt_jump_bytes > 0xFFFFFFFFll) return g3_set_error(G3_ERR_ARG, "%s: the skipped V^T range exceeds the kernel's 32-bit byte offsets", fn);
-    return flash_attn_launch(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, o, o_row,
-                             o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, stream, variant, o_partial, lse, 0, nullptr, 0.f, true, carry_o,
-                             carry_lse, kv_skip_begin, kv_skip_len, (uint32_t)vt_jump_bytes, logit_bound, bounded_cp);
-}
-
 extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
                                             int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
                                             int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
                                             const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
                                             int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant,
                                             void* stream) {
-    return flash_attn_carry_entry(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, kv_skip_begin,
-                                  kv_skip_len, carry_o, carry_lse, o, o_partial, lse, o_row, o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, variant, stream,
-                                  0.f, false);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_CARRY;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; c.o_partial = o_partial; c.lse = lse; c.variant = variant;
+    c.kv_skip_begin = kv_skip_begin; c.kv_skip_len = kv_skip_len; c.carry_o = carry_o; c.carry_lse = carry_lse;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
 }
 
 /* ---- the same with bounded logits: the no-max kernels under key sharding (segmented V^T, carry-in, skipped key range), else exactly the entry above ------ */
@@ -1346,9 +1338,52 @@ extern "C" int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, in
                                                 const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch,
                                                 int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, float logit_bound,
                                                 int variant, void* stream) {
-    return flash_attn_carry_entry(q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride, kv_skip_begin,
-                                  kv_skip_len, carry_o, carry_lse, o, o_partial, lse, o_row, o_batch, o_head, Sq, Skv, B, H, head_dim, softmax_scale, variant, stream,
-                                  logit_bound, true);
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_BOUNDED_CP;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; c.o_partial = o_partial; c.lse = lse; c.variant = variant; c.logit_bound = logit_bound;
+    c.kv_skip_begin = kv_skip_begin; c.kv_skip_len = kv_skip_len; c.carry_o = carry_o; c.carry_lse = carry_lse;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
+}
+
+/* ---- dry run: the kernel a call to `entry` with these arguments would launch, or NULL with the call's own refusal in g3_last_error(). Never touches HIP. ---- */
+extern "C" const char* g3_attn_plan_bf16(int entry, const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* q_norm_weight, float q_norm_eps,
+                                         const void* k, int64_t k_row, int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch,
+                                         int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                         const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
+                                         int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant) {
+    if (entry < G3_ATTN_ENTRY_FWD || entry > G3_ATTN_ENTRY_BOUNDED_CP) { g3_set_error(G3_ERR_ARG, "g3_attn_plan_bf16: unknown entry %d", entry); return nullptr; }
+    const bool cp_form = entry == G3_ATTN_ENTRY_CARRY || entry == G3_ATTN_ENTRY_BOUNDED_CP;
+    AttnCall c;  // only what the named entry takes: the rest keeps its default, as in that entry
+    c.entry = entry;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale;
+    if (entry == G3_ATTN_ENTRY_CROSS) { c.kv_dense = kv_dense; c.q_norm_w = q_norm_weight; c.q_norm_eps = q_norm_eps; }
+    if (entry == G3_ATTN_ENTRY_KVSEG || entry >= G3_ATTN_ENTRY_EX) { c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; }
+    if (entry >= G3_ATTN_ENTRY_EX) { c.o_partial = o_partial; c.lse = lse; c.variant = variant; }
+    if (entry == G3_ATTN_ENTRY_BOUNDED || entry == G3_ATTN_ENTRY_BOUNDED_CP) c.logit_bound = logit_bound;
+    if (cp_form) { c.kv_skip_begin = kv_skip_begin; c.kv_skip_len = kv_skip_len; c.carry_o = carry_o; c.carry_lse = carry_lse; }
+    AttnPlan plan;
+    return attn_plan(c, plan) == G3_OK ? plan.kernel->name : nullptr;
+}
+
+/* ---- the shapes-only name functions: the plan's own choice code for a call with plain, addressable operands (g3_attn_plan_bf16 answers for a real call) ---- */
+extern "C" const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant) {
+    return attn_kernel_for(attn_resolve_variant(Sq, Skv, B, H, variant), Skv, false, false, false).name;
+}
+
+extern "C" const char* g3_flash_attn_kernel_name(int Sq, int Skv, int B, int H) { return g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, 0); }
+
+extern "C" const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant) {
+    return attn_kernel_for(attn_resolve_variant(Sq, Skv, B, H, variant), Skv, false, attn_bound_usable(attn_bound_log2(logit_bound)), false).name;
+}
+
+// Skv: the attended keys (a skipped range not counted); segmented: V^T in key segments (the name does not depend on it: both forms run the same
+// kernels); cp_form: a carry-in state, or a skipped range strictly inside the keys (0 < kv_skip_begin < S_kv, kv_skip_len > 0)
+extern "C" const char* g3_self_attn_cp_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant, int segmented, int cp_form) {
+    (void)segmented;
+    return attn_kernel_for(attn_resolve_variant(Sq, Skv, B, H, variant), Skv, true, attn_bound_usable(attn_bound_log2(logit_bound)), cp_form != 0).name;
 }
 
 namespace {

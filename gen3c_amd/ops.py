@@ -483,59 +483,12 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv:
     counts the attended keys). partial=True may then also take `out`, an fp32 view to write the part into (it may be carry's o_part).
     Either one (or partial=True with `out`) runs g3_flash_attn_fwd_carry_bf16 - variant 0, 4 or 11 only; no fallback."""
     if carry is not None or kv_skip is not None or (partial and out is not None):
-        return _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip)
-    qr, qw, ldq = _rowmajor2d(q, "q")
-    kr, kw, ldk = _rowmajor2d(k, "k")
-    assert qr == Sq * B and kr == Skv * B and qw == H * 128 and kw == H * 128
-    assert vt.is_contiguous() and vt.dim() in (4, 5) and tuple(vt.shape[-4:-1]) == (B, H, 128)
-    ldvt = vt.shape[-1]
-    o_part = lse = None
-    if partial:
-        assert out is None
-        o_part = torch.empty((Sq * B, H * 128), dtype=torch.float32, device=q.device)
-        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-        ldo = o_part.stride(0)
-    else:
-        if out is None:
-            out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=q.device)
-        ldo = out.stride(0)
-    if softmax_scale is None:
-        softmax_scale = 1.0 / math.sqrt(128)
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None:
-        timer = HipTimer()
-        timer.start()
-    n_seg = vt.shape[0] if vt.dim() == 5 else 0
-    if n_seg:
-        assert Skv % n_seg == 0
+        return _attn_call("carry", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry=carry, kv_skip=kv_skip)
     if 0 < kv_dense < Skv or q_norm_weight is not None:
-        assert not partial and not n_seg and not variant, "the cross-attention form takes plain V^T, a bf16 output and the automatic kernel choice"
-        kd = int(kv_dense) if 0 < kv_dense < Skv else 0
-        _lib.check(lib.g3_cross_attn_fwd_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(q_norm_weight, "q_norm_weight") if q_norm_weight is not None else 0, float(q_norm_eps),
-                                              _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt, 128 * ldvt,
-                                              _dev(out, "out"), ldo * B, ldo, 128, Sq, Skv, kd, B, H, 128, float(softmax_scale), _stream()),
-                   "g3_cross_attn_fwd_bf16")
-        if timer is not None:
-            timer.stop()
-            _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=False, kv_dense=kd, q_norm=q_norm_weight is not None,
-                                                          kernel=lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, 4).decode()), timer))
-        return out
-    _lib.check(lib.g3_flash_attn_fwd_ex_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt, 128 * ldvt,
-                                             Skv // n_seg if n_seg else 0, B * H * 128 * ldvt if n_seg else 0,
-                                             0 if partial else _dev(out, "out"), _dev(o_part, "o_part", torch.float32) if partial else 0,
-                                             _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128,
-                                             float(softmax_scale), int(variant), _stream()), "g3_flash_attn_fwd_ex_bf16")
-    if timer is not None:
-        timer.stop()
-        # the kernel the launcher picked for THIS launch (per-call variant, else the library option in force)
-        _record_attn_timer(timer, Sq, Skv, B, H, partial, lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())
-    return (o_part, lse) if partial else out
-
-
-def _record_attn_timer(timer, Sq: int, Skv: int, B: int, H: int, partial: bool, kernel: str):
-    """The timer entry of a self-attention launch: ONE place for the name and the meta keys bench.py finds the launches by (flash_attn, self_attn_bounded)."""
-    _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, kernel=kernel), timer))
+        assert not partial and vt.dim() == 4 and not variant, "the cross-attention form takes plain V^T, a bf16 output and the automatic kernel choice"
+        return _attn_call("cross", q, k, vt, Sq, Skv, B, H, out, softmax_scale, 0, False, kv_dense=int(kv_dense) if 0 < kv_dense < Skv else 0,
+                          q_norm_weight=q_norm_weight, q_norm_eps=q_norm_eps)
+    return _attn_call("ex", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial)
 
 
 def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int, logit_bound: float,
@@ -547,50 +500,31 @@ def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: in
     The key-sharded forms of flash_attn - 5-D segmented V^T, carry=, kv_skip=, partial=True with `out` - go to g3_self_attn_fwd_bounded_cp_bf16:
     the no-max kernels where they apply (variant 11, the bound in range), else exactly flash_attn's carry call (variant 0, 4 or 11 only)."""
     if vt.dim() == 5 or carry is not None or kv_skip is not None or (partial and out is not None):
-        return _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip, logit_bound=float(logit_bound))
-    qr, qw, ldq = _rowmajor2d(q, "q")
-    kr, kw, ldk = _rowmajor2d(k, "k")
-    assert qr == Sq * B and kr == Skv * B and qw == H * 128 and kw == H * 128
-    assert vt.is_contiguous() and vt.dim() == 4 and tuple(vt.shape[:3]) == (B, H, 128)
-    ldvt = vt.shape[-1]
-    o_part = lse = None
-    if partial:
-        assert out is None
-        o_part = torch.empty((Sq * B, H * 128), dtype=torch.float32, device=q.device)
-        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-        ldo = o_part.stride(0)
-    else:
-        if out is None:
-            out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=q.device)
-        ldo = out.stride(0)
-    if softmax_scale is None:
-        softmax_scale = 1.0 / math.sqrt(128)
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None:
-        timer = HipTimer()
-        timer.start()
-    _lib.check(lib.g3_self_attn_fwd_bounded_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt, 128 * ldvt,
-                                                 0, 0, 0 if partial else _dev(out, "out"), _dev(o_part, "o_part", torch.float32) if partial else 0,
-                                                 _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128,
-                                                 float(softmax_scale), float(logit_bound), int(variant), _stream()), "g3_self_attn_fwd_bounded_bf16")
-    if timer is not None:
-        timer.stop()
-        _record_attn_timer(timer, Sq, Skv, B, H, partial, lib.g3_self_attn_kernel_name(Sq, Skv, B, H, float(logit_bound), int(variant)).decode())
-    return (o_part, lse) if partial else out
+        return _attn_call("bounded_cp", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry=carry, kv_skip=kv_skip, logit_bound=logit_bound)
+    return _attn_call("bounded", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, logit_bound=logit_bound)
 
 
-def _carry_kernel_name(plain: str) -> str:
-    """The CP instantiation g3_flash_attn_fwd_carry_bf16 launches in place of the plain kernel the launcher resolves to (attention.hip)."""
-    return {"flash_attn_fwd_w4b_kernel<true>": "flash_attn_fwd_w4b_carry_kernel<true>",
-            "flash_attn_fwd_v3_kernel<0, 6, 8, true>": "flash_attn_fwd_v3_kernel<2, 6, 8, true>",
-            "flash_attn_fwd_v3_kernel<1, 6, 8, false>": "flash_attn_fwd_v3_kernel<3, 6, 8, false>"}.get(plain, plain)
+# The launching entry points ops uses: (enum g3_attn_entry, symbol, its arguments by name in call order - the stream follows). g3_attn_plan_bf16 takes
+# the union (_ATTN_PLAN_ARGS), so the kernel a timer records is the dry run's answer for the very arguments launched.
+_AQ, _AK, _AVT = ("q", "q_row", "q_batch", "q_head"), ("k", "k_row", "k_batch", "k_head"), ("vt", "vt_row", "vt_batch", "vt_head", "vt_seg_len", "vt_seg_stride")
+_AOUT, _ASHAPE = ("o", "o_partial", "lse", "o_row", "o_batch", "o_head"), ("Sq", "Skv", "B", "H", "head_dim", "softmax_scale")
+_ACP = ("kv_skip_begin", "kv_skip_len", "carry_o", "carry_lse")
+_ATTN_ENTRIES = {
+    "cross": (2, "g3_cross_attn_fwd_bf16", _AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq", "Skv", "kv_dense") + _ASHAPE[2:]),
+    "ex": (3, "g3_flash_attn_fwd_ex_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("variant",)),
+    "bounded": (4, "g3_self_attn_fwd_bounded_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
+    "carry": (5, "g3_flash_attn_fwd_carry_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("variant",)),
+    "bounded_cp": (6, "g3_self_attn_fwd_bounded_cp_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("logit_bound", "variant")),
+}
+_ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] + ("logit_bound", "variant"))
 
 
-def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry, kv_skip, logit_bound=None):
-    """logit_bound None: g3_flash_attn_fwd_carry_bf16 (flash_attn); a float: g3_self_attn_fwd_bounded_cp_bf16 (self_attn_bounded)."""
+def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
+               logit_bound=0.0):
+    """The one marshaller of flash_attn and self_attn_bounded, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
+    launch and the kernel timer."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
-    skv_all = Skv + skip_len
+    skv_all = Skv + skip_len  # keys the operands hold
     qr, qw, ldq = _rowmajor2d(q, "q")
     kr, kw, ldk = _rowmajor2d(k, "k")
     assert qr == Sq * B and kr == skv_all * B and qw == H * 128 and kw == H * 128
@@ -618,29 +552,29 @@ def _flash_attn_carry(q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
         if l_c.dtype != torch.float32 or l_c.shape != (B, H, Sq) or not l_c.is_contiguous():
             raise ValueError(f"flash_attn: carry lse must be contiguous fp32 {(B, H, Sq)}")
         co, cl = _dev(o_c, "carry_o", torch.float32), _dev(l_c, "carry_lse", torch.float32)
-    if softmax_scale is None:
-        softmax_scale = 1.0 / math.sqrt(128)
+    a = dict(q=_dev(q, "q"), q_row=ldq * B, q_batch=ldq, q_head=128, q_norm_weight=_dev(q_norm_weight, "q_norm_weight") if q_norm_weight is not None else 0,
+             q_norm_eps=float(q_norm_eps), k=_dev(k, "k"), k_row=ldk * B, k_batch=ldk, k_head=128, vt=_dev(vt, "vt"), vt_row=ldvt, vt_batch=H * 128 * ldvt,
+             vt_head=128 * ldvt, vt_seg_len=skv_all // n_seg if n_seg else 0, vt_seg_stride=B * H * 128 * ldvt if n_seg else 0, kv_skip_begin=skip_begin,
+             kv_skip_len=skip_len, carry_o=co, carry_lse=cl, o=0 if partial else _dev(out, "out"), o_partial=_dev(out, "o_part", torch.float32) if partial else 0,
+             lse=_dev(lse, "lse", torch.float32) if partial else 0, o_row=ldo * B, o_batch=ldo, o_head=128, Sq=Sq, Skv=Skv, kv_dense=kv_dense, B=B, H=H,
+             head_dim=128, softmax_scale=float(1.0 / math.sqrt(128) if softmax_scale is None else softmax_scale), logit_bound=float(logit_bound), variant=int(variant))
+    entry_id, symbol, names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
     timer = None
     if _KERNEL_TIMERS is not None:
         timer = HipTimer()
         timer.start()
-    head = (_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, _dev(vt, "vt"), ldvt, H * 128 * ldvt,
-            128 * ldvt, skv_all // n_seg if n_seg else 0, B * H * 128 * ldvt if n_seg else 0, skip_begin, skip_len, co, cl,
-            0 if partial else _dev(out, "out"), _dev(out, "o_part", torch.float32) if partial else 0,
-            _dev(lse, "lse", torch.float32) if partial else 0, ldo * B, ldo, 128, Sq, Skv, B, H, 128, float(softmax_scale))
-    if logit_bound is None:
-        _lib.check(lib.g3_flash_attn_fwd_carry_bf16(*head, int(variant), _stream()), "g3_flash_attn_fwd_carry_bf16")
-    else:
-        _lib.check(lib.g3_self_attn_fwd_bounded_cp_bf16(*head, logit_bound, int(variant), _stream()), "g3_self_attn_fwd_bounded_cp_bf16")
+    _lib.check(getattr(lib, symbol)(*[a[n] for n in names], _stream()), symbol)
     if timer is not None:
         timer.stop()
-        if logit_bound is None:
-            kernel = _carry_kernel_name(lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, int(variant)).decode())
-        else:  # (the C entry point turns a skip at either end into a base offset: no CP form then)
-            cp_form = carry is not None or (skip_len > 0 and 0 < skip_begin < Skv)
-            kernel = lib.g3_self_attn_cp_kernel_name(Sq, Skv, B, H, logit_bound, int(variant), int(bool(n_seg)), int(cp_form)).decode()
-        _KERNEL_TIMERS.append(("flash_attn_fwd", dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial, carry=carry is not None, kv_skip=skip_len, kernel=kernel), timer))
+        # the kernel the launcher picked for THIS launch: every fallback, the per-call variant, else the library option in force
+        meta = dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial)
+        if entry == "cross":
+            meta.update(kv_dense=kv_dense, q_norm=q_norm_weight is not None)
+        elif entry in ("carry", "bounded_cp"):
+            meta.update(carry=carry is not None, kv_skip=skip_len)
+        meta["kernel"] = lib.g3_attn_plan_bf16(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
+        _KERNEL_TIMERS.append(("flash_attn_fwd", meta, timer))
     return (out, lse) if partial else out
 
 

@@ -133,7 +133,8 @@ int g3_flash_attn_fwd_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_
                            int B, int H, int head_dim, float softmax_scale, void* stream);
 
 /* Name of the kernel g3_flash_attn_fwd_bf16 launches for this problem under the current "attn_variant" option (0 = automatic choice
- * between the 8-wave and the one-wave-per-SIMD kernels): for profilers and bench.py's roofline line, never needed to run the op. */
+ * between the 8-wave and the one-wave-per-SIMD kernels): for profilers and bench.py's roofline line, never needed to run the op. From shapes only,
+ * i.e. for plain V^T and operands the 32-bit-offset kernels can address; g3_attn_plan_bf16 is the exact answer for a given call. */
 const char* g3_flash_attn_kernel_name(int Sq, int Skv, int B, int H);
 
 /* The CROSS-attention form of the same call (Attention.forward with a context: cal_qkv's to_q[1] norm + DotProductAttention, attention.py:247-297), two options:
@@ -173,6 +174,7 @@ int g3_flash_attn_fwd_ex_bf16(const void* q, int64_t q_row, int64_t q_batch, int
                               int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                               int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
                               int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, int variant, void* stream);
+/* g3_flash_attn_kernel_name with the per-call variant, from shapes only: g3_attn_plan_bf16 is the exact answer for a given call. */
 const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant);
 
 /* g3_flash_attn_fwd_ex_bf16 for callers that can BOUND the logits: logit_bound >= |q . k| * softmax_scale (natural units) for every query / key
@@ -182,7 +184,8 @@ const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int vari
  * bound above the limit, another kernel - the call IS g3_flash_attn_fwd_ex_bf16. An understated bound is a caller error (rows may overflow).
  * g3_self_attn_kernel_name reports the kernel such a call launches with PLAIN V^T (vt_seg_len == 0) and operands the 32-bit-offset kernels can
  * address; like g3_flash_attn_kernel_name_ex it sees shapes only: a call with segments runs what g3_flash_attn_fwd_ex_bf16 runs, and a V^T leading
- * dimension below ceil64(S_kv) or operands spanning more than 4 GiB demote either entry to the 64-bit-addressing kernel, whatever the name says. */
+ * dimension below ceil64(S_kv) or operands spanning more than 4 GiB demote either entry to the 64-bit-addressing kernel, whatever the name says:
+ * g3_attn_plan_bf16 is the exact answer for a given call. */
 int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
                                   int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                                   int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
@@ -218,13 +221,35 @@ int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, 
  * In every other case - bound 0, negative or above the limit, variant 4 - the call IS g3_flash_attn_fwd_carry_bf16: the same output bit for bit,
  * the same refusals (G3_ERR_ARG, nothing launched). g3_self_attn_fwd_bounded_bf16 keeps its own contract: a segmented call through it runs the max form.
  * g3_self_attn_cp_kernel_name: the kernel such a call launches, from shapes only (Skv = attended keys; cp_form != 0: a carry-in state, or a skip
- * with 0 < kv_skip_begin < S_kv and kv_skip_len > 0; segmented is informational - both V^T forms run the same kernels). */
+ * with 0 < kv_skip_begin < S_kv and kv_skip_len > 0; segmented is informational - both V^T forms run the same kernels); g3_attn_plan_bf16 is the
+ * exact answer for a given call. */
 int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
                                      int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
                                      int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o, const float* carry_lse,
                                      void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv, int B,
                                      int H, int head_dim, float softmax_scale, float logit_bound, int variant, void* stream);
 const char* g3_self_attn_cp_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant, int segmented, int cp_form);
+
+/* Dry run of the launching entry points above: the name of the kernel instantiation the call `entry` would launch with exactly these arguments -
+ * every check, normalisation and fallback of the real call (per-call variant and "attn_variant" option, split-KV partials, the cross-attention
+ * form, a short V^T leading dimension, operands beyond 4 GiB, carry / skip, the logit bound) - or NULL where the call would be refused, with
+ * g3_last_error() set exactly as the call sets it. Nothing is launched, no HIP call is made and no pointer is dereferenced (pointers are tested for
+ * NULL and alignment only). The arguments are the union of the entries' arguments (no stream); those `entry` does not take are ignored. */
+enum g3_attn_entry {
+    G3_ATTN_ENTRY_FWD = 0,        /* g3_flash_attn_fwd_bf16 */
+    G3_ATTN_ENTRY_KVSEG = 1,      /* g3_flash_attn_fwd_kvseg_bf16 */
+    G3_ATTN_ENTRY_CROSS = 2,      /* g3_cross_attn_fwd_bf16 */
+    G3_ATTN_ENTRY_EX = 3,         /* g3_flash_attn_fwd_ex_bf16 */
+    G3_ATTN_ENTRY_BOUNDED = 4,    /* g3_self_attn_fwd_bounded_bf16 */
+    G3_ATTN_ENTRY_CARRY = 5,      /* g3_flash_attn_fwd_carry_bf16 */
+    G3_ATTN_ENTRY_BOUNDED_CP = 6  /* g3_self_attn_fwd_bounded_cp_bf16 */
+};
+const char* g3_attn_plan_bf16(int entry, const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* q_norm_weight, float q_norm_eps,
+                              const void* k, int64_t k_row, int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch,
+                              int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                              const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
+                              int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant);
+
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);

@@ -700,6 +700,48 @@ def test_flash_attn_per_call_variant_leaves_global_option_alone():
     assert _rel_l2(a, b) < 6e-3
 
 
+@pytest.mark.parametrize("case,kernel", [("partial_ragged_v11", "flash_attn_fwd_v3_kernel<1, 6, 8, false>"), ("short_vt_ld", "flash_attn_fwd_v2_kernel<1>"),
+                                         ("cross_tail_qnorm", "flash_attn_fwd_v3_kernel<1, 6, 8, false>")])
+def test_kernel_timer_records_the_kernel_that_ran_after_a_launcher_fallback(case, kernel):
+    """The `kernel` of a kernel-timer entry is the dry run's answer (g3_attn_plan_bf16) for the arguments launched, launcher fallbacks included:
+    split-KV partials on ragged keys under variant 11 (-> w4 -> the 8-wave kernel), a V^T leading dimension of ceil8 but below ceil64 of the keys
+    (-> the 64-bit-addressing kernel), the cross-attention form (-> the v3 kernels). Outputs against the fp32 softmax at test_flash_attn's bar."""
+    from gen3c_amd import ops
+    from oracle import dit_oracle
+    dev = _dev()
+    Sq, B, H = 200, 2, 2
+    Skv = 512 if case == "cross_tail_qnorm" else 100
+    g = torch.Generator(device=dev).manual_seed(len(case))
+    q = torch.randn(Sq * B, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    k = torch.randn(Skv * B, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    v = torch.randn(Skv * B, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    q_ref = q
+    ops.enable_kernel_timers(True)
+    try:
+        if case == "partial_ragged_v11":
+            out, _ = ops.flash_attn(q, k, ops.transpose_v(v, Skv, B, H), Sq, Skv, B, H, partial=True, variant=11)
+        elif case == "short_vt_ld":
+            vt = ops.transpose_v(v, Skv, B, H)[..., :104].contiguous()  # (the zero tail [100, 104) included)
+            out = ops.flash_attn(q, k, vt, Sq, Skv, B, H)
+        else:
+            k[64 * B:] = 0
+            v[64 * B:] = 0
+            w = (torch.rand(128, device=dev, generator=g) + 0.5).to(torch.bfloat16)
+            out = ops.flash_attn(q, k, ops.transpose_v(v, Skv, B, H), Sq, Skv, B, H, kv_dense=64, q_norm_weight=w)
+            q_ref = dit_oracle.te_rmsnorm(q.float().reshape(Sq, B, H, 128), w.float()).reshape(Sq * B, H * 128)
+        torch.cuda.synchronize()
+        timers = ops.collected_kernel_timers()
+    finally:
+        ops.enable_kernel_timers(False)
+    (name, meta, _), = [t for t in timers if t[0] == "flash_attn_fwd"]
+    print(f"[attn timer {case}] kernel={meta['kernel']}")
+    assert meta["kernel"] == kernel
+    ref = _attn_ref(q_ref, k, v, Sq, Skv, B, H)
+    _report(f"attn fallback {case}", out, ref)
+    torch.testing.assert_close(out.float(), ref, rtol=2e-2, atol=2e-2)
+    assert _rel_l2(out, ref) < 1e-2
+
+
 def test_hip_dot_product_attention_operator_seam():
     """SURVEY 8b "Attention operator": the reference's Attention module calls attn_op(q, k, v, core_attention_bias_type="no_bias",
     core_attention_bias=None) on sbhd tensors and expects [S, B, H*d] (attention.py:282-297); general_dit.py:541 hands the operator a
