@@ -16,6 +16,16 @@ vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int, C.c_float
 # status codes of include/gen3c_hip.h
 G3_OK, G3_ERR_ARG, G3_ERR_LAUNCH, G3_ERR_RESOURCE = 0, 1, 2, 3
 
+
+class GemmCall(C.Structure):
+    """g3_gemm_call of include/gen3c_hip.h, field for field: the argument of the dry run g3_gemm_plan_bf16."""
+    _fields_ = ([("entry", i32), ("A", vp), ("lda", i64), ("W", vp), ("ldw", i64), ("C", vp), ("ldc", i64), ("M", i32), ("N", i32), ("K", i32),
+                 ("epilogue", i32), ("gate", vp), ("gate_rows", i32), ("ldg", i64), ("residual", vp), ("ldr", i64),
+                 ("n_q", i32), ("n_k", i32), ("norm_q", vp), ("norm_k", vp), ("cos_table", vp), ("sin_table", vp), ("B", i32), ("eps", f32), ("vt", vp),
+                 ("vt_ld", i64)] + [(n, i32) for n in "Ti Hi Wi To Ho Wo kt kh kw st sh sw ot oh ow".split()] +
+                [("gn_stats", vp), ("gn_rows", i32), ("stream", vp)])
+
+
 # name -> argtypes (restype is int unless listed in _RESTYPES). Mirrors include/gen3c_hip.h one-to-one; the
 # CPU test tests/test_abi.py checks that every symbol declared in the header is listed here and exported.
 SIGNATURES = {
@@ -31,6 +41,7 @@ SIGNATURES = {
     "g3_flash_attn_fwd_kvseg_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, vp, i64, i64, i64, i32, i32, i32,
                                      i32, i32, f32, vp],
     "g3_gemm_kernel_name": [i32, i32, i32, i32],
+    "g3_gemm_plan_bf16": [C.POINTER(GemmCall), i32, C.POINTER(i32), C.POINTER(C.c_uint)],
     "g3_quant_mxfp8_bf16": [vp, i64, vp, i64, vp, i64, i32, i32, vp],
     "g3_gemm_mxfp8_nt": [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i32, i32, i32, i32, vp, i32, i64, vp, i64, vp],
     "g3_gemm_mxfp8_kernel_name": [i32, i32, i32, i32],
@@ -101,7 +112,7 @@ SIGNATURES = {
     "g3_edm_prepare_input_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     "g3_edm_cfg_euler_step_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
 }
-_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
+_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
              "g3_warp_windows_workspace_bytes": C.c_size_t, "g3_render_workspace_bytes": C.c_size_t}
 
 

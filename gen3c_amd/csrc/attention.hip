@@ -24,7 +24,6 @@
 //     K/V^T panels.
 #include "common.hpp"
 #include <stdlib.h>
-#include <mutex>
 #include <type_traits>
 
 namespace {
@@ -1232,20 +1231,8 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
 static int attn_launch(const AttnCall& c) {
     AttnPlan plan;
     if (int rc = attn_plan(c, plan)) return rc;
-    static bool attr_set[64] = {};  // per device: hipFuncSetAttribute applies to the current device only
-    static std::mutex attr_mu;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipGetDevice failed");
-    {
-        std::lock_guard<std::mutex> attr_lock(attr_mu);
-        if (!attr_set[dev_id]) {
-            for (const AttnKernel& kern : attn_kernels) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern.fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATTN_SMEM);
-                if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "flash_attn: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            }
-            attr_set[dev_id] = true;
-        }
-    }
+    static bool granted[AK_COUNT][G3_MAX_DEVICES] = {};
+    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(plan.kernel->fn), (int)ATTN_SMEM, granted[plan.kernel - attn_kernels], "flash_attn")) return rc;
     hipLaunchKernelGGL(plan.kernel->fn, plan.grid, dim3(plan.kernel->threads), ATTN_SMEM, (hipStream_t)c.stream, plan.p);
     return g3_check_launch("g3_flash_attn_fwd_bf16");
 }

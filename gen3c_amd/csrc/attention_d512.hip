@@ -375,14 +375,8 @@ extern "C" int g3_spatial_attn_d512_bf16(const void* q, const void* k, const voi
     p.scale_log2 = softmax_scale * 1.44269504088896340736f;
     p.xcd_frames = (frames % 8 == 0) ? frames / 8 : 0;
     const size_t smem = (size_t)(KV5 * D5 + D5 * KV5 + 4 * 4 * 64 * 8) * sizeof(bf16_t) + BQ5 * sizeof(float) + 4 * sizeof(int);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&spatial_attn_d512_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_RESOURCE, "g3_spatial_attn_d512_bf16: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set[dev] = true;
-    }
+    static bool granted[G3_MAX_DEVICES] = {};
+    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(&spatial_attn_d512_kernel), (int)smem, granted, "g3_spatial_attn_d512_bf16", G3_ERR_RESOURCE)) return rc;
     hipLaunchKernelGGL(spatial_attn_d512_kernel, dim3((unsigned)(frames * p.nqb)), dim3(NT5), smem, (hipStream_t)stream, p);
     return g3_check_launch("g3_spatial_attn_d512_bf16");
 }

@@ -1,6 +1,7 @@
 // Shared device helpers for the gfx950 (MI355X / CDNA4) kernels of the GEN3C denoising path.
 // Wave = 64 lanes everywhere. No portability shims: this code only targets gfx950.
 #pragma once
+#include <mutex>
 #include <type_traits>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +27,22 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 int g3_set_error(int code, const char* fmt, ...);
 int g3_check_launch(const char* what);
 
+// Dynamic LDS beyond 64 KiB must be granted per kernel (hipFuncAttributeMaxDynamicSharedMemorySize), and the grant holds for the CURRENT DEVICE only: every launcher asks
+// through here, once per (kernel, device), on the kernel's first launch on that device. granted: that kernel's own flags. G3_OK, or the error set as "<what>: ...".
+constexpr int G3_MAX_DEVICES = 64;
+inline int g3_grant_dynamic_lds(const void* kernel, int bytes, bool (&granted)[G3_MAX_DEVICES], const char* what, int refused = G3_ERR_LAUNCH) {
+    static std::mutex mu;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= G3_MAX_DEVICES) return g3_set_error(G3_ERR_LAUNCH, "%s: hipGetDevice failed", what);
+    std::lock_guard<std::mutex> lock(mu);
+    if (!granted[dev]) {
+        hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) return g3_set_error(refused, "%s: hipFuncSetAttribute: %s", what, hipGetErrorString(e));
+        granted[dev] = true;
+    }
+    return G3_OK;
+}
+
 // runtime switches for A/B measurements (g3_set_option); defaults come from the environment on first use
 extern int g3_opt_gemm_regstage;  // 1: register-staged GEMM even when the direct-to-LDS path applies
 extern int g3_opt_gemm_rowmajor_tiles;  // 1: plain row-major tile order inside an XCD run (A/B); 0: 4-token-tile super-rows
@@ -36,7 +53,7 @@ extern int g3_opt_gemm_deferred;        // 1 (default): persistent one-wave-per-
 extern int g3_opt_gemm_deferred_grid;    // tests: workgroups of the tile loop of the deferred-epilogue GEMM (0 = one per CU)
 extern int g3_opt_gemm_tokens_first;    // gemm_w4e.hpp: LDS-DMA piece order (0 weight rows get the two-tile lead, 1 token rows, 2 = default: token rows where N <= 4096)
 extern int g3_opt_conv_w4;              // tokenizer convolutions on the one-wave-per-SIMD kernel where it applies (default 1)
-extern int g3_opt_gemm_pingpong;        // plain K%64==0 GEMMs: 2 (default) / 1 = phase-staggered ping-pong kernel with 2 / 4 phases per K tile, 0 = classic
+extern int g3_opt_gemm_pingpong;        // plain K%64==0 GEMMs: 3 (default) = one wave per SIMD (gemm_w4.hpp, gemm_w4e.hpp) where it applies, else as 2; 2 / 1 = phase-staggered ping-pong kernel with 2 / 4 phases per K tile; 0 = classic
 extern int g3_opt_gemm_wide_store;      // 1 (default): LDS-transposed full-line epilogue when the operands allow 16-byte rows
 extern int g3_opt_render_exclusive;     // 1 (needs render_fused; default 0): every tile's destination rectangle is published by a pre-pass and texels a single tile reaches are resolved inside the splat
 extern int g3_opt_render_full_extent;   // 1 (default): g3_render_items_f32's tiles publish their unclamped destination rectangle and the gather pass reads the dense accumulator per texel, not per item

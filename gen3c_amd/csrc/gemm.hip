@@ -577,44 +577,57 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_nt_pp_kernel(GemmParams
     if (p.wide_store) store_tile_lds<EPI>(p, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
     else store_tile<EPI>(p, acc, m0 + m_w0, n0 + n_w0, l31, g);
 }
-
-template <int EPI, int PH, bool CONV>
-int launch_pp(const GemmParams& p, hipStream_t stream, const char* what) {
-    const size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(bf16_t);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_pp_kernel<EPI, PH, CONV>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_bf16_nt_pp_kernel<EPI, PH, CONV>), dim3(p.tiles_m * p.tiles_n), dim3(NTHREADS), smem, stream, p);
-    return g3_check_launch(what);
-}
-
-template <int EPI, bool STAGE_GLDS, bool CONV, bool PIN>
-int launch_variant(const GemmParams& p, hipStream_t stream, const char* what) {
-    const size_t smem = (size_t)2 * (BM + BN) * BK * sizeof(bf16_t);  // 128 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_kernel<EPI, STAGE_GLDS, CONV, PIN>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    const int nblk = p.tiles_m * p.tiles_n;
-    hipLaunchKernelGGL((gemm_bf16_nt_kernel<EPI, STAGE_GLDS, CONV, PIN>), dim3(nblk), dim3(NTHREADS), smem, stream, p);
-    return g3_check_launch(what);
-}
-
 #include "gemm_w4.hpp"
 #include "gemm_w4_conv.hpp"
 #include "gemm_w4e.hpp"
 
-static int device_cu_count() {  // cached per device (sizes the persistent grid of gemm_w4e.hpp)
-    static int n_cu[64] = {};
+/* ---- host side: every public entry point fills ONE call record (g3_gemm_call, gen3c_hip.h); gemm_plan turns it into a refusal or into the kernel's
+ * parameters, its row of the ONE kernel table, the grid and the entry's follow-up launches; gemm_launch launches that. g3_gemm_plan_bf16 and
+ * g3_gemm_kernel_name ask the same code. ------------------------------------------------------------------------------------------------------ */
+
+// The kernel table: one row per instantiation = family x epilogue. The reported names, the dynamic-LDS grant and the launch all come from here.
+struct GemmKernel { const char* name; void (*fn)(GemmParams); int threads, lds; const char* family; };
+constexpr int GEMM_LDS_BYTES = 2 * (BM + BN) * BK * (int)sizeof(bf16_t);  // 128 KiB: two stages of both operand tiles (= 2 * GW4_STAGE_BYTES)
+// epilogue lists, as the numerals of the EPI_* codes so that a row's name is the instantiation's own; a family's rows follow its list
+#define G3_EPI_ALL(X, ...) X(0, __VA_ARGS__) X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__)
+#define G3_EPI_ALL_QK(X, ...) G3_EPI_ALL(X, __VA_ARGS__) X(5, __VA_ARGS__)
+#define G3_EPI_DEFERRED(X, ...) X(0, __VA_ARGS__) X(1, __VA_ARGS__) X(2, __VA_ARGS__)
+#define G3_EPI_CONV(X, ...) X(0, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__)
+// F(row id stem, epilogue list, threads, LDS bytes, family as g3_gemm_kernel_name reports it, kernel template, its arguments behind EPI)
+#define G3_GEMM_FAMILIES(F) \
+    F(GK_W4E, DEFERRED, GW4_THREADS, GW4E_LDS_BYTES, "gemm_bf16_nt_w4e_kernel<EPI>", gemm_bf16_nt_w4e_kernel, false) \
+    F(GK_W4E_TF, DEFERRED, GW4_THREADS, GW4E_LDS_BYTES, "gemm_bf16_nt_w4e_kernel<EPI>", gemm_bf16_nt_w4e_kernel, true) \
+    F(GK_W4, ALL_QK, GW4_THREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_w4_kernel<EPI>", gemm_bf16_nt_w4_kernel, false) \
+    F(GK_W4_PERSIST, ALL, GW4_THREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_w4_kernel<EPI>", gemm_bf16_nt_w4_kernel, true) \
+    F(GK_W4_CONV, CONV, GW4_THREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_w4_conv_kernel<EPI>", gemm_bf16_nt_w4_conv_kernel) \
+    F(GK_PP2, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_pp_kernel<EPI, 2, false>", gemm_bf16_nt_pp_kernel, 2, false) \
+    F(GK_PP2_CONV, CONV, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_pp_kernel<EPI, 2, true>", gemm_bf16_nt_pp_kernel, 2, true) \
+    F(GK_PP4, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_pp_kernel<EPI, 4, false>", gemm_bf16_nt_pp_kernel, 4, false) \
+    F(GK_REG, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, false, false, PIN>", gemm_bf16_nt_kernel, false, false, false) \
+    F(GK_REG_PIN, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, false, false, PIN>", gemm_bf16_nt_kernel, false, false, true) \
+    F(GK_GLDS, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, true, false, PIN>", gemm_bf16_nt_kernel, true, false, false) \
+    F(GK_GLDS_PIN, ALL, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, true, false, PIN>", gemm_bf16_nt_kernel, true, false, true) \
+    F(GK_REG_CONV, CONV, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, false, true, PIN>", gemm_bf16_nt_kernel, false, true, false) \
+    F(GK_REG_CONV_PIN, CONV, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, false, true, PIN>", gemm_bf16_nt_kernel, false, true, true) \
+    F(GK_GLDS_CONV, CONV, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, true, true, PIN>", gemm_bf16_nt_kernel, true, true, false) \
+    F(GK_GLDS_CONV_PIN, CONV, NTHREADS, GEMM_LDS_BYTES, "gemm_bf16_nt_kernel<EPI, true, true, PIN>", gemm_bf16_nt_kernel, true, true, true)
+#define G3_STR(...) #__VA_ARGS__
+#define G3_GEMM_IDS(ID, EPIS, ...) G3_EPI_##EPIS(G3_GEMM_ID, ID)
+#define G3_GEMM_ID(E, ID) ID##_##E,
+#define G3_GEMM_ROWS(ID, EPIS, ...) G3_EPI_##EPIS(G3_GEMM_ROW, __VA_ARGS__)
+#define G3_GEMM_ROW(E, THREADS, LDS, FAMILY, KERNEL, ...) {G3_STR(KERNEL<E, ##__VA_ARGS__>), &KERNEL<E, ##__VA_ARGS__>, THREADS, LDS, FAMILY},
+enum GemmKernelId { G3_GEMM_FAMILIES(G3_GEMM_IDS) GK_COUNT };  // GK_<family>_<epilogue>; a family's first row is GK_<family>_0
+const GemmKernel gemm_kernels[GK_COUNT] = {G3_GEMM_FAMILIES(G3_GEMM_ROWS)};
+#undef G3_GEMM_IDS
+#undef G3_GEMM_ID
+#undef G3_GEMM_ROWS
+#undef G3_GEMM_ROW
+
+int device_cu_count() {  // cached per device (sizes the persistent grids); 0 without a device
+    static int n_cu[G3_MAX_DEVICES] = {};
     static std::mutex mu;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= G3_MAX_DEVICES) return 0;
     std::lock_guard<std::mutex> lock(mu);
     if (!n_cu[dev]) {
         int cus = 0;
@@ -626,33 +639,167 @@ static int device_cu_count() {  // cached per device (sizes the persistent grid 
 
 // CONV on the one-wave-per-SIMD kernel (gemm_w4_conv.hpp): whole 64-channel tiles, >= 2 K tiles, K * 2 bytes inside the zero page,
 // <= 32 spatial taps (bit masks), full-line epilogue, activation span addressable with 32-bit row * lda products
-static bool conv_w4_applies(const GemmParams& p) {
+bool conv_w4_applies(const GemmParams& p) {
     const int64_t in_rows = (int64_t)p.cv.Ti * p.cv.Hi * p.cv.Wi;
     return g3_opt_conv_w4 && (p.K % BK) == 0 && !g3_opt_gemm_regstage && p.wide_store && (p.K / BK) * p.cv.ntaps >= 2 && p.K * 2 <= G3_ZERO_PAGE_BYTES &&
            p.cv.kh * p.cv.kw <= 32 && in_rows < (1ll << 31) && p.lda * 2 < (1ll << 31) && p.cv.w_tap_stride * 2 < (1ll << 32);
 }
 
-template <int EPI, bool CONV>
-int launch(const GemmParams& p, hipStream_t stream, const char* what) {
+// The whole kernel choice: the FIRST row of the family that runs p with epilogue epi (the row itself is that plus the epilogue's place in the family's
+// list) and the grid. Reads the shapes, strides and wide_store of p and the options only.
+int gemm_choose(const GemmParams& p, int epi, bool conv, int n_cu, int& grid) {
     const bool glds = (p.K % BK) == 0 && !g3_opt_gemm_regstage;
-    if constexpr (CONV && (EPI == EPI_NONE || EPI == EPI_BIAS || EPI == EPI_BIAS_RESIDUAL)) {
-        if (conv_w4_applies(p)) return launch_w4_conv<EPI>(p, stream, what);
-    }
-    if constexpr (!CONV && (EPI == EPI_NONE || EPI == EPI_GELU || EPI == EPI_GATED_RESIDUAL)) {  // persistent form with the deferred epilogue (gemm_w4e.hpp)
-        if (glds && g3_opt_gemm_pingpong == 3) {
-            const int n_cu = device_cu_count();
-            if (w4e_applies(p, EPI, n_cu)) return launch_w4e<EPI>(p, stream, what, n_cu);
+    const int nblk = p.tiles_m * p.tiles_n;
+    grid = nblk;
+    if (conv) {
+        if (conv_w4_applies(p)) return GK_W4_CONV_0;
+    } else if (glds && g3_opt_gemm_pingpong == 3) {
+        // persistent forms: one workgroup per CU (a multiple of 8 keeps a workgroup's tiles on its XCD's band of the XCD-aware order)
+        const int grid_cu = (n_cu / 8) * 8;
+        if ((epi == EPI_NONE || epi == EPI_GELU || epi == EPI_GATED_RESIDUAL) && w4e_applies(p, epi, n_cu)) {  // deferred epilogue (gemm_w4e.hpp)
+            // (tests: g3_set_option("gemm_deferred_grid", g) runs the tile loop on g workgroups - any multiple of 8 that leaves every workgroup a tile -
+            // to walk long and uneven tile lists; 0 = one workgroup per CU)
+            const int g = g3_opt_gemm_deferred_grid;
+            grid = (g >= 8 && (g % 8) == 0 && g <= nblk) ? g : grid_cu;
+            // piece order, g3_set_option("gemm_tokens_first", 0 / 1 / 2): never / always / (default) where few feature tiles share a token panel (N <= 4096: its
+            // rows are fetched from HBM by the first of at most 16 workgroups and everybody waits for them) - measured (profiles/r5_gemm_tokens_first_ab.txt):
+            // out-projection +1 %, MLP-down +1.5 %; QKV (N = 12 288) -3.5 %, MLP-up (N = 16 384) -1 % -> those keep the weights-first order
+            const bool tf = g3_opt_gemm_tokens_first == 1 || (g3_opt_gemm_tokens_first == 2 && p.N <= 4096);
+            return tf ? GK_W4E_TF_0 : GK_W4E_0;
+        }
+        if (p.wide_store && p.K >= 2 * BK) {  // one wave per SIMD (gemm_w4.hpp): whole 64-wide K tiles, at least two, full-line epilogue
+            // persistent only where a workgroup gets at least two tiles (the norm / RoPE epilogue's tables do not fit beside the tile state: no such form)
+            if (epi != EPI_QK_NORM_ROPE && g3_opt_gemm_persistent && grid_cu >= 8 && nblk >= 2 * grid_cu) {
+                grid = grid_cu;
+                return GK_W4_PERSIST_0;
+            }
+            return GK_W4_0;
         }
     }
-    if constexpr (!CONV) {  // one wave per SIMD (gemm_w4.hpp): whole 64-wide K tiles, at least two, full-line epilogue
-        if (glds && g3_opt_gemm_pingpong == 3 && p.wide_store && p.K >= 2 * BK) return launch_w4<EPI>(p, stream, what);
+    if (glds && g3_opt_gemm_pingpong >= 2) return conv ? GK_PP2_CONV_0 : GK_PP2_0;
+    if (!conv && glds && g3_opt_gemm_pingpong) return GK_PP4_0;
+    static const GemmKernelId classic[2][2][2] = {{{GK_REG_PIN_0, GK_REG_0}, {GK_GLDS_PIN_0, GK_GLDS_0}},  // [conv][glds][unpinned]
+                                                  {{GK_REG_CONV_PIN_0, GK_REG_CONV_0}, {GK_GLDS_CONV_PIN_0, GK_GLDS_CONV_0}}};
+    return classic[conv][glds][g3_opt_gemm_unpinned != 0];
+}
+
+struct GemmPlan { GemmParams p; int row, grid; unsigned follow_up; const char* what; };  // what: the name g3_check_launch reports
+
+// Every check of a call, the one fill of GemmParams and the kernel choice; G3_OK and a filled plan, or the refusal (g3_set_error). No HIP call, and no
+// operand is dereferenced: n_cu comes from the caller.
+int gemm_plan(const g3_gemm_call& call, int n_cu, GemmPlan& plan) {
+    g3_gemm_call c = call;  // (normalised below: what the entry does not take, and what it derives)
+    const bool conv = c.entry == G3_GEMM_ENTRY_CONV || c.entry == G3_GEMM_ENTRY_CONV_GNSTATS, qk = c.entry == G3_GEMM_ENTRY_QK_NORM_ROPE;
+    auto at = [](const void* ptr) { return (uintptr_t)ptr; };
+    if (qk) {
+        if (!c.A || !c.W || !c.C) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: null operand");
+        if (c.M <= 0 || c.N <= 0 || c.K <= 0 || c.B <= 0 || (c.M % c.B))
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: bad shape M=%d N=%d K=%d B=%d", c.M, c.N, c.K, c.B);
+        if (c.n_q < 0 || c.n_k < 0 || (c.n_q % 128) || (c.n_k % 128) || c.n_q + c.n_k > c.N || (c.N % 128))
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: q / k feature ranges must be whole 128-wide heads inside N (n_q=%d n_k=%d N=%d)", c.n_q, c.n_k, c.N);
+        if ((c.n_q && !c.norm_q) || (c.n_k && !c.norm_k)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: missing norm weight");
+        if ((c.cos_table == nullptr) != (c.sin_table == nullptr)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: need both cos and sin tables or neither");
+        if ((c.K & 7) || (c.lda & 7) || (c.ldw & 7) || (c.ldc & 7)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: K, lda, ldw, ldc must be multiples of 8");
+        if (((at(c.A) | at(c.W) | at(c.C)) & 15) || ((at(c.norm_q) | at(c.norm_k)) & 15) || ((at(c.cos_table) | at(c.sin_table)) & 15))
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: operands must be 16-byte aligned");
+        if (c.vt && (c.N - c.n_q - c.n_k <= 0 || (c.vt_ld & 7) || c.vt_ld < c.M / c.B || (at(c.vt) & 15)))
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: V^T destination needs v heads, vt_ld %% 8 == 0, vt_ld >= S and 16-byte alignment");
+        c.epilogue = EPI_QK_NORM_ROPE; c.gate = c.residual = nullptr; c.ldg = c.ldr = 0;
+    } else if (conv) {
+        if (c.entry == G3_GEMM_ENTRY_CONV_GNSTATS) {
+            if (!c.gn_stats || c.gn_rows <= 0 || (at(c.gn_stats) & 7)) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_gnstats_bf16: bad statistics buffer");
+            if (((int64_t)c.To * c.Ho * c.Wo) % c.gn_rows) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_gnstats_bf16: gn_rows_per_frame must divide the output rows");
+        } else {
+            c.gn_stats = nullptr;
+        }
+        if (!c.A || !c.W || !c.C) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: null operand");
+        if (c.K <= 0 || c.N <= 0 || (c.K & 7) || (c.lda & 7) || (c.ldw & 7) || (c.N & 3) || (c.ldc & 3))
+            return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: need K, ld_in, ldw %% 8 == 0 and N, ld_out %% 4 == 0 (K=%d N=%d)", c.K, c.N);
+        if (c.Ti <= 0 || c.Hi <= 0 || c.Wi <= 0 || c.To <= 0 || c.Ho <= 0 || c.Wo <= 0 || c.kt <= 0 || c.kh <= 0 || c.kw <= 0 || c.st <= 0 || c.sh <= 0 || c.sw <= 0)
+            return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: bad geometry");
+        if ((int64_t)c.To * c.Ho * c.Wo > 0x7fffffffLL) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: too many output positions");
+        if (((at(c.A) | at(c.W)) & 15) || (at(c.C) & 7)) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: misaligned pointer");
+        if (c.residual && ((c.ldr & 3) || (at(c.residual) & 7))) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: misaligned residual");
+        if (c.residual && !c.gate) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: residual without bias is not instantiated");
+        c.M = c.To * c.Ho * c.Wo; c.epilogue = c.residual ? EPI_BIAS_RESIDUAL : c.gate ? EPI_BIAS : EPI_NONE; c.ldg = 0;
+    } else {
+        const bool gate_ok = c.gate && !(c.ldg & 3) && !(at(c.gate) & 7), gate_residual_ok = gate_ok && c.residual && !(c.ldr & 3) && !(at(c.residual) & 7);
+        if (!c.A || !c.W || !c.C) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: null operand");
+        if (c.M <= 0 || c.N <= 0 || c.K <= 0) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bad shape M=%d N=%d K=%d", c.M, c.N, c.K);
+        if ((c.K & 7) || (c.lda & 7) || (c.ldw & 7) || (c.N & 3) || (c.ldc & 3))
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: need K,lda,ldw %% 8 == 0 and N,ldc %% 4 == 0 (K=%d lda=%lld ldw=%lld N=%d ldc=%lld)",
+                                c.K, (long long)c.lda, (long long)c.ldw, c.N, (long long)c.ldc);
+        if ((at(c.A) | at(c.W)) & 15) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: A/W must be 16-byte aligned");
+        if (at(c.C) & 7) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: C must be 8-byte aligned");
+        if (c.epilogue == EPI_GATED_RESIDUAL && !gate_residual_ok)
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: gated-residual epilogue needs 8-byte aligned gate+residual");
+        if (c.epilogue == EPI_BIAS && !gate_ok) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bias epilogue needs bias");
+        if (c.epilogue == EPI_BIAS_RESIDUAL && !gate_residual_ok)
+            return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bias-residual epilogue needs 8-byte aligned bias+residual");
+        if (c.epilogue < EPI_NONE || c.epilogue > EPI_BIAS_RESIDUAL) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: unknown epilogue %d", c.epilogue);
     }
-    if (glds && g3_opt_gemm_pingpong >= 2) return launch_pp<EPI, 2, CONV>(p, stream, what);
-    if constexpr (!CONV) {
-        if (glds && g3_opt_gemm_pingpong) return launch_pp<EPI, 4, false>(p, stream, what);
+    if (c.entry != G3_GEMM_ENTRY_NT) c.gate_rows = 1;
+
+    GemmParams& p = plan.p;
+    p = GemmParams{};
+    p.A = (const bf16_t*)c.A; p.lda = c.lda; p.W = (const bf16_t*)c.W; p.ldw = c.ldw; p.C = (bf16_t*)c.C; p.ldc = c.ldc;
+    p.M = c.M; p.N = c.N; p.K = c.K;
+    p.gate = (const bf16_t*)c.gate; p.gate_rows = c.gate_rows > 0 ? c.gate_rows : 1; p.ldg = c.ldg;
+    p.R = (const bf16_t*)c.residual; p.ldr = c.ldr;
+    p.tiles_m = (c.M + BM - 1) / BM; p.tiles_n = (c.N + BN - 1) / BN;
+    p.tile_order_rowmajor = g3_opt_gemm_rowmajor_tiles;
+    p.wide_store = g3_opt_gemm_wide_store && !(c.N & 7) && !(c.ldc & 7) && !(at(c.C) & 15) && (!c.gate || (!(c.ldg & 7) && !(at(c.gate) & 15))) &&
+                   (!c.residual || (!(c.ldr & 7) && !(at(c.residual) & 15)));
+    if (conv) p.cv = ConvGeom{c.To, c.Ho, c.Wo, c.Ti, c.Hi, c.Wi, c.kt, c.kh, c.kw, c.st, c.sh, c.sw, c.ot, c.oh, c.ow, c.kt * c.kh * c.kw, (int64_t)c.N * c.ldw, g3_opt_conv_w4 != 2};
+
+    const int first = gemm_choose(p, c.epilogue, conv, n_cu, plan.grid);
+    plan.follow_up = 0;
+    plan.what = qk ? "g3_gemm_qk_norm_rope_bf16" : conv ? "g3_conv3d_cl_bf16" : "g3_gemm_bf16_nt";
+    if (qk) {
+        // The norm / RoPE epilogue exists on the one-wave-per-SIMD kernel only. Where the choice is another family it is the plain entry's for these operands (the
+        // deferred form applies to nothing the one-wave kernel does not): that kernel without epilogue, then the standalone passes over C in place.
+        const bool fused = first == GK_W4_0, vt_fused = fused && c.vt && (c.B == 1 || c.B == 2 || c.B == 4);
+        const int S = c.M / c.B, n_v = c.N - c.n_q - c.n_k;
+        if (fused) {
+            p.nw_q = (const bf16_t*)c.norm_q; p.nw_k = (const bf16_t*)c.norm_k; p.rope_cos = c.cos_table; p.rope_sin = c.sin_table;
+            p.n_q = c.n_q; p.n_k = c.n_k; p.rope_B = c.B; p.rms_eps = c.eps;
+            p.vt = vt_fused ? (bf16_t*)c.vt : nullptr; p.vt_ld = c.vt_ld; p.vt_batch = (int64_t)(n_v / 128) * 128 * c.vt_ld; p.vt_S = S;
+        } else {
+            c.epilogue = EPI_NONE;
+            plan.what = "g3_gemm_bf16_nt";
+            plan.follow_up = (c.n_q ? G3_GEMM_THEN_NORM_Q : 0) | (c.n_k ? G3_GEMM_THEN_NORM_K : 0);
+        }
+        if (c.vt && !vt_fused) plan.follow_up |= G3_GEMM_THEN_VT;  // (the fused form leaves C's v columns unwritten only where it writes V^T)
     }
-    if (g3_opt_gemm_unpinned) return glds ? launch_variant<EPI, true, CONV, false>(p, stream, what) : launch_variant<EPI, false, CONV, false>(p, stream, what);
-    return glds ? launch_variant<EPI, true, CONV, true>(p, stream, what) : launch_variant<EPI, false, CONV, true>(p, stream, what);
+    if (c.gn_stats && conv) {
+        // GroupNorm statistics of the output: in the one-wave kernel's epilogue when it runs (and a frame is at least one wave quadrant of rows), else by the
+        // statistics pass over the finished output
+        if (c.gn_rows >= 128 && first == GK_W4_CONV_0) { p.gn_stats = (double*)c.gn_stats; p.gn_rows = c.gn_rows; }
+        else plan.follow_up = G3_GEMM_THEN_GN_STATS;
+    }
+    plan.row = first + (conv && c.epilogue ? c.epilogue - 2 : c.epilogue);  // the epilogue's place in the family's list (G3_EPI_CONV: 0, 3, 4)
+    return G3_OK;
+}
+
+int gemm_launch(const g3_gemm_call& c) {
+    GemmPlan plan;
+    if (int rc = gemm_plan(c, device_cu_count(), plan)) return rc;
+    const GemmKernel& k = gemm_kernels[plan.row];
+    const GemmParams& p = plan.p;
+    static bool granted[GK_COUNT][G3_MAX_DEVICES] = {};
+    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, granted[plan.row], "gemm")) return rc;
+    hipLaunchKernelGGL(k.fn, dim3(plan.grid), dim3(k.threads), k.lds, (hipStream_t)c.stream, p);
+    int rc = g3_check_launch(plan.what);
+    const int S = c.B > 0 ? p.M / c.B : 0;
+    if (rc == G3_OK && (plan.follow_up & G3_GEMM_THEN_NORM_Q))
+        rc = g3_qk_rmsnorm_rope_bf16(p.C, p.ldc, c.norm_q, c.cos_table, c.sin_table, p.C, p.ldc, S, c.B, c.n_q / 128, 128, c.eps, c.stream);
+    if (rc == G3_OK && (plan.follow_up & G3_GEMM_THEN_NORM_K))
+        rc = g3_qk_rmsnorm_rope_bf16(p.C + c.n_q, p.ldc, c.norm_k, c.cos_table, c.sin_table, p.C + c.n_q, p.ldc, S, c.B, c.n_k / 128, 128, c.eps, c.stream);
+    if (rc == G3_OK && (plan.follow_up & G3_GEMM_THEN_VT))
+        rc = g3_transpose_v_bf16(p.C + c.n_q + c.n_k, p.ldc, c.vt, c.vt_ld, S, c.B, (p.N - c.n_q - c.n_k) / 128, 128, c.stream);
+    if (rc == G3_OK && (plan.follow_up & G3_GEMM_THEN_GN_STATS))
+        rc = g3_groupnorm_stats_cl_bf16(p.C, p.ldc, c.gn_stats, p.M / c.gn_rows, c.gn_rows, p.N, c.stream);
+    return rc;
 }
 
 }  // namespace
@@ -660,58 +807,35 @@ int launch(const GemmParams& p, hipStream_t stream, const char* what) {
 extern "C" int g3_gemm_bf16_nt(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M,
                                int N, int K, int epilogue, const void* gate, int gate_rows, int64_t ldg,
                                const void* residual, int64_t ldr, void* stream) {
-    if (!A || !W || !C) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: null operand");
-    if (M <= 0 || N <= 0 || K <= 0) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bad shape M=%d N=%d K=%d", M, N, K);
-    if ((K & 7) || (lda & 7) || (ldw & 7) || (N & 3) || (ldc & 3))
-        return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: need K,lda,ldw %% 8 == 0 and N,ldc %% 4 == 0 (K=%d lda=%lld ldw=%lld N=%d ldc=%lld)",
-                            K, (long long)lda, (long long)ldw, N, (long long)ldc);
-    if (((uintptr_t)A | (uintptr_t)W) & 15) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: A/W must be 16-byte aligned");
-    if ((uintptr_t)C & 7) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: C must be 8-byte aligned");
-    GemmParams p;
-    p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.C = (bf16_t*)C; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.gate = (const bf16_t*)gate; p.gate_rows = gate_rows > 0 ? gate_rows : 1; p.ldg = ldg;
-    p.R = (const bf16_t*)residual; p.ldr = ldr;
-    p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-    p.tile_order_rowmajor = g3_opt_gemm_rowmajor_tiles;
-    p.wide_store = g3_opt_gemm_wide_store && !(N & 7) && !(ldc & 7) && !((uintptr_t)C & 15) &&
-                   (!gate || (!(ldg & 7) && !((uintptr_t)gate & 15))) && (!residual || (!(ldr & 7) && !((uintptr_t)residual & 15)));
-    p.cv = ConvGeom{};
-    hipStream_t s = (hipStream_t)stream;
-    const char* what = "g3_gemm_bf16_nt";
-    switch (epilogue) {
-        case EPI_NONE: return launch<EPI_NONE, false>(p, s, what);
-        case EPI_GELU: return launch<EPI_GELU, false>(p, s, what);
-        case EPI_GATED_RESIDUAL:
-            if (!gate || !residual || (ldg & 3) || (ldr & 3) || (((uintptr_t)gate | (uintptr_t)residual) & 7))
-                return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: gated-residual epilogue needs 8-byte aligned gate+residual");
-            return launch<EPI_GATED_RESIDUAL, false>(p, s, what);
-        case EPI_BIAS:
-            if (!gate || (ldg & 3) || ((uintptr_t)gate & 7)) return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bias epilogue needs bias");
-            return launch<EPI_BIAS, false>(p, s, what);
-        case EPI_BIAS_RESIDUAL:
-            if (!gate || !residual || (ldg & 3) || (ldr & 3) || (((uintptr_t)gate | (uintptr_t)residual) & 7))
-                return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: bias-residual epilogue needs 8-byte aligned bias+residual");
-            return launch<EPI_BIAS_RESIDUAL, false>(p, s, what);
-        default: return g3_set_error(G3_ERR_ARG, "g3_gemm_bf16_nt: unknown epilogue %d", epilogue);
-    }
+    g3_gemm_call c{};
+    c.entry = G3_GEMM_ENTRY_NT;
+    c.A = A; c.lda = lda; c.W = W; c.ldw = ldw; c.C = C; c.ldc = ldc; c.M = M; c.N = N; c.K = K;
+    c.epilogue = epilogue; c.gate = gate; c.gate_rows = gate_rows; c.ldg = ldg; c.residual = residual; c.ldr = ldr; c.stream = stream;
+    return gemm_launch(c);
 }
 
 // Name of the kernel family g3_gemm_bf16_nt / g3_gemm_qk_norm_rope_bf16 launch for this shape under the options in force (16-byte aligned,
 // 8-element-strided operands assumed - what the DiT passes): for profilers and bench.py's roofline_gemm line, never needed to run the op.
+// The plan's own choice code on those canonical operands; g3_gemm_plan_bf16 is the exact answer for a given call.
 extern "C" const char* g3_gemm_kernel_name(int M, int N, int K, int epilogue) {
-    const bool glds = (K % BK) == 0 && !g3_opt_gemm_regstage;
-    const bool wide = g3_opt_gemm_wide_store && !(N & 7);
-    if (glds && g3_opt_gemm_pingpong == 3 && wide && (epilogue == EPI_NONE || epilogue == EPI_GELU || epilogue == EPI_GATED_RESIDUAL)) {
-        GemmParams p{};
-        p.M = M; p.N = N; p.K = K; p.wide_store = 1; p.gate_rows = 1; p.ldc = p.ldr = N; p.ldg = N;
-        p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-        if (w4e_applies(p, epilogue, device_cu_count())) return "gemm_bf16_nt_w4e_kernel<EPI>";
+    GemmParams p{};
+    p.M = M; p.N = N; p.K = K; p.gate_rows = 1; p.ldc = p.ldr = p.ldg = N;
+    p.wide_store = g3_opt_gemm_wide_store && !(N & 7);
+    p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
+    int grid;
+    return gemm_kernels[gemm_choose(p, epilogue, false, device_cu_count(), grid)].family;
+}
+
+extern "C" const char* g3_gemm_plan_bf16(const g3_gemm_call* call, int n_cu, int* grid, unsigned* follow_up) {
+    if (!call || call->entry < G3_GEMM_ENTRY_NT || call->entry > G3_GEMM_ENTRY_CONV_GNSTATS) {
+        g3_set_error(G3_ERR_ARG, "g3_gemm_plan_bf16: unknown entry %d", call ? call->entry : -1);
+        return nullptr;
     }
-    if (glds && g3_opt_gemm_pingpong == 3 && wide && K >= 2 * BK) return "gemm_bf16_nt_w4_kernel<EPI>";
-    if (glds && g3_opt_gemm_pingpong >= 2) return "gemm_bf16_nt_pp_kernel<EPI, 2, false>";
-    if (glds && g3_opt_gemm_pingpong) return "gemm_bf16_nt_pp_kernel<EPI, 4, false>";
-    return glds ? "gemm_bf16_nt_kernel<EPI, true, false, PIN>" : "gemm_bf16_nt_kernel<EPI, false, false, PIN>";
+    GemmPlan plan;
+    if (gemm_plan(*call, n_cu > 0 ? n_cu : device_cu_count(), plan)) return nullptr;
+    if (grid) *grid = plan.grid;
+    if (follow_up) *follow_up = plan.follow_up;
+    return gemm_kernels[plan.row].name;
 }
 
 // Q / K projection with the per-head RMSNorm (+ RoPE) of the reference's Attention.cal_qkv (attention.py:247-280) in the epilogue:
@@ -723,105 +847,42 @@ extern "C" const char* g3_gemm_kernel_name(int M, int N, int K, int epilogue) {
 extern "C" int g3_gemm_qk_norm_rope_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K,
                                          int n_q, int n_k, const void* norm_q, const void* norm_k, const float* cos_table,
                                          const float* sin_table, int B, float eps, void* vt, int64_t vt_ld, void* stream) {
-    if (!A || !W || !C) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: null operand");
-    if (M <= 0 || N <= 0 || K <= 0 || B <= 0 || (M % B)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: bad shape M=%d N=%d K=%d B=%d", M, N, K, B);
-    if (n_q < 0 || n_k < 0 || (n_q % 128) || (n_k % 128) || n_q + n_k > N || (N % 128))
-        return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: q / k feature ranges must be whole 128-wide heads inside N (n_q=%d n_k=%d N=%d)", n_q, n_k, N);
-    if ((n_q && !norm_q) || (n_k && !norm_k)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: missing norm weight");
-    if ((cos_table == nullptr) != (sin_table == nullptr)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: need both cos and sin tables or neither");
-    if ((K & 7) || (lda & 7) || (ldw & 7) || (ldc & 7)) return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: K, lda, ldw, ldc must be multiples of 8");
-    if ((((uintptr_t)A | (uintptr_t)W | (uintptr_t)C) & 15) || (((uintptr_t)norm_q | (uintptr_t)norm_k) & 15) || (((uintptr_t)cos_table | (uintptr_t)sin_table) & 15))
-        return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: operands must be 16-byte aligned");
-    const int S = M / B, n_v = N - n_q - n_k;
-    if (vt && (n_v <= 0 || (vt_ld & 7) || vt_ld < S || ((uintptr_t)vt & 15)))
-        return g3_set_error(G3_ERR_ARG, "g3_gemm_qk_norm_rope_bf16: V^T destination needs v heads, vt_ld %% 8 == 0, vt_ld >= S and 16-byte alignment");
-    hipStream_t s = (hipStream_t)stream;
-    const bool fused = (K % BK) == 0 && K >= 2 * BK && !g3_opt_gemm_regstage && g3_opt_gemm_pingpong == 3 && g3_opt_gemm_wide_store;
-    const bool vt_fused = fused && vt && (B == 1 || B == 2 || B == 4);
-    int rc;
-    if (fused) {
-        GemmParams p;
-        p.A = (const bf16_t*)A; p.lda = lda; p.W = (const bf16_t*)W; p.ldw = ldw; p.C = (bf16_t*)C; p.ldc = ldc;
-        p.M = M; p.N = N; p.K = K;
-        p.gate = nullptr; p.gate_rows = 1; p.ldg = 0; p.R = nullptr; p.ldr = 0;
-        p.tiles_m = (M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-        p.tile_order_rowmajor = g3_opt_gemm_rowmajor_tiles;
-        p.wide_store = 1;
-        p.cv = ConvGeom{};
-        p.nw_q = (const bf16_t*)norm_q; p.nw_k = (const bf16_t*)norm_k; p.rope_cos = cos_table; p.rope_sin = sin_table;
-        p.n_q = n_q; p.n_k = n_k; p.rope_B = B; p.rms_eps = eps;
-        p.vt = vt_fused ? (bf16_t*)vt : nullptr; p.vt_ld = vt_ld; p.vt_batch = (int64_t)(n_v / 128) * 128 * vt_ld; p.vt_S = S;
-        rc = launch_w4<EPI_QK_NORM_ROPE>(p, s, "g3_gemm_qk_norm_rope_bf16");
-    } else {
-        rc = g3_gemm_bf16_nt(A, lda, W, ldw, C, ldc, M, N, K, EPI_NONE, nullptr, 1, 0, nullptr, 0, stream);
-        bf16_t* c = (bf16_t*)C;
-        if (rc == G3_OK && n_q) rc = g3_qk_rmsnorm_rope_bf16(c, ldc, norm_q, cos_table, sin_table, c, ldc, S, B, n_q / 128, 128, eps, stream);
-        if (rc == G3_OK && n_k) rc = g3_qk_rmsnorm_rope_bf16(c + n_q, ldc, norm_k, cos_table, sin_table, c + n_q, ldc, S, B, n_k / 128, 128, eps, stream);
-    }
-    // V^T where the epilogue did not write it: the standalone transpose of C's v columns (which the fused form leaves unwritten)
-    if (rc == G3_OK && vt && !vt_fused) rc = g3_transpose_v_bf16((const bf16_t*)C + n_q + n_k, ldc, vt, vt_ld, S, B, n_v / 128, 128, stream);
-    return rc;
+    g3_gemm_call c{};
+    c.entry = G3_GEMM_ENTRY_QK_NORM_ROPE;
+    c.A = A; c.lda = lda; c.W = W; c.ldw = ldw; c.C = C; c.ldc = ldc; c.M = M; c.N = N; c.K = K;
+    c.n_q = n_q; c.n_k = n_k; c.norm_q = norm_q; c.norm_k = norm_k; c.cos_table = cos_table; c.sin_table = sin_table; c.B = B; c.eps = eps;
+    c.vt = vt; c.vt_ld = vt_ld; c.stream = stream;
+    return gemm_launch(c);
 }
 
 // Causal 3-D convolution as an implicit GEMM over channels-last activations.
 //   in  [Ti*Hi*Wi][ld_in]  (C_in = K valid channels per position), w [kt*kh*kw][N][ldw] (tap-major, K contiguous),
 //   out [To*Ho*Wo][ld_out]; bias [N] (may be NULL), residual [To*Ho*Wo][ldr] (may be NULL) added after the bias.
-extern "C" int g3_groupnorm_stats_cl_bf16(const void* x, int64_t ld, void* stats_f64, int frames, int rows_per_frame, int C, void* stream);
-
-static int conv3d_cl(const void* in, int64_t ld_in, const void* w, int64_t ldw, const void* bias, const void* residual,
-                     int64_t ldr, void* out, int64_t ld_out, int K, int N, int Ti, int Hi, int Wi, int To, int Ho,
-                     int Wo, int kt, int kh, int kw, int st, int sh, int sw, int ot, int oh, int ow, double* gn_stats, int gn_rows, void* stream) {
-    if (!in || !w || !out) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: null operand");
-    if (K <= 0 || N <= 0 || (K & 7) || (ld_in & 7) || (ldw & 7) || (N & 3) || (ld_out & 3))
-        return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: need K, ld_in, ldw %% 8 == 0 and N, ld_out %% 4 == 0 (K=%d N=%d)", K, N);
-    if (Ti <= 0 || Hi <= 0 || Wi <= 0 || To <= 0 || Ho <= 0 || Wo <= 0 || kt <= 0 || kh <= 0 || kw <= 0 || st <= 0 || sh <= 0 || sw <= 0)
-        return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: bad geometry");
-    if ((int64_t)To * Ho * Wo > 0x7fffffffLL) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: too many output positions");
-    if ((((uintptr_t)in | (uintptr_t)w) & 15) || ((uintptr_t)out & 7)) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: misaligned pointer");
-    if (residual && ((ldr & 3) || ((uintptr_t)residual & 7))) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: misaligned residual");
-    if (residual && !bias) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_bf16: residual without bias is not instantiated");
-    GemmParams p;
-    p.A = (const bf16_t*)in; p.lda = ld_in; p.W = (const bf16_t*)w; p.ldw = ldw; p.C = (bf16_t*)out; p.ldc = ld_out;
-    p.M = To * Ho * Wo; p.N = N; p.K = K;
-    p.gate = (const bf16_t*)bias; p.gate_rows = 1; p.ldg = 0;
-    p.R = (const bf16_t*)residual; p.ldr = ldr;
-    p.tiles_m = (p.M + BM - 1) / BM; p.tiles_n = (N + BN - 1) / BN;
-    p.tile_order_rowmajor = g3_opt_gemm_rowmajor_tiles;
-    p.wide_store = g3_opt_gemm_wide_store && !(N & 7) && !(ld_out & 7) && !((uintptr_t)out & 15) && (!bias || !((uintptr_t)bias & 15)) &&
-                   (!residual || (!(ldr & 7) && !((uintptr_t)residual & 15)));
-    p.cv = ConvGeom{To, Ho, Wo, Ti, Hi, Wi, kt, kh, kw, st, sh, sw, ot, oh, ow, kt * kh * kw, (int64_t)N * ldw, g3_opt_conv_w4 != 2};
-    hipStream_t s = (hipStream_t)stream;
-    const char* what = "g3_conv3d_cl_bf16";
-    // GroupNorm statistics of the output: in the one-wave kernel's epilogue when it runs (and a frame is at least one wave quadrant of rows),
-    // else by the statistics pass over the finished output
-    const bool fuse_stats = gn_stats && gn_rows >= 128 && conv_w4_applies(p);
-    if (fuse_stats) { p.gn_stats = gn_stats; p.gn_rows = gn_rows; }
-    int rc;
-    if (residual) rc = launch<EPI_BIAS_RESIDUAL, true>(p, s, what);
-    else if (bias) rc = launch<EPI_BIAS, true>(p, s, what);
-    else rc = launch<EPI_NONE, true>(p, s, what);
-    if (rc == G3_OK && gn_stats && !fuse_stats) {
-        if (gn_rows <= 0 || (p.M % gn_rows)) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_gnstats_bf16: gn_rows_per_frame must divide the output rows");
-        rc = g3_groupnorm_stats_cl_bf16(out, ld_out, gn_stats, p.M / gn_rows, gn_rows, N, stream);
-    }
-    return rc;
+// g3_conv3d_cl_gnstats_bf16 additionally ADDS, per output frame (gn_rows_per_frame consecutive output rows = Ho * Wo), the sum and the sum of squares of
+// the stored bf16 outputs to gn_stats[frame][0 / 1] (doubles; the caller zeroes them): the statistics CausalNormalize needs of this tensor
+// (tokenizer/modules/utils.py:58-83), so that the following g3_groupnorm_apply_cl_bf16 does not have to read the tensor twice.
+static int conv3d_cl(int entry, const void* in, int64_t ld_in, const void* w, int64_t ldw, const void* bias, const void* residual, int64_t ldr, void* out,
+                     int64_t ld_out, int K, int N, int Ti, int Hi, int Wi, int To, int Ho, int Wo, int kt, int kh, int kw, int st, int sh, int sw, int ot,
+                     int oh, int ow, void* gn_stats_f64, int gn_rows_per_frame, void* stream) {
+    g3_gemm_call c{};
+    c.entry = entry;
+    c.A = in; c.lda = ld_in; c.W = w; c.ldw = ldw; c.C = out; c.ldc = ld_out; c.N = N; c.K = K; c.gate = bias; c.residual = residual; c.ldr = ldr;
+    c.Ti = Ti; c.Hi = Hi; c.Wi = Wi; c.To = To; c.Ho = Ho; c.Wo = Wo; c.kt = kt; c.kh = kh; c.kw = kw; c.st = st; c.sh = sh; c.sw = sw; c.ot = ot; c.oh = oh; c.ow = ow;
+    c.gn_stats = gn_stats_f64; c.gn_rows = gn_rows_per_frame; c.stream = stream;
+    return gemm_launch(c);
 }
 
 extern "C" int g3_conv3d_cl_bf16(const void* in, int64_t ld_in, const void* w, int64_t ldw, const void* bias, const void* residual,
                                  int64_t ldr, void* out, int64_t ld_out, int K, int N, int Ti, int Hi, int Wi, int To, int Ho,
                                  int Wo, int kt, int kh, int kw, int st, int sh, int sw, int ot, int oh, int ow, void* stream) {
-    return conv3d_cl(in, ld_in, w, ldw, bias, residual, ldr, out, ld_out, K, N, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, ot, oh, ow, nullptr, 0, stream);
+    return conv3d_cl(G3_GEMM_ENTRY_CONV, in, ld_in, w, ldw, bias, residual, ldr, out, ld_out, K, N, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, ot, oh, ow,
+                     nullptr, 0, stream);
 }
 
-// Same convolution; additionally ADDS, per output frame (gn_rows_per_frame consecutive output rows = Ho * Wo), the sum and the sum of squares of
-// the stored bf16 outputs to gn_stats[frame][0 / 1] (doubles; the caller zeroes them): the statistics CausalNormalize needs of this tensor
-// (tokenizer/modules/utils.py:58-83), so that the following g3_groupnorm_apply_cl_bf16 does not have to read the tensor twice.
 extern "C" int g3_conv3d_cl_gnstats_bf16(const void* in, int64_t ld_in, const void* w, int64_t ldw, const void* bias, const void* residual,
                                          int64_t ldr, void* out, int64_t ld_out, int K, int N, int Ti, int Hi, int Wi, int To, int Ho,
                                          int Wo, int kt, int kh, int kw, int st, int sh, int sw, int ot, int oh, int ow, void* gn_stats_f64,
                                          int gn_rows_per_frame, void* stream) {
-    if (!gn_stats_f64 || gn_rows_per_frame <= 0 || ((uintptr_t)gn_stats_f64 & 7)) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_gnstats_bf16: bad statistics buffer");
-    if (((int64_t)To * Ho * Wo) % gn_rows_per_frame) return g3_set_error(G3_ERR_ARG, "g3_conv3d_cl_gnstats_bf16: gn_rows_per_frame must divide the output rows");
-    return conv3d_cl(in, ld_in, w, ldw, bias, residual, ldr, out, ld_out, K, N, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, ot, oh, ow,
-                     (double*)gn_stats_f64, gn_rows_per_frame, stream);
+    return conv3d_cl(G3_GEMM_ENTRY_CONV_GNSTATS, in, ld_in, w, ldw, bias, residual, ldr, out, ld_out, K, N, Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, ot, oh, ow,
+                     gn_stats_f64, gn_rows_per_frame, stream);
 }

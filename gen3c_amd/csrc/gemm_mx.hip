@@ -270,31 +270,58 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mxfp8_nt_kernel(MxParams p) 
         store_tile_lds<EPI>(p.ep, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
 }
 
-template <int EPI>
-int launch_mx(const MxParams& p, hipStream_t stream, const char* f = "g3_gemm_mxfp8_nt") {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp8_nt_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", f, hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_mxfp8_nt_kernel<EPI>), dim3(p.ep.tiles_m * p.ep.tiles_n), dim3(NTHREADS), MX_SMEM, stream, p);
+// The one launch of the MX GEMMs. KERNEL: the instantiation; P: its parameter block (MxParams / Mx6Params).
+template <auto KERNEL, class P>
+int mx_launch(const P& p, void* stream, const char* f) {
+    static bool granted[G3_MAX_DEVICES] = {};
+    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(KERNEL), MX_SMEM, granted, f)) return rc;
+    hipLaunchKernelGGL(KERNEL, dim3(p.ep.tiles_m * p.ep.tiles_n), dim3(NTHREADS), MX_SMEM, (hipStream_t)stream, p);
     return g3_check_launch(f);
 }
 
 bool mx_shape_ok(int M, int N, int K) { return M > 0 && N > 0 && K > 0 && (N % BN) == 0 && (K % MX_BK) == 0; }
 
-// What both GEMM entry points require of their MXFP8 operands; G3_OK or the error already set.
+// What every GEMM entry point requires of its MX operands; row_bytes: the packed bytes of a row's K elements (K as e4m3, 3K/4 as e2m3). G3_OK or the error already set.
 int mx_check_operands(const char* f, const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws,
-                      int M, int N, int K) {
+                      int M, int N, int K, int64_t row_bytes) {
     if (!aq || !as || !wq || !ws) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
     if (!mx_shape_ok(M, N, K)) return g3_set_error(G3_ERR_ARG, "%s: need M > 0, N a multiple of 256 and K a multiple of 128 (M=%d N=%d K=%d)", f, M, N, K);
-    if (lda < K || ldw < K || (lda & 15) || (ldw & 15)) return g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= K and multiples of 16 (lda=%lld ldw=%lld)", f, (long long)lda, (long long)ldw);
+    if (lda < row_bytes || ldw < row_bytes || (lda & 15) || (ldw & 15))
+        return row_bytes == K ? g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= K and multiples of 16 (lda=%lld ldw=%lld)", f, (long long)lda, (long long)ldw)
+                              : g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= 3K/4 and multiples of 16 (lda=%lld ldw=%lld K=%d)", f, (long long)lda, (long long)ldw, K);
     if (ldas < K / MX_BLOCK || ldws < K / MX_BLOCK || (ldas & 3) || (ldws & 3))
         return g3_set_error(G3_ERR_ARG, "%s: need scale strides >= K/32 and multiples of 4 (ldas=%lld ldws=%lld K=%d)", f, (long long)ldas, (long long)ldws, K);
     if (((uintptr_t)aq | (uintptr_t)wq) & 15) return g3_set_error(G3_ERR_ARG, "%s: operands must be 16-byte aligned", f);
     if (((uintptr_t)as | (uintptr_t)ws) & 3) return g3_set_error(G3_ERR_ARG, "%s: scales must be 4-byte aligned", f);
     return G3_OK;
+}
+
+// What the entries with a bf16 output (MXFP8 and MXFP6 operands) require of C and of the epilogue's operands.
+int mx_check_bf16_output(const char* f, const void* c, int64_t ldc, int N, int epilogue, const void* gate, int gate_rows, int64_t ldg, const void* residual, int64_t ldr) {
+    if (ldc < N || (ldc & 7) || ((uintptr_t)c & 15)) return g3_set_error(G3_ERR_ARG, "%s: C needs ldc >= N, ldc %% 8 == 0 and 16-byte alignment", f);
+    if (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL) return g3_set_error(G3_ERR_ARG, "%s: unsupported epilogue %d", f, epilogue);
+    if (epilogue == EPI_GATED_RESIDUAL &&
+        (!gate || !residual || gate_rows <= 0 || (ldg & 7) || (ldr & 7) || ldr < N || (gate_rows > 1 && ldg < N) ||
+         (((uintptr_t)gate | (uintptr_t)residual) & 15)))
+        return g3_set_error(G3_ERR_ARG, "%s: gated-residual epilogue needs gate [gate_rows][ldg >= N] and residual [M][ldr >= N], 16-byte aligned rows", f);
+    return G3_OK;
+}
+
+// The one fill of a parameter block (P: MxParams / Mx6Params): the operands, and the part the shared epilogue reads (the MXFP8-output entry has no C, gate or residual).
+template <class P>
+P mx_params(const void* aq, int64_t lda, const void* as, int64_t ldas, const void* wq, int64_t ldw, const void* ws, int64_t ldws, int M, int N, int K,
+            void* c = nullptr, int64_t ldc = 0, const void* gate = nullptr, int gate_rows = 1, int64_t ldg = 0, const void* residual = nullptr, int64_t ldr = 0) {
+    P p{};
+    p.ep.tile_order_rowmajor = 0;
+    p.ep.wide_store = 1;
+    p.ep.C = (bf16_t*)c; p.ep.ldc = ldc;
+    p.ep.M = M; p.ep.N = N; p.ep.K = K;
+    p.ep.gate = (const bf16_t*)gate; p.ep.gate_rows = gate_rows > 0 ? gate_rows : 1; p.ep.ldg = ldg;
+    p.ep.R = (const bf16_t*)residual; p.ep.ldr = ldr;
+    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
+    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
+    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
+    return p;
 }
 
 }  // namespace
@@ -319,28 +346,13 @@ extern "C" int g3_gemm_mxfp8_nt(const void* aq, int64_t lda, const void* as, int
                                 int64_t ldg, const void* residual, int64_t ldr, void* stream) {
     const char* f = "g3_gemm_mxfp8_nt";
     if (!c) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
-    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K)) return rc;
-    if (ldc < N || (ldc & 7) || ((uintptr_t)c & 15)) return g3_set_error(G3_ERR_ARG, "%s: C needs ldc >= N, ldc %% 8 == 0 and 16-byte alignment", f);
-    if (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL) return g3_set_error(G3_ERR_ARG, "%s: unsupported epilogue %d", f, epilogue);
-    if (epilogue == EPI_GATED_RESIDUAL &&
-        (!gate || !residual || gate_rows <= 0 || (ldg & 7) || (ldr & 7) || ldr < N || (gate_rows > 1 && ldg < N) ||
-         (((uintptr_t)gate | (uintptr_t)residual) & 15)))
-        return g3_set_error(G3_ERR_ARG, "%s: gated-residual epilogue needs gate [gate_rows][ldg >= N] and residual [M][ldr >= N], 16-byte aligned rows", f);
-    MxParams p{};
-    p.ep.tile_order_rowmajor = 0;
-    p.ep.wide_store = 1;
-    p.ep.C = (bf16_t*)c; p.ep.ldc = ldc;
-    p.ep.M = M; p.ep.N = N; p.ep.K = K;
-    p.ep.gate = (const bf16_t*)gate; p.ep.gate_rows = gate_rows > 0 ? gate_rows : 1; p.ep.ldg = ldg;
-    p.ep.R = (const bf16_t*)residual; p.ep.ldr = ldr;
-    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
-    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
-    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
-    hipStream_t s = (hipStream_t)stream;
+    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K, K)) return rc;
+    if (int rc = mx_check_bf16_output(f, c, ldc, N, epilogue, gate, gate_rows, ldg, residual, ldr)) return rc;
+    const MxParams p = mx_params<MxParams>(aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K, c, ldc, gate, gate_rows, ldg, residual, ldr);
     switch (epilogue) {
-        case EPI_NONE: return launch_mx<EPI_NONE>(p, s);
-        case EPI_GELU: return launch_mx<EPI_GELU>(p, s);
-        default: return launch_mx<EPI_GATED_RESIDUAL>(p, s);
+        case EPI_NONE: return mx_launch<gemm_mxfp8_nt_kernel<EPI_NONE>>(p, stream, f);
+        case EPI_GELU: return mx_launch<gemm_mxfp8_nt_kernel<EPI_GELU>>(p, stream, f);
+        default: return mx_launch<gemm_mxfp8_nt_kernel<EPI_GATED_RESIDUAL>>(p, stream, f);
     }
 }
 
@@ -355,23 +367,15 @@ extern "C" int g3_gemm_mxfp8_nt_mxout(const void* aq, int64_t lda, const void* a
                                       void* stream) {
     const char* f = "g3_gemm_mxfp8_nt_mxout";
     if (!q_out || !s_out) return g3_set_error(G3_ERR_ARG, "%s: null output", f);
-    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K)) return rc;
+    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K, K)) return rc;
     if (ldq < N || (ldq & 7) || lds < N / MX_BLOCK)
         return g3_set_error(G3_ERR_ARG, "%s: need ldq >= N (a multiple of 8) and lds >= N/32 (ldq=%lld lds=%lld N=%d)", f, (long long)ldq, (long long)lds, N);
     if ((uintptr_t)q_out & 7) return g3_set_error(G3_ERR_ARG, "%s: q_out must be 8-byte aligned", f);
     if (epilogue != EPI_NONE && epilogue != EPI_GELU)
         return g3_set_error(G3_ERR_ARG, "%s: epilogue %d has no MXFP8 output (NONE and GELU only: the gated residual's output is the bf16 residual stream)", f, epilogue);
-    MxParams p{};
-    p.ep.tile_order_rowmajor = 0;
-    p.ep.wide_store = 1;
-    p.ep.M = M; p.ep.N = N; p.ep.K = K;
-    p.ep.gate_rows = 1;
-    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
-    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
-    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
+    MxParams p = mx_params<MxParams>(aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K);
     p.Q = (uint8_t*)q_out; p.ldq = ldq; p.S = (uint8_t*)s_out; p.lds = lds;
-    hipStream_t s = (hipStream_t)stream;
-    return epilogue == EPI_GELU ? launch_mx<MX_OUT | EPI_GELU>(p, s, f) : launch_mx<MX_OUT | EPI_NONE>(p, s, f);
+    return epilogue == EPI_GELU ? mx_launch<gemm_mxfp8_nt_kernel<MX_OUT | EPI_GELU>>(p, stream, f) : mx_launch<gemm_mxfp8_nt_kernel<MX_OUT | EPI_NONE>>(p, stream, f);
 }
 
 extern "C" const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int epilogue) {
@@ -589,18 +593,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_mxfp6_nt_kernel(Mx6Params p)
     store_tile_lds<EPI>(p.ep, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
 }
 
-template <int EPI>
-int launch_mx6(const Mx6Params& p, hipStream_t stream, const char* f) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_mxfp6_nt_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-        if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "%s: hipFuncSetAttribute: %s", f, hipGetErrorString(e));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_mxfp6_nt_kernel<EPI>), dim3(p.ep.tiles_m * p.ep.tiles_n), dim3(NTHREADS), MX_SMEM, stream, p);
-    return g3_check_launch(f);
-}
-
 }  // namespace
 
 extern "C" int g3_quant_mxfp6_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream) {
@@ -622,36 +614,14 @@ extern "C" int g3_gemm_mxfp6_nt(const void* aq, int64_t lda, const void* as, int
                                 int64_t ldws, void* c, int64_t ldc, int M, int N, int K, int epilogue, const void* gate, int gate_rows,
                                 int64_t ldg, const void* residual, int64_t ldr, void* stream) {
     const char* f = "g3_gemm_mxfp6_nt";
-    if (!c || !aq || !as || !wq || !ws) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
-    if (!mx_shape_ok(M, N, K)) return g3_set_error(G3_ERR_ARG, "%s: need M > 0, N a multiple of 256 and K a multiple of 128 (M=%d N=%d K=%d)", f, M, N, K);
-    const int64_t row_bytes = (int64_t)K / 4 * 3;
-    if (lda < row_bytes || ldw < row_bytes || (lda & 15) || (ldw & 15))
-        return g3_set_error(G3_ERR_ARG, "%s: need lda, ldw >= 3K/4 and multiples of 16 (lda=%lld ldw=%lld K=%d)", f, (long long)lda, (long long)ldw, K);
-    if (ldas < K / MX_BLOCK || ldws < K / MX_BLOCK || (ldas & 3) || (ldws & 3))
-        return g3_set_error(G3_ERR_ARG, "%s: need scale strides >= K/32 and multiples of 4 (ldas=%lld ldws=%lld K=%d)", f, (long long)ldas, (long long)ldws, K);
-    if (((uintptr_t)aq | (uintptr_t)wq) & 15) return g3_set_error(G3_ERR_ARG, "%s: operands must be 16-byte aligned", f);
-    if (((uintptr_t)as | (uintptr_t)ws) & 3) return g3_set_error(G3_ERR_ARG, "%s: scales must be 4-byte aligned", f);
-    if (ldc < N || (ldc & 7) || ((uintptr_t)c & 15)) return g3_set_error(G3_ERR_ARG, "%s: C needs ldc >= N, ldc %% 8 == 0 and 16-byte alignment", f);
-    if (epilogue != EPI_NONE && epilogue != EPI_GELU && epilogue != EPI_GATED_RESIDUAL) return g3_set_error(G3_ERR_ARG, "%s: unsupported epilogue %d", f, epilogue);
-    if (epilogue == EPI_GATED_RESIDUAL &&
-        (!gate || !residual || gate_rows <= 0 || (ldg & 7) || (ldr & 7) || ldr < N || (gate_rows > 1 && ldg < N) ||
-         (((uintptr_t)gate | (uintptr_t)residual) & 15)))
-        return g3_set_error(G3_ERR_ARG, "%s: gated-residual epilogue needs gate [gate_rows][ldg >= N] and residual [M][ldr >= N], 16-byte aligned rows", f);
-    Mx6Params p{};
-    p.ep.tile_order_rowmajor = 0;
-    p.ep.wide_store = 1;
-    p.ep.C = (bf16_t*)c; p.ep.ldc = ldc;
-    p.ep.M = M; p.ep.N = N; p.ep.K = K;
-    p.ep.gate = (const bf16_t*)gate; p.ep.gate_rows = gate_rows > 0 ? gate_rows : 1; p.ep.ldg = ldg;
-    p.ep.R = (const bf16_t*)residual; p.ep.ldr = ldr;
-    p.ep.tiles_m = (M + BM - 1) / BM; p.ep.tiles_n = N / BN;
-    p.A = (const uint8_t*)aq; p.lda = lda; p.As = (const uint8_t*)as; p.ldas = ldas;
-    p.W = (const uint8_t*)wq; p.ldw = ldw; p.Ws = (const uint8_t*)ws; p.ldws = ldws;
-    hipStream_t s = (hipStream_t)stream;
+    if (!c) return g3_set_error(G3_ERR_ARG, "%s: null operand", f);
+    if (int rc = mx_check_operands(f, aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K, (int64_t)K / 4 * 3)) return rc;
+    if (int rc = mx_check_bf16_output(f, c, ldc, N, epilogue, gate, gate_rows, ldg, residual, ldr)) return rc;
+    const Mx6Params p = mx_params<Mx6Params>(aq, lda, as, ldas, wq, ldw, ws, ldws, M, N, K, c, ldc, gate, gate_rows, ldg, residual, ldr);
     switch (epilogue) {
-        case EPI_NONE: return launch_mx6<EPI_NONE>(p, s, f);
-        case EPI_GELU: return launch_mx6<EPI_GELU>(p, s, f);
-        default: return launch_mx6<EPI_GATED_RESIDUAL>(p, s, f);
+        case EPI_NONE: return mx_launch<gemm_mxfp6_nt_kernel<EPI_NONE>>(p, stream, f);
+        case EPI_GELU: return mx_launch<gemm_mxfp6_nt_kernel<EPI_GELU>>(p, stream, f);
+        default: return mx_launch<gemm_mxfp6_nt_kernel<EPI_GATED_RESIDUAL>>(p, stream, f);
     }
 }
 

@@ -572,38 +572,3 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4_kernel(GemmPar
     L = Lnext;
   }
 }
-
-template <int EPI>
-int launch_w4(const GemmParams& p, hipStream_t stream, const char* what) {
-    const size_t smem = 2 * GW4_STAGE_BYTES;
-    static bool attr_set[64] = {};
-    static int n_cu[64] = {};
-    static std::mutex attr_mu;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipGetDevice failed");
-    {
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (!attr_set[dev_id]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_w4_kernel<EPI, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if constexpr (EPI != EPI_QK_NORM_ROPE)
-                if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_w4_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            int cus = 0;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev_id) != hipSuccess || cus <= 0) cus = 256;
-            n_cu[dev_id] = cus;
-            attr_set[dev_id] = true;
-        }
-    }
-    const int nblk = p.tiles_m * p.tiles_n;
-    // persistent form: one workgroup per CU (a multiple of 8 keeps a workgroup's tiles on its XCD's band of the XCD-aware order); only worth it
-    // when a workgroup gets at least two tiles
-    const int grid_p = (n_cu[dev_id] / 8) * 8;
-    if constexpr (EPI != EPI_QK_NORM_ROPE) {  // (the norm / RoPE epilogue's tables do not fit beside the tile state: no persistent form)
-        if (g3_opt_gemm_persistent && grid_p >= 8 && nblk >= 2 * grid_p) {
-            hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<EPI, true>), dim3(grid_p), dim3(GW4_THREADS), smem, stream, p);
-            return g3_check_launch(what);
-        }
-    }
-    hipLaunchKernelGGL((gemm_bf16_nt_w4_kernel<EPI, false>), dim3(nblk), dim3(GW4_THREADS), smem, stream, p);
-    return g3_check_launch(what);
-}

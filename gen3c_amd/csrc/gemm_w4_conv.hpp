@@ -395,22 +395,3 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4_conv_kernel(Ge
         }
     }
 }
-
-template <int EPI>
-int launch_w4_conv(const GemmParams& p, hipStream_t stream, const char* what) {
-    const size_t smem = 2 * GW4_STAGE_BYTES;
-    static bool attr_set[64] = {};
-    static std::mutex attr_mu;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return g3_set_error(G3_ERR_LAUNCH, "conv: hipGetDevice failed");
-    {
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (!attr_set[dev_id]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_w4_conv_kernel<EPI>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "conv: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr_set[dev_id] = true;
-        }
-    }
-    hipLaunchKernelGGL((gemm_bf16_nt_w4_conv_kernel<EPI>), dim3(p.tiles_m * p.tiles_n), dim3(GW4_THREADS), smem, stream, p);
-    return g3_check_launch(what);
-}

@@ -28,7 +28,7 @@ constexpr int GW4E_MIN_NK = 38;                               // K tile 0 preamb
 
 // TF (token pieces first): the order in which a K tile's 16 LDS-DMA pieces are requested. false (gemm_w4.hpp's order): weight rows 0..5 two K tiles ahead (K step 3),
 // weight rows 6, 7 + token rows one tile ahead (K steps 0, 1); true: the same with the operands' roles swapped - the token panel gets the longer lead. The token
-// operand of MLP-down is a 3.7 GB stream from HBM (K = 16 384), its weights come from the L2 / Infinity Cache: host heuristic in launch_w4e (N <= 4096).
+// operand of MLP-down is a 3.7 GB stream from HBM (K = 16 384), its weights come from the L2 / Infinity Cache: host heuristic in gemm_choose, gemm.hip (N <= 4096).
 template <int EPI, bool TF>
 __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmParams p) {
     static_assert(EPI == EPI_NONE || EPI == EPI_GELU || EPI == EPI_GATED_RESIDUAL, "gemm_bf16_nt_w4e_kernel: epilogue class without a deferred form");
@@ -427,35 +427,4 @@ static bool w4e_applies(const GemmParams& p, int epi, int n_cu) {
     if (epi == EPI_GATED_RESIDUAL && !(p.gate_rows == 1 || p.gate_rows == 2 || p.gate_rows == 4)) return false;
     if ((int64_t)8 * p.ldc * 2 >= (1ll << 31) || (int64_t)8 * p.ldr * 2 >= (1ll << 31) || (int64_t)4 * p.ldg * 2 >= (1ll << 31)) return false;
     return true;
-}
-
-template <int EPI, bool TF>
-int launch_w4e_tf(const GemmParams& p, hipStream_t stream, const char* what, int n_cu) {
-    static bool attr_set[64] = {};
-    static std::mutex attr_mu;
-    int dev_id = 0;
-    if (hipGetDevice(&dev_id) != hipSuccess || dev_id < 0 || dev_id >= 64) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipGetDevice failed");
-    {
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (!attr_set[dev_id]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_nt_w4e_kernel<EPI, TF>), hipFuncAttributeMaxDynamicSharedMemorySize, GW4E_LDS_BYTES);
-            if (e != hipSuccess) return g3_set_error(G3_ERR_LAUNCH, "gemm: hipFuncSetAttribute(w4e): %s", hipGetErrorString(e));
-            attr_set[dev_id] = true;
-        }
-    }
-    int grid = (n_cu / 8) * 8;
-    // (tests: g3_set_option("gemm_deferred_grid", g) runs the tile loop on g workgroups - any multiple of 8 that leaves every workgroup a tile - to walk long and
-    // uneven tile lists; 0 = one workgroup per CU)
-    if (g3_opt_gemm_deferred_grid >= 8 && (g3_opt_gemm_deferred_grid % 8) == 0 && g3_opt_gemm_deferred_grid <= p.tiles_m * p.tiles_n) grid = g3_opt_gemm_deferred_grid;
-    hipLaunchKernelGGL((gemm_bf16_nt_w4e_kernel<EPI, TF>), dim3(grid), dim3(GW4_THREADS), GW4E_LDS_BYTES, stream, p);
-    return g3_check_launch(what);
-}
-
-// piece order by shape: g3_set_option("gemm_tokens_first", 0 / 1 / 2): never / always / (default) where few feature tiles share a token panel (N <= 4096: its
-// rows are fetched from HBM by the first of at most 16 workgroups and everybody waits for them) - measured (profiles/r5_gemm_tokens_first_ab.txt): out-projection +1 %,
-// MLP-down +1.5 %; QKV (N = 12 288) -3.5 %, MLP-up (N = 16 384) -1 % -> those keep the weights-first order
-template <int EPI>
-int launch_w4e(const GemmParams& p, hipStream_t stream, const char* what, int n_cu) {
-    const bool tf = g3_opt_gemm_tokens_first == 1 || (g3_opt_gemm_tokens_first == 2 && p.N <= 4096);
-    return tf ? launch_w4e_tf<EPI, true>(p, stream, what, n_cu) : launch_w4e_tf<EPI, false>(p, stream, what, n_cu);
 }

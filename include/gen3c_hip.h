@@ -448,6 +448,31 @@ int g3_conv3d_cl_gnstats_bf16(const void* in, int64_t ld_in, const void* w, int6
                               int64_t ldr, void* out, int64_t ld_out, int K, int N, int Ti, int Hi, int Wi, int To, int Ho, int Wo,
                               int kt, int kh, int kw, int st, int sh, int sw, int ot, int oh, int ow, void* gn_stats_f64,
                               int gn_rows_per_frame, void* stream);
+
+/* Dry run of the bf16 GEMM entries (g3_gemm_bf16_nt, g3_gemm_qk_norm_rope_bf16, g3_conv3d_cl_bf16, g3_conv3d_cl_gnstats_bf16): the call record those
+ * entries fill, and the name of the kernel instantiation the call would launch with exactly these arguments under the options in force - every check
+ * and the whole kernel choice of the real call - or NULL where the call would be refused, with g3_last_error() set exactly as the call sets it.
+ * n_cu: the device's CU count the choice assumes (0 = the current device's). *grid (if not NULL): workgroups of that launch; *follow_up (if not
+ * NULL): the G3_GEMM_THEN_* launches the entry makes after it. Nothing is launched, the plan itself makes no HIP call and no pointer is dereferenced
+ * (pointers are tested for NULL and alignment only). Fields `entry` does not take are ignored. */
+enum g3_gemm_entry { G3_GEMM_ENTRY_NT = 0, G3_GEMM_ENTRY_QK_NORM_ROPE = 1, G3_GEMM_ENTRY_CONV = 2, G3_GEMM_ENTRY_CONV_GNSTATS = 3 };
+typedef struct g3_gemm_call {
+    int entry;                                                                         /* enum g3_gemm_entry */
+    const void* A; int64_t lda; const void* W; int64_t ldw; void* C; int64_t ldc;      /* conv: in / ld_in, w / ldw, out / ld_out */
+    int M, N, K;                                                                       /* conv: M = To*Ho*Wo is derived */
+    int epilogue; const void* gate; int gate_rows; int64_t ldg;                        /* NT only, but gate: also the conv's bias */
+    const void* residual; int64_t ldr;                                                 /* NT and conv */
+    int n_q, n_k; const void* norm_q; const void* norm_k; const float* cos_table; const float* sin_table; int B; float eps; void* vt; int64_t vt_ld;
+    int Ti, Hi, Wi, To, Ho, Wo, kt, kh, kw, st, sh, sw, ot, oh, ow;                    /* conv geometry */
+    void* gn_stats; int gn_rows;                                                       /* CONV_GNSTATS: gn_stats_f64, gn_rows_per_frame */
+    void* stream;                                                                      /* (not read by the dry run) */
+} g3_gemm_call;
+#define G3_GEMM_THEN_NORM_Q 1u   /* g3_qk_rmsnorm_rope_bf16 over the q heads (the norm / RoPE epilogue does not apply) */
+#define G3_GEMM_THEN_NORM_K 2u   /* ... over the k heads */
+#define G3_GEMM_THEN_VT 4u       /* g3_transpose_v_bf16 of C's v columns (the epilogue does not write V^T for this call) */
+#define G3_GEMM_THEN_GN_STATS 8u /* g3_groupnorm_stats_cl_bf16 over the finished output (the statistics are not taken in the epilogue) */
+const char* g3_gemm_plan_bf16(const g3_gemm_call* call /*host*/, int n_cu, int* grid /*host*/, unsigned* follow_up /*host*/);
+
 int g3_groupnorm_stats_cl_bf16(const void* x, int64_t ld, void* stats_f64, int frames, int rows_per_frame, int C, void* stream);
 int g3_groupnorm_apply_cl_bf16(const void* x, int64_t ld, const void* gamma, const void* beta, const void* stats_f64, void* out,
                                int64_t ldo, int frames, int rows_per_frame, int C, float eps, int swish, void* stream);

@@ -4,6 +4,7 @@ Tolerances (stated per test): operands are bf16, accumulation fp32, outputs roun
 error vs an fp32 evaluation of the same bf16 operands is ~2^-9 relative per output (one bf16 rounding) plus
 accumulation-order noise.
 """
+import ctypes as C
 import math
 
 import pytest
@@ -45,6 +46,112 @@ def test_gemm_pingpong_bitwise_equals_classic_and_is_race_free():
             outs[variant] = first
         ops.set_option("gemm_pingpong", 3)
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2]) and torch.equal(outs[0], outs[3]), f"ping-pong / w4 != classic at {M}x{N}x{K} epi {epi}"
+
+
+_GEMM_OPTION_DEFAULTS = {"gemm_pingpong": 3, "gemm_regstage": 0, "gemm_unpinned": 1, "gemm_persistent": 0, "gemm_tokens_first": 2}
+_GEMM_ROW_FAMILIES = [  # (instantiation with {e} for the epilogue, the options that select it, the smallest shape that reaches it, its epilogues)
+    ("gemm_bf16_nt_kernel<{e}, true, false, false>", {"gemm_pingpong": 0}, "small", range(5)),
+    ("gemm_bf16_nt_kernel<{e}, true, false, true>", {"gemm_pingpong": 0, "gemm_unpinned": 0}, "small", range(5)),
+    ("gemm_bf16_nt_kernel<{e}, false, false, false>", {"gemm_regstage": 1}, "small", range(5)),
+    ("gemm_bf16_nt_kernel<{e}, false, false, true>", {"gemm_regstage": 1, "gemm_unpinned": 0}, "small", range(5)),
+    ("gemm_bf16_nt_pp_kernel<{e}, 2, false>", {"gemm_pingpong": 2}, "small", range(5)),
+    ("gemm_bf16_nt_pp_kernel<{e}, 4, false>", {"gemm_pingpong": 1}, "small", range(5)),
+    ("gemm_bf16_nt_w4_kernel<{e}, false>", {}, "k128", range(5)),
+    ("gemm_bf16_nt_w4_kernel<{e}, true>", {"gemm_persistent": 1}, "two_tiles_k128", range(5)),
+    ("gemm_bf16_nt_w4e_kernel<{e}, false>", {"gemm_tokens_first": 0}, "two_tiles_k2432", range(3)),
+    ("gemm_bf16_nt_w4e_kernel<{e}, true>", {"gemm_tokens_first": 1}, "two_tiles_k2432", range(3)),
+]
+_gemm_row_cache = {}
+
+
+def _gemm_row_operands(shape, epi):
+    """Operands of a shape (made once) and the output of the gemm_pingpong = 0 kernel on them per epilogue (computed once, never written again)."""
+    from gen3c_amd import _lib, ops
+    dev = _dev()
+    if shape not in _gemm_row_cache:
+        cus = C.c_int(0)
+        _lib.check(_lib.load().g3_device_info(0, C.byref(cus), None, None, 0), "g3_device_info")
+        m_two = 256 * -(-2 * (cus.value // 8 * 8) // 16)  # with N = 4096 (16 tiles): at least two tiles for each of the persistent grid's workgroups
+        M, N, K = {"small": (256, 256, 64), "k128": (256, 256, 128), "two_tiles_k128": (m_two, 4096, 128), "two_tiles_k2432": (m_two, 4096, 2432)}[shape]
+        g = torch.Generator(device=dev).manual_seed(M + N + K)
+        a = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+        w = (torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16)
+        _gemm_row_cache[shape] = (a, w, torch.randn(1, N, device=dev, generator=g).to(torch.bfloat16), torch.randn(M, N, device=dev, generator=g).to(torch.bfloat16))
+    a, w, gate, res = _gemm_row_cache[shape]
+    kw = dict(gate=gate, residual=res) if epi in (2, 4) else (dict(gate=gate) if epi == 3 else {})
+    if (shape, epi) not in _gemm_row_cache:
+        ops.set_option("gemm_pingpong", 0)
+        try:
+            _gemm_row_cache[shape, epi] = ops.gemm_nt(a, w, epilogue=epi, **kw)
+            torch.cuda.synchronize()
+        finally:
+            ops.set_option("gemm_pingpong", 3)
+    return a, w, kw, _gemm_row_cache[shape, epi]
+
+
+@pytest.mark.parametrize("name,options,shape,epi", [(n.format(e=e), o, s, e) for n, o, s, epis in _GEMM_ROW_FAMILIES for e in epis])
+def test_gemm_launcher_launches_the_row_the_plan_names(name, options, shape, epi):
+    """One case per kernel-table row of g3_gemm_bf16_nt, at the smallest shape that reaches the row: the dry run names that row for exactly the call made,
+    the call runs, and the output is BITWISE that of the gemm_pingpong = 0 kernel on the same operands (every GEMM kernel accumulates over K in one order
+    and rounds at the same points: the bar of test_gemm_pingpong_bitwise_equals_classic_and_is_race_free and test_gemm_deferred_epilogue_kernel)."""
+    from gen3c_amd import _lib, ops
+    lib = _lib.load()
+    a, w, kw, ref = _gemm_row_operands(shape, epi)
+    (M, K), N = a.shape, w.shape[0]
+    gate, res = kw.get("gate"), kw.get("residual")
+    out = torch.empty_like(ref)
+    call = _lib.GemmCall(entry=0, A=a.data_ptr(), lda=K, W=w.data_ptr(), ldw=K, C=out.data_ptr(), ldc=N, M=M, N=N, K=K, epilogue=epi,
+                         gate=gate.data_ptr() if gate is not None else 0, gate_rows=1, ldg=N, residual=res.data_ptr() if res is not None else 0, ldr=N)
+    try:
+        for k, v in options.items():
+            ops.set_option(k, v)
+        planned = lib.g3_gemm_plan_bf16(C.byref(call), 0, None, None)
+        assert planned is not None and planned.decode() == name, (planned, _lib.last_error())
+        ops.gemm_nt(a, w, out=out, epilogue=epi, **kw)
+        torch.cuda.synchronize()
+    finally:
+        for k, v in _GEMM_OPTION_DEFAULTS.items():
+            ops.set_option(k, v)
+    assert torch.equal(out, ref), f"{name} != the gemm_pingpong = 0 kernel on {int((out != ref).sum())} of {M * N} elements"
+
+
+@pytest.mark.parametrize("K,fused", [(128, True), (64, False)])
+def test_gemm_qk_entry_launches_what_the_plan_says(K, fused):
+    """g3_gemm_qk_norm_rope_bf16 on both sides of its kernel choice: K = 128 runs the norm / RoPE (+ V^T) epilogue of the one-wave kernel and nothing else,
+    K = 64 the plain GEMM and the standalone norm / RoPE and transpose passes - as the dry run says; both against the unfused chain, at the bar of
+    test_gemm_qk_norm_rope_epilogue_matches_unfused (the fallback IS that chain: bitwise)."""
+    from gen3c_amd import _lib, ops
+    dev = _dev()
+    lib = _lib.load()
+    S, B, D = 300, 2, 256
+    g = torch.Generator(device=dev).manual_seed(S + K)
+    a = torch.randn(S * B, K, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(3 * D, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16)
+    wq, wk = [(torch.rand(128, device=dev, generator=g) + 0.5).to(torch.bfloat16) for _ in range(2)]
+    ang = torch.randn(S, 128, device=dev, generator=g) * 3
+    cos, sin = ang.cos().contiguous(), ang.sin().contiguous()
+    vt = torch.zeros((B, D // 128, 128, ops.ceil_to(S, 64)), dtype=torch.bfloat16, device=dev)
+    out = torch.full((S * B, 3 * D), 7.0, dtype=torch.bfloat16, device=dev)
+    call = _lib.GemmCall(entry=1, A=a.data_ptr(), lda=K, W=w.data_ptr(), ldw=K, C=out.data_ptr(), ldc=3 * D, M=S * B, N=3 * D, K=K, n_q=D, n_k=D,
+                         norm_q=wq.data_ptr(), norm_k=wk.data_ptr(), cos_table=cos.data_ptr(), sin_table=sin.data_ptr(), B=B, eps=1e-6, vt=vt.data_ptr(),
+                         vt_ld=vt.shape[-1])
+    grid, follow = C.c_int(0), C.c_uint(99)
+    planned = lib.g3_gemm_plan_bf16(C.byref(call), 0, C.byref(grid), C.byref(follow))
+    want = ("gemm_bf16_nt_w4_kernel<5, false>", 0) if fused else ("gemm_bf16_nt_pp_kernel<0, 2, false>", 1 | 2 | 4)  # THEN_NORM_Q | THEN_NORM_K | THEN_VT
+    assert planned is not None and (planned.decode(), follow.value, grid.value) == (*want, 3 * 3), (planned, follow.value, grid.value, _lib.last_error())
+    ops.gemm_qk_norm_rope(a, w, D, D, wq, wk, cos, sin, S, B, out=out, vt=vt)
+    ref = ops.gemm_nt(a, w)
+    ops.qk_rmsnorm_rope(ref[:, :D], wq, cos, sin, S, B, D // 128, out=ref[:, :D])
+    ops.qk_rmsnorm_rope(ref[:, D:2 * D], wk, cos, sin, S, B, D // 128, out=ref[:, D:2 * D])
+    torch.cuda.synchronize()
+    assert torch.equal(vt, ops.transpose_v(ref[:, 2 * D:], S, B, D // 128))
+    if fused:
+        assert bool((out[:, 2 * D:] == 7.0).all()), "v columns of C must stay unwritten where the epilogue writes V^T"
+        got, exp = out[:, :2 * D], ref[:, :2 * D]
+        same, diff = float((got == exp).float().mean()), float((got.float() - exp.float()).abs().max())
+        assert same > 0.995 and diff <= 2.0 ** -5 * float(exp.float().abs().max())  # at most one bf16 ulp, on a few elements
+    else:
+        assert torch.equal(out, ref)
 
 
 def _report(name, got, ref):

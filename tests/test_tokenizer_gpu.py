@@ -309,6 +309,48 @@ def test_conv_one_wave_kernel_bitwise_equals_pingpong_and_delivers_groupnorm_sta
         assert err < 2e-6, f"conv_w4={w4}: GroupNorm statistics off by {err:.2e}"
 
 
+def test_conv_entry_launches_what_the_plan_says():
+    """One geometry of the test above per "conv_w4" value: the dry run names the table row and says where the GroupNorm statistics come from (the one-wave
+    kernel's epilogue, or the statistics pass behind the ping-pong kernel) for exactly the call made; the outputs are bitwise equal across the values and the
+    statistics meet that test's bar."""
+    import ctypes as C
+    from gen3c_amd import _lib, ops
+    dev = torch.device("cuda:0")
+    lib = _lib.load()
+    kt, kh, kw, st, sh, sw, ot, oh, ow = _CONV_GEOMS["s3"]
+    K, N, T, H, W = 64, 128, 2, 9, 31
+    g = torch.Generator(device=dev).manual_seed(K + N + T)
+    x = torch.randn(T, H, W, K, device=dev, generator=g).to(torch.bfloat16)
+    w = (torch.randn(kt * kh * kw, N, K, device=dev, generator=g) / (K * kt * kh * kw) ** 0.5).to(torch.bfloat16)
+    b = torch.randn(N, device=dev, generator=g).to(torch.bfloat16)
+    r = torch.randn(T, H, W, N, device=dev, generator=g).to(torch.bfloat16)
+    rows = {1: ("gemm_bf16_nt_w4_conv_kernel<4>", 0), 2: ("gemm_bf16_nt_w4_conv_kernel<4>", 0), 0: ("gemm_bf16_nt_pp_kernel<4, 2, true>", 8)}  # 8: THEN_GN_STATS
+    outs = {}
+    try:
+        for w4, want in rows.items():
+            ops.set_option("conv_w4", w4)
+            o = torch.full((T, H, W, N), float("nan"), device=dev, dtype=torch.bfloat16)
+            stats = torch.zeros(T, 2, device=dev, dtype=torch.float64)
+            call = _lib.GemmCall(entry=3, A=x.data_ptr(), lda=K, W=w.data_ptr(), ldw=K, gate=b.data_ptr(), residual=r.data_ptr(), ldr=N, C=o.data_ptr(), ldc=N, K=K, N=N,
+                                 Ti=T, Hi=H, Wi=W, To=T, Ho=H, Wo=W, kt=kt, kh=kh, kw=kw, st=st, sh=sh, sw=sw, ot=ot, oh=oh, ow=ow, gn_stats=stats.data_ptr(), gn_rows=H * W)
+            grid, follow = C.c_int(0), C.c_uint(99)
+            planned = lib.g3_gemm_plan_bf16(C.byref(call), 0, C.byref(grid), C.byref(follow))
+            assert planned is not None and (planned.decode(), follow.value, grid.value) == (*want, 3), (w4, planned, follow.value, grid.value, _lib.last_error())
+            rc = lib.g3_conv3d_cl_gnstats_bf16(x.data_ptr(), K, w.data_ptr(), K, b.data_ptr(), r.data_ptr(), N, o.data_ptr(), N, K, N, T, H, W, T, H, W,
+                                               kt, kh, kw, st, sh, sw, ot, oh, ow, stats.data_ptr(), H * W, torch.cuda.current_stream().cuda_stream)
+            _lib.check(rc, "g3_conv3d_cl_gnstats_bf16")
+            torch.cuda.synchronize()
+            outs[w4] = (o, stats)
+    finally:
+        ops.set_option("conv_w4", 1)
+    assert torch.isfinite(outs[1][0].float()).all() and torch.equal(outs[1][0], outs[0][0]) and torch.equal(outs[2][0], outs[0][0])
+    of = outs[1][0].double().reshape(T, -1)
+    ref = torch.stack([of.sum(1), (of * of).sum(1)], dim=1)
+    for w4, (_, st_) in outs.items():
+        err = ((st_ - ref).abs() / (ref.abs() + 1.0)).max().item()
+        assert err < 2e-6, f"conv_w4={w4}: GroupNorm statistics off by {err:.2e}"
+
+
 @pytest.mark.parametrize("T,HW,C", [(16, 1000, 512), (3, 77, 64), (5, 256, 256), (1, 40, 128)])
 def test_temporal_attention_per_pixel_kernel_bitwise_equals_first_form_and_matches_fp32(T, HW, C):
     """CausalTemporalAttnBlock core (layers3d.py:386-427): the one-wave-per-pixel kernel (K / V rows of a pixel read once for all query frames)

@@ -121,8 +121,8 @@ _CONV_PATHS = {
     "w4_gaps": dict(conv_w4=1),                      # one wave per SIMD, tap change in the MFMA gaps
     "w4_stmt": dict(conv_w4=2),                      # one wave per SIMD, tap change between statements
     "pingpong": dict(conv_w4=0, gemm_pingpong=3),
-    "lds_dma": dict(conv_w4=0, gemm_pingpong=0),     # launch_variant, LDS-DMA staging
-    "direct": dict(gemm_regstage=1),                 # launch_variant, register staging (also what K % 64 != 0 takes under any options)
+    "lds_dma": dict(conv_w4=0, gemm_pingpong=0),     # gemm_bf16_nt_kernel, LDS-DMA staging
+    "direct": dict(gemm_regstage=1),                 # gemm_bf16_nt_kernel, register staging (also what K % 64 != 0 takes under any options)
 }
 
 
