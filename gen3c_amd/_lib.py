@@ -32,6 +32,7 @@ SIGNATURES = {
     "g3_last_error": [],
     "g3_abi_version": [],
     "g3_set_option": [C.c_char_p, i32],
+    "g3_get_option": [C.c_char_p, C.POINTER(i32)],
     "g3_device_info": [i32, C.POINTER(i32), C.POINTER(i32), C.c_char_p, i32],
     "g3_event_create": [C.POINTER(vp)],
     "g3_event_record": [vp, vp],
@@ -64,6 +65,11 @@ SIGNATURES = {
     "g3_self_attn_fwd_bounded_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, vp, vp, vp, i64, i64, i64, i32, i32, i32,
                                       i32, i32, f32, f32, i32, vp],
     "g3_self_attn_kernel_name": [i32, i32, i32, i32, f32, i32],
+    "g3_self_attn_fwd_bounded16_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, vp, vp, vp, i64, i64, i64, i32, i32, i32,
+                                        i32, i32, f32, f32, i32, vp],
+    "g3_self_attn16_kernel_name": [i32, i32, i32, i32, f32, i32],
+    "g3_attn_plan16_bf16": [i32, vp, i64, i64, i64, vp, f32, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, i32, i32, vp, vp, vp, vp, vp, i64, i64, i64,
+                            i32, i32, i32, i32, i32, i32, f32, f32, i32],
     "g3_self_attn_fwd_bounded_cp_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i64, i32, i32, vp, vp, vp, vp, vp, i64, i64,
                                          i64, i32, i32, i32, i32, i32, f32, f32, i32, vp],
     "g3_self_attn_cp_kernel_name": [i32, i32, i32, i32, f32, i32, i32, i32],
@@ -112,7 +118,7 @@ SIGNATURES = {
     "g3_edm_prepare_input_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     "g3_edm_cfg_euler_step_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
 }
-_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
+_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_self_attn16_kernel_name": C.c_char_p, "g3_attn_plan16_bf16": C.c_char_p, "g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
              "g3_warp_windows_workspace_bytes": C.c_size_t, "g3_render_workspace_bytes": C.c_size_t}
 
 

@@ -48,29 +48,42 @@ int g3_opt_ln_wave_rows = env_int("G3_LN_WAVE_ROWS", 0);  // norm_rope.hip: ln_m
 int g3_opt_norm_octets = env_int("G3_NORM_OCTETS", 1);  // norm_rope.hip: octet form of the per-head RMSNorm + RoPE pass (0: one group per (row, head), A/B)
 int g3_opt_gemm_unpinned = env_int("G3_GEMM_UNPINNED", 1);  // measured: pinning the LDS prefetch does not help this kernel (profiles/r1_v4_gemm_pin_ab.txt)
 
+// the A/B switches by name: the one table g3_set_option and g3_get_option share
+static int* opt_by_name(const char* name) {
+    if (!strcmp(name, "gemm_regstage")) return &g3_opt_gemm_regstage;
+    if (!strcmp(name, "gemm_wide_store")) return &g3_opt_gemm_wide_store;
+    if (!strcmp(name, "splat_tiled")) return &g3_opt_splat_tiled;
+    if (!strcmp(name, "render_overlap")) return &g3_opt_render_overlap;
+    if (!strcmp(name, "render_fused")) return &g3_opt_render_fused;
+    if (!strcmp(name, "render_exclusive")) return &g3_opt_render_exclusive;
+    if (!strcmp(name, "render_full_extent")) return &g3_opt_render_full_extent;
+    if (!strcmp(name, "gemm_pingpong")) return &g3_opt_gemm_pingpong;
+    if (!strcmp(name, "gemm_unpinned")) return &g3_opt_gemm_unpinned;
+    if (!strcmp(name, "conv_w4")) return &g3_opt_conv_w4;
+    if (!strcmp(name, "gemm_persistent")) return &g3_opt_gemm_persistent;
+    if (!strcmp(name, "gemm_deferred")) return &g3_opt_gemm_deferred;
+    if (!strcmp(name, "gemm_tokens_first")) return &g3_opt_gemm_tokens_first;
+    if (!strcmp(name, "gemm_deferred_grid")) return &g3_opt_gemm_deferred_grid;
+    if (!strcmp(name, "tok_tattn_px")) return &g3_opt_tok_tattn_px;
+    if (!strcmp(name, "gemm_rowmajor_tiles")) return &g3_opt_gemm_rowmajor_tiles;
+    if (!strcmp(name, "ln_wave_rows")) return &g3_opt_ln_wave_rows;
+    if (!strcmp(name, "norm_octets")) return &g3_opt_norm_octets;
+    if (!strcmp(name, "attn_variant")) return &g3_opt_attn_variant;
+    if (!strcmp(name, "attn_xcd_heads")) return &g3_opt_attn_xcd_heads;
+    return nullptr;
+}
+
 extern "C" int g3_set_option(const char* name, int value) {
     if (!name) return g3_set_error(G3_ERR_ARG, "g3_set_option: null name");
-    if (!strcmp(name, "gemm_regstage")) { g3_opt_gemm_regstage = value; return G3_OK; }
-    if (!strcmp(name, "gemm_wide_store")) { g3_opt_gemm_wide_store = value; return G3_OK; }
-    if (!strcmp(name, "splat_tiled")) { g3_opt_splat_tiled = value; return G3_OK; }
-    if (!strcmp(name, "render_overlap")) { g3_opt_render_overlap = value; return G3_OK; }
-    if (!strcmp(name, "render_fused")) { g3_opt_render_fused = value; return G3_OK; }
-    if (!strcmp(name, "render_exclusive")) { g3_opt_render_exclusive = value; return G3_OK; }
-    if (!strcmp(name, "render_full_extent")) { g3_opt_render_full_extent = value; return G3_OK; }
-    if (!strcmp(name, "gemm_pingpong")) { g3_opt_gemm_pingpong = value; return G3_OK; }
-    if (!strcmp(name, "gemm_unpinned")) { g3_opt_gemm_unpinned = value; return G3_OK; }
-    if (!strcmp(name, "conv_w4")) { g3_opt_conv_w4 = value; return G3_OK; }
-    if (!strcmp(name, "gemm_persistent")) { g3_opt_gemm_persistent = value; return G3_OK; }
-    if (!strcmp(name, "gemm_deferred")) { g3_opt_gemm_deferred = value; return G3_OK; }
-    if (!strcmp(name, "gemm_tokens_first")) { g3_opt_gemm_tokens_first = value; return G3_OK; }
-    if (!strcmp(name, "gemm_deferred_grid")) { g3_opt_gemm_deferred_grid = value; return G3_OK; }
-    if (!strcmp(name, "tok_tattn_px")) { g3_opt_tok_tattn_px = value; return G3_OK; }
-    if (!strcmp(name, "gemm_rowmajor_tiles")) { g3_opt_gemm_rowmajor_tiles = value; return G3_OK; }
-    if (!strcmp(name, "ln_wave_rows")) { g3_opt_ln_wave_rows = value; return G3_OK; }
-    if (!strcmp(name, "norm_octets")) { g3_opt_norm_octets = value; return G3_OK; }
-    if (!strcmp(name, "attn_variant")) { g3_opt_attn_variant = value; return G3_OK; }
-    if (!strcmp(name, "attn_xcd_heads")) { g3_opt_attn_xcd_heads = value; return G3_OK; }
+    if (int* opt = opt_by_name(name)) { *opt = value; return G3_OK; }
     return g3_set_error(G3_ERR_ARG, "g3_set_option: unknown option %s", name);
+}
+
+// the value in force: the option's default, its environment variable or the last g3_set_option, whoever called it
+extern "C" int g3_get_option(const char* name, int* value) {
+    if (!name || !value) return g3_set_error(G3_ERR_ARG, "g3_get_option: null argument");
+    if (const int* opt = opt_by_name(name)) { *value = *opt; return G3_OK; }
+    return g3_set_error(G3_ERR_ARG, "g3_get_option: unknown option %s", name);
 }
 
 extern "C" const char* g3_last_error(void) { return g_err; }

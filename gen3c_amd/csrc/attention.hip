@@ -1021,6 +1021,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_carry_kernel: the no-max form with the CP form (g3_self_attn_fwd_bounded_cp_bf16)
 #undef W4B_NM
 #undef W4B_CP
+#include "attention_w4c.hpp"  // flash_attn_fwd_w4c_nm_kernel: the plain no-max form on 16x16x32 MFMAs (g3_self_attn_fwd_bounded16_bf16)
 
 }  // namespace
 
@@ -1040,11 +1041,14 @@ struct AttnCall {
     int kv_dense = 0; const void* q_norm_w = nullptr; float q_norm_eps = 0.f;
     const float* carry_o = nullptr; const float* carry_lse = nullptr; int kv_skip_begin = 0, kv_skip_len = 0;
     float logit_bound = 0.f;
+    int mfma16 = 0;  // g3_self_attn_fwd_bounded16_bf16: the 16x16x32 tile loop where the plain no-max kernel would run
     void* stream = nullptr;
 };
 
 // The kernel table: one row per instantiation. The reported name, the hipFuncSetAttribute pass and the launch all come from here.
 struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_rows; };
+// (the row only g3_self_attn_fwd_bounded16_bf16 reaches, apart from the rows the recorded launcher decisions cover: tests/golden/attn_plan_parent.json)
+#define G3_ATTN_KERNELS16(X) X(AK_W4C_NM, W4_THREADS, W4_BQ, flash_attn_fwd_w4c_nm_kernel)
 #define G3_ATTN_KERNELS(X) \
     X(AK_V1_L, NTHREADS, BQ, flash_attn_fwd_kernel<0>) X(AK_V1_S, NTHREADS, BQ, flash_attn_fwd_kernel<1>) \
     X(AK_V2_L, NTHREADS, BQ, flash_attn_fwd_v2_kernel<0>) X(AK_V2_S, NTHREADS, BQ, flash_attn_fwd_v2_kernel<1>) \
@@ -1059,8 +1063,8 @@ struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_row
     X(AK_W4BX_NM_CARRY, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_carry_kernel<true>)
 #define G3_ATTN_ID(ID, THREADS, Q_ROWS, ...) ID,
 #define G3_ATTN_ROW(ID, THREADS, Q_ROWS, ...) {#__VA_ARGS__, &__VA_ARGS__, THREADS, Q_ROWS},
-enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) AK_COUNT };
-static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW)};
+enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) G3_ATTN_KERNELS16(G3_ATTN_ID) AK_COUNT };
+static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW) G3_ATTN_KERNELS16(G3_ATTN_ROW)};
 #undef G3_ATTN_ID
 #undef G3_ATTN_ROW
 
@@ -1219,6 +1223,9 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     // only; g3_self_attn_fwd_bounded_cp_bf16: also with segmented V^T, and with a carry-in state or a skipped key range. Everything else runs as it always did.
     const bool no_max = attn_bound_usable(p.logit_bound_log2) && (c.entry == G3_ATTN_ENTRY_BOUNDED_CP || (!cp_form && c.vt_seg_len == 0));
     plan.kernel = &attn_kernel_for(variant, c.Skv, cp_form, no_max, c.carry_o || c.kv_skip_len > 0);
+    // the 16x16x32 tile loop covers the plain no-max kernel's bf16-output launches only (that row already means: variant 11, S_kv % 64 == 0, bound in
+    // range, plain V^T, no carry, no skip); everything else keeps the kernel chosen above
+    if (c.mfma16 && plan.kernel == &attn_kernels[AK_W4BX_NM] && !c.o_partial) plan.kernel = &attn_kernels[AK_W4C_NM];
     plan.grid = dim3((c.Sq + plan.kernel->q_rows - 1) / plan.kernel->q_rows, c.H, c.B);
     if (variant == 10 || variant == 11) {  // w4b (attention_w4b.hpp): optionally a 1-D grid that gives every XCD its own (batch, head) pairs
         p.grid_q = (int)plan.grid.x; p.n_hb = c.H * c.B;
@@ -1302,6 +1309,21 @@ extern "C" int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64
     return attn_launch(c);
 }
 
+/* ---- the same entry with the 16x16x32 tile loop where the plain no-max kernel would run with a bf16 output; every other call IS the entry above ---------- */
+extern "C" int g3_self_attn_fwd_bounded16_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                               int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
+                                               int vt_seg_len, int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row,
+                                               int64_t o_batch, int64_t o_head, int Sq, int Skv, int B, int H, int head_dim, float softmax_scale,
+                                               float logit_bound, int variant, void* stream) {
+    AttnCall c;
+    c.entry = G3_ATTN_ENTRY_BOUNDED;
+    c.mfma16 = 1;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.vt_seg_len = vt_seg_len; c.vt_seg_stride = vt_seg_stride; c.o_partial = o_partial; c.lse = lse; c.variant = variant; c.logit_bound = logit_bound;
+    c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+    return attn_launch(c);
+}
+
 /* ---- carry-in state + skipped key range (context parallelism without a merge pass) --------------------------------------------------------- */
 extern "C" int g3_flash_attn_fwd_carry_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
                                             int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head,
@@ -1335,7 +1357,7 @@ extern "C" int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, in
 }
 
 /* ---- dry run: the kernel a call to `entry` with these arguments would launch, or NULL with the call's own refusal in g3_last_error(). Never touches HIP. ---- */
-extern "C" const char* g3_attn_plan_bf16(int entry, const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* q_norm_weight, float q_norm_eps,
+static const char* attn_plan_name(int mfma16, int entry, const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* q_norm_weight, float q_norm_eps,
                                          const void* k, int64_t k_row, int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch,
                                          int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
                                          const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
@@ -1351,9 +1373,24 @@ extern "C" const char* g3_attn_plan_bf16(int entry, const void* q, int64_t q_row
     if (entry >= G3_ATTN_ENTRY_EX) { c.o_partial = o_partial; c.lse = lse; c.variant = variant; }
     if (entry == G3_ATTN_ENTRY_BOUNDED || entry == G3_ATTN_ENTRY_BOUNDED_CP) c.logit_bound = logit_bound;
     if (cp_form) { c.kv_skip_begin = kv_skip_begin; c.kv_skip_len = kv_skip_len; c.carry_o = carry_o; c.carry_lse = carry_lse; }
+    c.mfma16 = mfma16 && entry == G3_ATTN_ENTRY_BOUNDED;
     AttnPlan plan;
     return attn_plan(c, plan) == G3_OK ? plan.kernel->name : nullptr;
 }
+#define G3_ATTN_PLAN_PARAMS                                                                                                                                   \
+    int entry, const void *q, int64_t q_row, int64_t q_batch, int64_t q_head, const void *q_norm_weight, float q_norm_eps, const void *k, int64_t k_row,      \
+        int64_t k_batch, int64_t k_head, const void *vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride,            \
+        int kv_skip_begin, int kv_skip_len, const float *carry_o, const float *carry_lse, void *o, float *o_partial, float *lse, int64_t o_row,               \
+        int64_t o_batch, int64_t o_head, int Sq, int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant
+#define G3_ATTN_PLAN_ARGS                                                                                                                                      \
+    entry, q, q_row, q_batch, q_head, q_norm_weight, q_norm_eps, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, vt_seg_len, vt_seg_stride,          \
+        kv_skip_begin, kv_skip_len, carry_o, carry_lse, o, o_partial, lse, o_row, o_batch, o_head, Sq, Skv, kv_dense, B, H, head_dim, softmax_scale,           \
+        logit_bound, variant
+extern "C" const char* g3_attn_plan_bf16(G3_ATTN_PLAN_PARAMS) { return attn_plan_name(0, G3_ATTN_PLAN_ARGS); }
+/* g3_attn_plan_bf16 with entry G3_ATTN_ENTRY_BOUNDED standing for g3_self_attn_fwd_bounded16_bf16 (every other entry: the same answer) */
+extern "C" const char* g3_attn_plan16_bf16(G3_ATTN_PLAN_PARAMS) { return attn_plan_name(1, G3_ATTN_PLAN_ARGS); }
+#undef G3_ATTN_PLAN_PARAMS
+#undef G3_ATTN_PLAN_ARGS
 
 /* ---- the shapes-only name functions: the plan's own choice code for a call with plain, addressable operands (g3_attn_plan_bf16 answers for a real call) ---- */
 extern "C" const char* g3_flash_attn_kernel_name_ex(int Sq, int Skv, int B, int H, int variant) {
@@ -1364,6 +1401,12 @@ extern "C" const char* g3_flash_attn_kernel_name(int Sq, int Skv, int B, int H) 
 
 extern "C" const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant) {
     return attn_kernel_for(attn_resolve_variant(Sq, Skv, B, H, variant), Skv, false, attn_bound_usable(attn_bound_log2(logit_bound)), false).name;
+}
+
+/* the kernel g3_self_attn_fwd_bounded16_bf16 launches for a bf16-output call with plain V^T, from shapes only */
+extern "C" const char* g3_self_attn16_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant) {
+    const AttnKernel& kn = attn_kernel_for(attn_resolve_variant(Sq, Skv, B, H, variant), Skv, false, attn_bound_usable(attn_bound_log2(logit_bound)), false);
+    return (&kn == &attn_kernels[AK_W4BX_NM] ? attn_kernels[AK_W4C_NM] : kn).name;
 }
 
 // Skv: the attended keys (a skipped range not counted); segmented: V^T in key segments (the name does not depend on it: both forms run the same

@@ -44,6 +44,16 @@ _V_OPERAND_SWAP = __import__("os").environ.get("G3_V_OPERAND_SWAP", "1") != "0"
 # of the q / k RMSNorms by _pack() - "fa_bound", see _qk_logit_bounds. The one-wave-per-SIMD kernel then runs without a running row maximum; a block whose
 # bound is beyond the kernel's range (max|w_q| * max|w_k| above ~3.6), and every launch that takes another kernel, runs as before. False: ops.flash_attn (A/B, tests).
 _SELF_ATTN_LOGIT_BOUND = True
+# Those bounded launches (the single-GPU branch and the head_parallel schedule) may ask for the no-max kernel's tile loop on 16x16x32 MFMAs
+# (ops.self_attn_bounded(mfma16=True), flash_attn_fwd_w4c_nm_kernel): the same arithmetic at the same rounding points, on the MFMA shape the chip clocks
+# higher under load (profiles/mfma_shape_probe.txt, profiles/attn_mfma16_ab.txt). Launches outside that kernel's form run what they ran.
+# "auto" (default): ask for it where the library chooses the attention kernel itself; a process-wide "attn_variant" option (its environment variable or
+# g3_set_option, read back from the library by ops.option: A/B runs and tests that name one kernel family) keeps the kernel it names. True: always ask. False: never (A/B, tests).
+_SELF_ATTN_MFMA16 = "auto"
+
+
+def _self_attn_mfma16() -> bool:
+    return _SELF_ATTN_MFMA16 is True or (_SELF_ATTN_MFMA16 == "auto" and ops.option("attn_variant") == 0)
 # margin on the bound for the four bf16 roundings of q and k between the norm and the MFMA (norm output, RoPE output, the softmax scale folded into Q):
 # each is within 2^-8 relative; a CPU emulation with unit weights and aligned q / k rows reached 16.35 (log2 domain) against 16.81
 _LOGIT_BOUND_MARGIN = 1.03
@@ -620,6 +630,7 @@ class VideoExtendGeneralDIT(nn.Module):
                 qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
                                          wq=_mx_rows(blk, "fa_qkv", slice(None)))
                 pending = self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
+                self._cp_attn.mfma16 = _self_attn_mfma16()  # (head_parallel only)
                 # (the bound is read by head_parallel, whose launches see all keys of their heads at once as the single-GPU call below, and by the other
                 # schedules when ContextParallelAttention's `bounded` switch is on)
                 o = self._cp_attn.finish(qkv[:, :D], pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)
@@ -630,6 +641,7 @@ class VideoExtendGeneralDIT(nn.Module):
                 kv = _project_norm_rope(h, blk["fa_qkv"][D:], 0, D, None, blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
                                         wq=_mx_rows(blk, "fa_qkv", slice(D, None)))  # [S*B, 2D]: k normalised + rotated, v plain
                 pending = self._cp_attn.start(kv[:, :D], kv[:, D:], S, B, nH)
+                self._cp_attn.mfma16 = _self_attn_mfma16()  # (head_parallel only)
                 q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH, hq=hq,
                                        wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
                 o = self._cp_attn.finish(q, pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)  # (read with `bounded` only)
@@ -659,7 +671,7 @@ class VideoExtendGeneralDIT(nn.Module):
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
                 if _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
-                    o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"])
+                    o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"], mfma16=_self_attn_mfma16())
                 else:
                     o = ops.flash_attn(q, k, vt, S, S, B, nH)
             self._linear(o, blk, "fa_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)

@@ -24,6 +24,14 @@ def set_option(name: str, value: int):
     _lib.check(_lib.load().g3_set_option(name.encode(), int(value)), "g3_set_option")
 
 
+def option(name: str) -> int:
+    """The value of a switch in force in the C library (g3_get_option): its default, its environment variable or the last g3_set_option, whoever called it."""
+    import ctypes as C
+    v = C.c_int(0)
+    _lib.check(_lib.load().g3_get_option(name.encode(), C.byref(v)), "g3_get_option")
+    return int(v.value)
+
+
 def enable_kernel_timers(on: bool = True):
     global _KERNEL_TIMERS
     _KERNEL_TIMERS = [] if on else None
@@ -492,20 +500,24 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv:
 
 
 def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv: int, B: int, H: int, logit_bound: float,
-                      out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False, carry=None, kv_skip=None):
+                      out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, variant: int = 0, partial: bool = False, carry=None, kv_skip=None,
+                      mfma16: bool = False):
     """flash_attn (operands, `out`, `variant` and `partial` as there) for callers that guarantee
     |q . k| * softmax_scale <= logit_bound for every query / key pair, e.g. q and k behind a per-head RMSNorm:
     |q . k| / sqrt(128) <= sqrt(128) * max|w_q| * max|w_k|. Where the one-wave-per-SIMD kernel (variant 11) is the choice and
     0 < logit_bound * log2(e) <= 60 it runs without its running row maximum (g3_self_attn_fwd_bounded_bf16); every other call is flash_attn's.
     The key-sharded forms of flash_attn - 5-D segmented V^T, carry=, kv_skip=, partial=True with `out` - go to g3_self_attn_fwd_bounded_cp_bf16:
-    the no-max kernels where they apply (variant 11, the bound in range), else exactly flash_attn's carry call (variant 0, 4 or 11 only)."""
+    the no-max kernels where they apply (variant 11, the bound in range), else exactly flash_attn's carry call (variant 0, 4 or 11 only).
+    mfma16=True: g3_self_attn_fwd_bounded16_bf16 - the no-max kernel's tile loop on 16x16x32 MFMAs where the plain no-max kernel would run with a bf16
+    output (equal to rounding, not bit for bit); every other call, the key-sharded forms included, is the call without the flag."""
     if vt.dim() == 5 or carry is not None or kv_skip is not None or (partial and out is not None):
         return _attn_call("bounded_cp", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, carry=carry, kv_skip=kv_skip, logit_bound=logit_bound)
-    return _attn_call("bounded", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, logit_bound=logit_bound)
+    return _attn_call("bounded16" if mfma16 else "bounded", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, logit_bound=logit_bound)
 
 
 # The launching entry points ops uses: (enum g3_attn_entry, symbol, its arguments by name in call order - the stream follows). g3_attn_plan_bf16 takes
-# the union (_ATTN_PLAN_ARGS), so the kernel a timer records is the dry run's answer for the very arguments launched.
+# the union (_ATTN_PLAN_ARGS), so the kernel a timer records is the dry run's answer for the very arguments launched ("bounded16": g3_attn_plan16_bf16,
+# the dry run in which entry 4 stands for g3_self_attn_fwd_bounded16_bf16).
 _AQ, _AK, _AVT = ("q", "q_row", "q_batch", "q_head"), ("k", "k_row", "k_batch", "k_head"), ("vt", "vt_row", "vt_batch", "vt_head", "vt_seg_len", "vt_seg_stride")
 _AOUT, _ASHAPE = ("o", "o_partial", "lse", "o_row", "o_batch", "o_head"), ("Sq", "Skv", "B", "H", "head_dim", "softmax_scale")
 _ACP = ("kv_skip_begin", "kv_skip_len", "carry_o", "carry_lse")
@@ -513,6 +525,7 @@ _ATTN_ENTRIES = {
     "cross": (2, "g3_cross_attn_fwd_bf16", _AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq", "Skv", "kv_dense") + _ASHAPE[2:]),
     "ex": (3, "g3_flash_attn_fwd_ex_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("variant",)),
     "bounded": (4, "g3_self_attn_fwd_bounded_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
+    "bounded16": (4, "g3_self_attn_fwd_bounded16_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
     "carry": (5, "g3_flash_attn_fwd_carry_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("variant",)),
     "bounded_cp": (6, "g3_self_attn_fwd_bounded_cp_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("logit_bound", "variant")),
 }
@@ -573,7 +586,8 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
             meta.update(kv_dense=kv_dense, q_norm=q_norm_weight is not None)
         elif entry in ("carry", "bounded_cp"):
             meta.update(carry=carry is not None, kv_skip=skip_len)
-        meta["kernel"] = lib.g3_attn_plan_bf16(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
+        plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
+        meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
         _KERNEL_TIMERS.append(("flash_attn_fwd", meta, timer))
     return (out, lse) if partial else out
 

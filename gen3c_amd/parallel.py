@@ -196,8 +196,8 @@ def _default_backend():
             q, k, vt, Sq, Skv, B, H, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
         scatter_heads=lambda q, k, v, H, n_dest, head0, Hg: ops.cp_scatter_heads(q, k, v, H, n_dest, head0, Hg),
         gather_heads=lambda x, out, H, head0: ops.cp_gather_heads(x, out, H, head0),
-        attention_bounded=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out, variant=0: ops.self_attn_bounded(
-            q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant),
+        attention_bounded=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out, variant=0, mfma16=False: ops.self_attn_bounded(
+            q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant, mfma16=mfma16),
         # the key-sharded forms with a logit bound (g3_self_attn_fwd_bounded_cp_bf16): what "attention", "attention_partial" and "attention_carry" take
         attention_bounded_cp=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out=None, carry=None, kv_skip=None, partial=False, variant=0: ops.self_attn_bounded(
             q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
@@ -264,6 +264,9 @@ class ContextParallelAttention:
         self.schedule = schedule
         self.kernel = kernel
         self.bounded = bool(bounded)
+        # head_parallel only (its launches see all keys of their heads at once, as the single-GPU call): ask "attention_bounded" for the 16x16x32 tile
+        # loop (ops.self_attn_bounded(mfma16=True)). The DiT sets it from dit._SELF_ATTN_MFMA16; the backend is passed the keyword only when it is on.
+        self.mfma16 = False
         self.stats = None
         self.effective = None  # set by finish(): dict(schedule, kernel, head_groups) of the configuration that actually ran
         self.effective_bounded = False  # set by finish(): the key-sharding schedules' launches went through "attention_bounded_cp" (see `bounded`)
@@ -398,7 +401,7 @@ class ContextParallelAttention:
                     ob = torch.empty_like(qr)  # [S_all*B, Hg*128] in row blocks of `rows`: already one chunk per destination rank
                     qa, ka, oa = (t.view(S_all * B, Hg * 128) for t in (qr, kr, ob))
                     if logit_bound > 0:
-                        be["attention_bounded"](qa, ka, vt, S_all, S_all, B, Hg, logit_bound, oa, variant=variant)
+                        be["attention_bounded"](qa, ka, vt, S_all, S_all, B, Hg, logit_bound, oa, variant=variant, **(dict(mfma16=True) if self.mfma16 else {}))
                     else:
                         be["attention"](qa, ka, vt, S_all, S_all, B, Hg, oa, variant=variant)
                     orecv = torch.empty_like(ob)

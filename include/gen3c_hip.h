@@ -45,6 +45,8 @@ int g3_abi_version(void);
  * "render_exclusive" (1: extent pre-pass + single-writer texels resolved inside the splat - a quarter less memory traffic, 18 % slower; default 0),
  * "tok_tattn_px". Outputs do not depend on them. */
 int g3_set_option(const char* name /*host*/, int value);
+/* The value of a switch in force in this process (its default, its environment variable or the last g3_set_option). */
+int g3_get_option(const char* name /*host*/, int* value /*host*/);
 int g3_device_info(int device, int* cu_count, int* is_gfx950, char* arch_name /*host*/, int arch_name_len);
 
 /* hipEvent helpers (opaque handles) so a host can time a stream without linking HIP itself. */
@@ -191,6 +193,17 @@ int g3_self_attn_fwd_bounded_bf16(const void* q, int64_t q_row, int64_t q_batch,
                                   int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
                                   int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant, void* stream);
 const char* g3_self_attn_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant);
+/* g3_self_attn_fwd_bounded_bf16 with the tile loop on 16x16x32 MFMAs (flash_attn_fwd_w4c_nm_kernel; the chip holds a higher clock on that shape,
+ * profiles/mfma_shape_probe.txt) where that call would launch flash_attn_fwd_w4b_nm_kernel<true> with a bf16 output (o, not o_partial): the same
+ * function, P rounded to bf16, row sums and O accumulated in fp32, so the result agrees to rounding, not bit for bit. In every other case - a
+ * partial output, segments, a bound out of range, another variant, S_kv % 64 != 0 - the call IS g3_self_attn_fwd_bounded_bf16: the same kernel,
+ * bit for bit, the same refusals. g3_self_attn16_kernel_name is g3_self_attn_kernel_name for this entry (a bf16-output call);
+ * g3_attn_plan16_bf16 is g3_attn_plan_bf16 with G3_ATTN_ENTRY_BOUNDED standing for this entry. */
+int g3_self_attn_fwd_bounded16_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                    int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, int vt_seg_len,
+                                    int64_t vt_seg_stride, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head,
+                                    int Sq, int Skv, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant, void* stream);
+const char* g3_self_attn16_kernel_name(int Sq, int Skv, int B, int H, float logit_bound, int variant);
 
 /* Carry-in form of g3_flash_attn_fwd_ex_bf16: a row's keys in a CHAIN of launches with no merge pass - the context-parallel schedule that
  * TransformerEngine's CP attention runs behind attn_op.set_context_parallel_group (general_dit.py:536-541, module/attention.py:282-297) keeps
@@ -249,6 +262,12 @@ const char* g3_attn_plan_bf16(int entry, const void* q, int64_t q_row, int64_t q
                               int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
                               const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
                               int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant);
+/* The same dry run with G3_ATTN_ENTRY_BOUNDED standing for g3_self_attn_fwd_bounded16_bf16 (every other entry: g3_attn_plan_bf16's answer). */
+const char* g3_attn_plan16_bf16(int entry, const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* q_norm_weight, float q_norm_eps,
+                                const void* k, int64_t k_row, int64_t k_batch, int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch,
+                                int64_t vt_head, int vt_seg_len, int64_t vt_seg_stride, int kv_skip_begin, int kv_skip_len, const float* carry_o,
+                                const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
+                                int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant);
 
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,

@@ -37,7 +37,8 @@ def _back_branch(v, hdr):
 
 
 # the one-wave-per-SIMD instantiations attention.hip launches: each must be in the assembly (and is then audited like every flash_attn_fwd kernel found there)
-W4B_KERNELS = ("w4b_kernel<Lb0E>", "w4b_kernel<Lb1E>", "w4b_carry_kernel<Lb1E>", "w4b_nm_kernel<Lb1E>", "w4b_nm_carry_kernel<Lb1E>")  # (names as audit() forms them)
+W4B_KERNELS = ("w4b_kernel<Lb0E>", "w4b_kernel<Lb1E>", "w4b_carry_kernel<Lb1E>", "w4b_nm_kernel<Lb1E>", "w4b_nm_carry_kernel<Lb1E>",
+               "w4c_nm_kernel<>")  # (names as audit() forms them; w4c: attention_w4c.hpp, not a template)
 
 
 def audit(asm_text: str):
@@ -58,7 +59,7 @@ def audit(asm_text: str):
         pending = {}
         in_asm = False
         owned_agprs = "w4" in name_full.get(name, "")
-        owned_limit = 256 if "w4b" in name_full.get(name, "") else 192  # w4b also owns the fragment ring a[192:255]
+        owned_limit = 256 if ("w4b" in name_full.get(name, "") or "w4c" in name_full.get(name, "")) else 192  # w4b / w4c also own the fragment ring a[192:255]
         hdr0 = [i for i, l in enumerate(v) if "Inner Loop Header" in l]
         loop_lo = hdr0[0] if hdr0 else len(v)
         loop_end = max([i for i, l in enumerate(v) if "in Loop: Header" in l] + [_back_branch(v, hdr0[0]) if hdr0 else 0])

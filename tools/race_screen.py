@@ -3,7 +3,8 @@ product library against the same sources built with -DG3_AB_JITTER=<n> (pseudo-r
 boundaries) and demands BITWISE equal outputs.
   build (here, before gpurun):  python tools/race_screen.py --build [n]
   run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]
-                                                            [--bounded-cp-only: the no-max key-sharded attention section alone]"""
+                                                            [--bounded-cp-only: the no-max key-sharded attention section alone]
+                                                            [--mfma16-only: the 16x16x32 no-max attention section alone]"""
 import ctypes as C
 import math
 import os
@@ -37,7 +38,8 @@ st = torch.cuda.current_stream().cuda_stream
 g = torch.Generator(device=dev).manual_seed(3)
 bad = 0
 ONLY_BCP = "--bounded-cp-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded_cp_bf16
-ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP  # run only the last section (the launches that emit MXFP8)
+ONLY_W4C = "--mfma16-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded16_bf16
+ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP or ONLY_W4C  # run only the last section (the launches that emit MXFP8)
 
 
 def both(fn):
@@ -162,6 +164,29 @@ for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)] if (
             report(f"bounded {'carry-in + skip' if cp_form else 'segmented V^T'} form ({name}) S_local={Sl} segs={nseg} rank={rank} H={H} {'fp32 partial' if partial else 'bf16'}", a, b)
     del q, k, v, vt
 
+# ---- the no-max kernel on 16x16x32 MFMAs (g3_self_attn_fwd_bounded16_bf16, flash_attn_fwd_w4c_nm_kernel): the DiT step's launch, an odd tile count with a
+# ragged last query block, a single tile; q, k RMS-normalised per head so that the bound holds
+for (Sq, Skv, H) in [(56320, 56320, 4), (320, 192, 2), (256, 64, 8)] if (ONLY_W4C or not ONLY_MX) else []:
+    rms = lambda x: (x.view(x.shape[0], H, 128) * torch.rsqrt(x.view(x.shape[0], H, 128).pow(2).mean(-1, keepdim=True))).reshape(x.shape[0], H * 128)
+    q = rms(torch.randn(Sq, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    k = rms(torch.randn(Skv, H * 128, device=dev, generator=g)).to(torch.bfloat16)
+    v = torch.randn(Skv, H * 128, device=dev, generator=g).to(torch.bfloat16)
+    vt = ops.transpose_v(v, Skv, 1, H)
+    ld = vt.shape[-1]
+    bound = 128 / math.sqrt(128) * 1.03
+    name = base.g3_self_attn16_kernel_name(Sq, Skv, 1, H, bound, 11).decode()
+    assert name == "flash_attn_fwd_w4c_nm_kernel", name
+
+    def run(lib):
+        o = torch.empty_like(q)
+        rc = lib.g3_self_attn_fwd_bounded16_bf16(q.data_ptr(), H * 128, H * 128, 128, k.data_ptr(), H * 128, H * 128, 128, vt.data_ptr(), ld, H * 128 * ld, 128 * ld, 0, 0,
+                                                 o.data_ptr(), None, None, H * 128, H * 128, 128, Sq, Skv, 1, H, 128, 1.0 / math.sqrt(128), bound, 11, st)
+        assert rc == 0, lib.g3_last_error()
+        return o
+    a, b = both(run)
+    report(f"no-max 16x16x32 form ({name}) Sq={Sq} Skv={Skv} H={H}", a, b)
+    del q, k, v, vt
+
 # ---- GEMM: every K-loop structure x epilogues x ragged shapes
 for (M, N, K, epi) in [] if ONLY_MX else [(56320, 4096, 4096, 2), (7040, 12288, 4096, 0), (4096, 16384, 4096, 1), (3000, 4096, 16384, 2), (513, 264, 192, 3), (300, 520, 128, 0),
                        (256, 256, 64, 0), (8192, 12288, 4096, 0), (16384, 16384, 4096, 1), (8448, 4096, 2432, 2)]:
@@ -256,7 +281,7 @@ if "--no-tokenizer" not in sys.argv and not ONLY_MX:
 # ---- the producers that emit MXFP8 from their registers (mxfp8_producers = "fused"): the GEMM with MXFP8 output (its K loop carries the jitter; the epilogue
 # transposes through each wave's own LDS slice and quantises across lane quads) and the two LayerNorm forms, plain and with the position embedding
 LN_WAVE_START = int(os.environ.get("G3_LN_WAVE_ROWS", "0"))  # what both libraries start with (csrc/api.hip); restored after each case
-for (M, N, K, epi) in [] if ONLY_BCP else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
+for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C) else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
     aq, as_ = ops.quant_mxfp8(torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16))
     wq, ws = ops.quant_mxfp8((torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16))
 
@@ -270,7 +295,7 @@ for (M, N, K, epi) in [] if ONLY_BCP else [(14080, 16384, 4096, 1), (7040, 4096,
     a, b = both(run)
     report(f"gemm_mxfp8 with MXFP8 output {M}x{N}x{K} epi{epi}", a, b)
     del aq, as_, wq, ws
-for (T_, Hp, Wp, B_, D_, wave) in [] if ONLY_BCP else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
+for (T_, Hp, Wp, B_, D_, wave) in [] if (ONLY_BCP or ONLY_W4C) else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
     rows = T_ * Hp * Wp * B_
     x_ = torch.randn(rows, D_, device=dev, generator=g).to(torch.bfloat16)
     pe = (0.3 * torch.randn(T_ * Hp * Wp, D_, device=dev, generator=g)).to(torch.bfloat16)
