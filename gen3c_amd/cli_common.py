@@ -48,7 +48,12 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--width", type=int, default=1280)
     p.add_argument("--fps", type=int, default=24)
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--num_gpus", type=int, default=1, help="context-parallel ranks (launch with torchrun --nproc_per_node=N)")
+    p.add_argument("--num_gpus", type=int, default=1, help="context-parallel ranks (launch with torchrun --nproc_per_node=N); with --cfg_parallel the total "
+                   "rank count: 2 guidance branches x num_gpus / 2 context-parallel ranks")
+    p.add_argument("--cfg_parallel", action="store_true",
+                   help="with an even --num_gpus: the conditional and the unconditional branch of every denoise step run on separate rank groups of "
+                        "num_gpus / 2 context-parallel ranks each and exchange only the network output (opt-in, default off; same output bit for "
+                        "bit; same as G3_CFG_PARALLEL=1)")
     p.add_argument("--dit_precision", choices=("bf16", "mxfp8", "mxfp6"), default="bf16",
                    help="precision of the DiT's six per-block linears: bf16 (default, the parity path), mxfp8 (opt-in MXFP8 matrix cores) or mxfp6 "
                         "(opt-in MXFP6 e2m3 operands on the same matrix cores at twice the rate); both outside the parity statement, DESIGN.md "
@@ -73,6 +78,28 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--random_init", action="store_true", help="random weights instead of checkpoints (plumbing tests)")
     p.add_argument("--tiny", action="store_true", help="a small DiT/tokenizer configuration and a 9-frame chunk (plumbing tests; with --random_init or a matching checkpoint_dir)")
     return p
+
+
+def resolve_parallel_layout(num_gpus: int, cfg_parallel: bool, latent_frames: int):
+    """--num_gpus (the total rank count) and --cfg_parallel -> (cfg, cp): guidance-branch groups x context-parallel ranks per group. Without
+    --cfg_parallel that is (1, num_gpus), unchecked as before (the frame split itself refuses a cp that does not divide the latent frames). With it
+    the world is 2 x cp: an odd rank count and a cp that does not divide the latent frames are refused here, with the counts that work."""
+    if not cfg_parallel:
+        return 1, num_gpus
+    valid = [2 * cp for cp in range(1, latent_frames + 1) if latent_frames % cp == 0]
+    if num_gpus < 2 or num_gpus % 2 != 0:
+        raise ValueError(f"--cfg_parallel splits the ranks into 2 guidance branches: --num_gpus {num_gpus} is not an even count >= 2 "
+                         f"(valid with {latent_frames} latent frames: {valid})")
+    cp = num_gpus // 2
+    if latent_frames % cp != 0:
+        raise ValueError(f"--cfg_parallel with --num_gpus {num_gpus} is 2 x cp = {cp}, and {cp} does not divide the {latent_frames} latent frames "
+                         f"(valid with {latent_frames} latent frames: {valid})")
+    return 2, cp
+
+
+def cfg_parallel_requested(args) -> bool:
+    """--cfg_parallel, or G3_CFG_PARALLEL=1 in the environment (opt-in, default off)."""
+    return bool(getattr(args, "cfg_parallel", False)) or os.environ.get("G3_CFG_PARALLEL", "0").strip() not in ("", "0")
 
 
 def log_ignored_flags(args, log=print) -> List[str]:
@@ -169,9 +196,11 @@ class Session:
             args.num_video_frames = self.chunk
         assert (args.num_video_frames - 1) % self.step_frames == 0, f"num_video_frames must be N*{self.step_frames}+1"  # gen3c_single_image.py:112
         local = 0
+        # (cfg, cp): 1 x num_gpus unless CFG-parallel is asked for; the tokenizers here compress 8 frames into one latent frame after the first
+        self.cfg_size, self.cp_size = resolve_parallel_layout(args.num_gpus, cfg_parallel_requested(args), 1 + (self.chunk - 1) // 8)
         if args.num_gpus > 1:
             local = init_distributed("nccl")
-            parallel_state.initialize_model_parallel(context_parallel_size=args.num_gpus)
+            parallel_state.initialize_model_parallel(context_parallel_size=self.cp_size, cfg_parallel_size=self.cfg_size)
         self.dev = dev = torch.device(f"cuda:{local}")
         torch.cuda.set_device(dev)
         H, W = args.height, args.width
@@ -192,18 +221,28 @@ class Session:
             net.load_state_dict({k[len("net."):]: v for k, v in sd.items() if k.startswith("net.")}, strict=True)
             tk.load_weights(os.path.join(args.checkpoint_dir, getattr(args, "tokenizer_dir", "Cosmos-Tokenize1-CV8x8x8-720p")))
         self.cp_group = None  # also shards the renderer's item pairs and the tokenizer encodes of a chunk
-        if args.num_gpus > 1:
+        self.cfg_group = None  # CFG-parallel: this rank's pair {r, r + cp}
+        if self.cp_size > 1:  # (= num_gpus without CFG-parallel; cfg 2 x cp 1 has no K / V exchange and no context-parallel machinery at all)
             self.cp_group = parallel_state.get_context_parallel_group()
             net.enable_context_parallel(self.cp_group)
             if getattr(args, "cp_logit_bound", False):
                 net._cp_attn.configure(bounded=True)
+        if self.cfg_size > 1:
+            self.cfg_group = parallel_state.get_cfg_parallel_group()
+            print(f"[gen3c_amd] --cfg_parallel: 2 guidance branches x {self.cp_size} context-parallel rank(s); this rank runs the "
+                  f"{'conditional' if parallel_state.get_cfg_parallel_rank() == 0 else 'unconditional'} branch")
+        # the group the chunk's replicated stages (render item pairs, tokenizer encodes) are split over: every rank of the job
+        self.shard_group = parallel_state.get_model_parallel_group() if self.cfg_size > 1 else self.cp_group
         if getattr(args, "dit_precision", "bf16") != "bf16":
             net.set_linear_precision(args.dit_precision)
             print(f"[gen3c_amd] --dit_precision {args.dit_precision}: the DiT block linears run on {args.dit_precision.upper()} operands; this mode is "
                   f"outside the bf16 parity statement (DESIGN.md section {'10' if args.dit_precision == 'mxfp8' else '10.2'})")
         net.set_mxfp8_producers(getattr(args, "dit_mxfp8_producers", "separate"))  # inert under bf16 and mxfp6
         self.net, self.tokenizer = net, tk
-        self.model = DiffusionGen3CModel(net, tk, latent_shape=(16, tk.get_latent_num_frames(self.chunk), H // 8, W // 8))
+        self.model = DiffusionGen3CModel(net, tk, latent_shape=(16, tk.get_latent_num_frames(self.chunk), H // 8, W // 8),
+                                         shard_group=self.shard_group if self.cfg_size > 1 else None)
+        if self.cfg_group is not None:
+            self.model.denoiser.enable_cfg_parallel(self.cfg_group)
         self.pipe = Gen3cPipeline(self.model, guidance=args.guidance, num_steps=args.num_steps, height=H, width=W, fps=args.fps,
                                   num_video_frames=self.chunk, seed=args.seed)
         log_ignored_flags(args)
@@ -260,6 +299,7 @@ class Session:
         if self.args.num_gpus > 1:
             import torch.distributed as dist
             from .parallel import parallel_state
+            self.model.denoiser.disable_cfg_parallel()
             parallel_state.destroy_model_parallel()
             if dist.is_initialized():
                 dist.destroy_process_group()

@@ -88,7 +88,7 @@ class Gen3cPersistentModel:
             self.cache = renderer.Cache4D(input_image=image.clone(), input_depth=depth, input_mask=mask, input_w2c=w2c, input_intrinsics=Kt,
                                           input_format=["F", "C", "H", "W"], **common)
             seeding = image
-        self.cache.shard_group = self.session.cp_group  # multi-GPU: render item pairs are split over the ranks
+        self.cache.shard_group = self.session.shard_group  # multi-GPU: render item pairs are split over the ranks
         if seeding.shape[2] != self.H or seeding.shape[3] != self.W:
             seeding = torch.nn.functional.interpolate(seeding, size=(self.H, self.W), mode="bicubic", antialias=True, align_corners=False)
         self.seeding_image = seeding[:, :, None]
@@ -193,5 +193,6 @@ class Gen3cPersistentModel:
         if self.args.num_gpus > 1:
             import torch.distributed as dist
             from gen3c_amd.parallel import parallel_state
+            self.session.model.denoiser.disable_cfg_parallel()
             parallel_state.destroy_model_parallel()
             dist.destroy_process_group()

@@ -9,6 +9,8 @@ but NOT its communication pattern. The reference lets TransformerEngine run a P2
 K / V shard is exchanged with a direct all-gather (all 7 links busy at once), split into head groups so that the
 attention kernel of group g runs on the compute stream while RCCL is still gathering group g+1. An opt-in schedule, "head_parallel",
 exchanges heads for tokens with two all-to-alls instead (ContextParallelAttention below).
+A second, opt-in axis (CFG-parallel) puts the two classifier-free-guidance branches of a step on separate groups of cp ranks each: the extra groups of
+_ParallelState, and cfg_exchange for the one tensor the pairs exchange per step.
 
 Token layout: rows are (s, b) pairs with b fastest and the latent frames sharded contiguously over ranks, so a
 rank-major all-gather of row blocks IS the global (s, b) order - no re-sort after the collective.
@@ -47,12 +49,18 @@ def cat_outputs_cp(x: torch.Tensor, seq_dim: int, cp_group) -> torch.Tensor:
 def broadcast(item, to_tp: bool = True, to_cp: bool = True):
     """Broadcast a tensor / picklable object from the lowest rank of the CP group (parallel.py:90-163).
     There is no tensor parallelism on this path (Attention.tp_size = 1, attention.py:205): `to_tp` is accepted
-    and ignored."""
+    and ignored.
+    Under CFG-parallel (initialize_model_parallel(cfg_parallel_size=2)) the source is the lowest rank of the model-parallel group - all 2 cp ranks -
+    with or without `to_cp`: the two branch groups feed the same gt_latent and pose buffers to the Euler kernel, and gt_latent derives from renders
+    whose fp32 atomic sums are not order-reproducible, so "every rank computes it" does not give both groups the same bytes."""
     if not parallel_state.is_initialized():
         return item
-    group = parallel_state.get_context_parallel_group()
-    if not (to_cp and dist.get_world_size(group) > 1):
-        return item
+    if parallel_state.get_cfg_parallel_world_size() > 1:
+        group = parallel_state.get_model_parallel_group()
+    else:
+        group = parallel_state.get_context_parallel_group()
+        if not (to_cp and dist.get_world_size(group) > 1):
+            return item
     src = min(dist.get_process_group_ranks(group))
     if isinstance(item, torch.Tensor):
         dev = item.device
@@ -74,14 +82,25 @@ def broadcast(item, to_tp: bool = True, to_cp: bool = True):
 
 
 class _ParallelState:
-    """The part of megatron.core.parallel_state that gen3c_*.py use, for a pure context-parallel job."""
+    """The part of megatron.core.parallel_state that gen3c_*.py use, for a context-parallel job, optionally with the two classifier-free-guidance
+    branches on separate rank groups (CFG-parallel, opt-in).
+
+    cfg_parallel_size = 2 needs world == 2 * cp. Global rank r: cfg_rank = r // cp (0 runs the conditional branch, 1 the unconditional one),
+    cp_rank = r % cp. The CP groups are the contiguous blocks [0, cp) and [cp, 2 cp); the pair groups {r, r + cp} exchange the network output of a
+    step (cfg_exchange); the model-parallel group is all 2 cp ranks (broadcast, the sharded render / encode stages of a chunk)."""
 
     def __init__(self):
         self._cp_group = None
+        self._cfg_group = None
+        self._mp_group = None
 
-    def initialize_model_parallel(self, context_parallel_size: int = 1, **_unused):
+    def initialize_model_parallel(self, context_parallel_size: int = 1, cfg_parallel_size: int = 1, **_unused):
         world = dist.get_world_size()
         assert world % context_parallel_size == 0, f"world size {world} not divisible by cp {context_parallel_size}"
+        assert cfg_parallel_size in (1, 2), f"cfg_parallel_size {cfg_parallel_size}: classifier-free guidance has two branches (1 = off, 2 = one rank group each)"
+        if cfg_parallel_size == 2:
+            assert world == 2 * context_parallel_size, f"CFG-parallel needs world == 2 x cp: world {world}, cp {context_parallel_size}"
+        # every rank creates every group, in the same order (torch.distributed.new_group is collective over the whole world)
         my_group = None
         for start in range(0, world, context_parallel_size):
             ranks = list(range(start, start + context_parallel_size))
@@ -89,6 +108,29 @@ class _ParallelState:
             if dist.get_rank() in ranks:
                 my_group = g
         self._cp_group = my_group
+        self._cfg_group = self._mp_group = None
+        if cfg_parallel_size == 2:
+            for r in range(context_parallel_size):
+                ranks = [r, r + context_parallel_size]
+                g = dist.new_group(ranks)
+                if dist.get_rank() in ranks:
+                    self._cfg_group = g
+            self._mp_group = dist.new_group(list(range(world)))
+
+    def get_cfg_parallel_group(self):
+        """The pair {r, r + cp} of this rank, or None without CFG-parallel."""
+        return self._cfg_group
+
+    def get_cfg_parallel_world_size(self) -> int:
+        return dist.get_world_size(self._cfg_group) if self._cfg_group is not None else 1
+
+    def get_cfg_parallel_rank(self) -> int:
+        """0: this rank runs the conditional branch (also without CFG-parallel), 1: the unconditional one."""
+        return dist.get_rank(self._cfg_group) if self._cfg_group is not None else 0
+
+    def get_model_parallel_group(self):
+        """Every rank that works on the same sample: all 2 cp ranks under CFG-parallel, otherwise the CP group itself."""
+        return self._mp_group if self._mp_group is not None else self.get_context_parallel_group()
 
     def is_initialized(self) -> bool:
         return self._cp_group is not None
@@ -111,6 +153,8 @@ class _ParallelState:
 
     def destroy_model_parallel(self):
         self._cp_group = None
+        self._cfg_group = None
+        self._mp_group = None
 
 
 parallel_state = _ParallelState()
@@ -175,6 +219,23 @@ def run_jobs_round_robin(jobs: List[Callable[[], torch.Tensor]], group, shape, d
     full = torch.empty((world * slots, *shape), dtype=dtype, device=device)
     dist.all_gather_into_tensor(full, local, group=group)
     return [full[(j % world) * slots + j // world] for j in range(len(jobs))]
+
+
+def cfg_exchange(out_local: torch.Tensor, cfg_group):
+    """CFG-parallel: the one exchange of a denoise step. Each rank of the pair `cfg_group` has run the network on its own guidance branch;
+    one all_gather_into_tensor hands both outputs to both ranks -> (out_cond, out_uncond), slot 0 = the pair's rank 0 = the conditional branch.
+    7.2 MB / cp per step at full size, against the per-layer K / V exchange of context parallelism. CPU tensors over gloo and device tensors over
+    RCCL go straight through; device tensors on a gloo group (tests and tools/cfg_check.py with several ranks on one GPU) are staged through the host."""
+    assert dist.get_world_size(cfg_group) == 2, "classifier-free guidance has two branches"
+    flat = out_local.contiguous().view(-1)
+    both = torch.empty(2 * flat.numel(), dtype=flat.dtype, device=flat.device)  # rank-major concatenation along dim 0: the form every backend takes
+    if flat.is_cuda and dist.get_backend(cfg_group) == "gloo":
+        host = torch.empty(both.shape, dtype=both.dtype)
+        _HostStagedWork(dist.all_gather_into_tensor(host, flat.cpu(), group=cfg_group, async_op=True), host, both).wait()
+    else:
+        dist.all_gather_into_tensor(both, flat, group=cfg_group)
+    both = both.view((2,) + tuple(out_local.shape))
+    return both[0], both[1]
 
 
 # ------------------------------------------------------------------------------------------------------------------

@@ -50,8 +50,9 @@ def prepare_data_batch(height: int, width: int, num_frames: int, fps: int, promp
 
 class DiffusionGen3CModel:
     def __init__(self, net: VideoExtendGeneralDIT, tokenizer: VideoTokenizer, sigma_data: float = 0.5,
-                 latent_shape=(16, 16, 88, 160), frame_buffer_max: int = 2):
+                 latent_shape=(16, 16, 88, 160), frame_buffer_max: int = 2, shard_group=None):
         self.net, self.tokenizer = net, tokenizer
+        self.shard_group = shard_group  # group over which encode_warped_frames splits its encodes (None: the net's CP group when CP is enabled)
         self.sigma_data = sigma_data
         self.state_shape = list(latent_shape)
         self.frame_buffer_max = frame_buffer_max
@@ -103,8 +104,9 @@ class DiffusionGen3CModel:
             jobs.append(lambda i=i: self.encode(condition_state[:, :, i].permute(0, 2, 1, 3, 4).to(dtype)).contiguous())
             jobs.append(lambda i=i: self.encode(mask[:, :, i].permute(0, 2, 1, 3, 4).to(dtype)).contiguous())
         # Multi-GPU: the 2N encodes are independent clips - with context parallelism on, clip j is encoded by rank
-        # j % cp only and the 7.2 MB latents are all-gathered (the reference encodes all of them on every rank).
-        group = self.net.cp_group if self.net.is_context_parallel_enabled else None
+        # j % cp only and the 7.2 MB latents are all-gathered (the reference encodes all of them on every rank). Under CFG-parallel the caller
+        # passes the model-parallel group as `shard_group`: both branch groups need the same latents, so all 2 cp ranks share the work.
+        group = self.shard_group if self.shard_group is not None else (self.net.cp_group if self.net.is_context_parallel_enabled else None)
         B, T = condition_state.shape[:2]
         tk = self.tokenizer
         shape = (B, tk.channel, tk.get_latent_num_frames(T), condition_state.shape[-2] // tk.spatial_compression_factor,

@@ -23,10 +23,11 @@ from typing import Dict, Optional
 
 import numpy as np
 import torch
+import torch.distributed as dist
 
 from . import ops
 from .dit import DataType, cacheable, tensor_version
-from .parallel import cat_outputs_cp, split_inputs_cp
+from .parallel import cat_outputs_cp, cfg_exchange, split_inputs_cp
 
 
 class EDMEulerScheduler:
@@ -117,6 +118,19 @@ class Gen3CDenoiser:
         self._noise_cache: Dict[tuple, torch.Tensor] = {}
         self._fused_cache = None
         self.fuse_cond_uncond = os.environ.get("G3_FUSE_COND_UNCOND", "1") != "0"  # one batched forward for the conditional and the unconditional branch of a step (False: two calls)
+        self.cfg_group = None  # CFG-parallel (opt-in): the pair of ranks that run the two guidance branches of a step, see enable_cfg_parallel
+
+    def enable_cfg_parallel(self, group) -> None:
+        """CFG-parallel: `group` is a 2-rank torch.distributed group (parallel_state.get_cfg_parallel_group()). Its rank 0 runs the conditional
+        branch of every step, its rank 1 the unconditional one, each as ONE network call at B; the outputs are exchanged (parallel.cfg_exchange)
+        and both ranks run the same CFG / Euler kernel on the same bytes, so both end the step with bit-identical xt. The network call of a
+        branch is the call the two-call form makes, hence the step is bit-identical to fuse_cond_uncond=False (and to the fused form, which is
+        pinned to it). Context parallelism, if enabled on the net, shards the frames of each branch over the net's own CP group as before."""
+        assert dist.get_world_size(group) == 2, "classifier-free guidance has two branches"
+        self.cfg_group = group
+
+    def disable_cfg_parallel(self) -> None:
+        self.cfg_group = None
 
     # ---- host-side scalar algebra, in the reference's dtypes ------------------------------------------------------
     def _coefficients(self, sigma32: torch.Tensor, sigma_next32: torch.Tensor, augment_sigma: float) -> dict:
@@ -204,7 +218,7 @@ class Gen3CDenoiser:
                                                       co["c_in_aug"], co["c_in_bf16"], co["c_in_step"])
         t = sch.timesteps[step_index].to(device=xt.device, dtype=torch.bfloat16)
         fused = None
-        if self.fuse_cond_uncond:
+        if self.fuse_cond_uncond and self.cfg_group is None:
             # the conditions are the same objects for all steps of a chunk: build the batched arguments once (this also keeps the DiT's
             # per-context cross-attention K / V cache valid, which is keyed on the context tensor)
             # identity AND content version of every value: an in-place edit of a condition tensor between steps / chunks (crossattn_emb.copy_,
@@ -220,7 +234,12 @@ class Gen3CDenoiser:
                 # (the cache entry keeps the condition objects alive, so the ids in the key cannot be recycled while it is valid)
                 fc = self._fused_cache = (key, self._fused_cond_uncond_kwargs(condition, uncondition, B), condition.to_dict(), uncondition.to_dict())
             fused = fc[1]
-        if fused is not None:
+        if self.cfg_group is not None:
+            # CFG-parallel: this rank's branch only, at B (the fused-call cache is not consulted); the exchange is the step's one collective
+            # besides the net's own context-parallel ones
+            branch = condition if dist.get_rank(self.cfg_group) == 0 else uncondition
+            out_c, out_u = cfg_exchange(self.net(x=new_xt_scaled, timesteps=t, **branch.to_dict()), self.cfg_group)
+        elif fused is not None:
             # the conditional and the unconditional forward (model_v2w.py:137-141: two net calls) as ONE forward over a batch of 2 B: every
             # row is computed exactly as in its own call (GEMM / attention / norm kernels work row-, head- and batch-wise), but the chip sees
             # launches twice as long - 55 instead of 27.5 rounds of attention workgroups, no half-empty last round - and half as many of them

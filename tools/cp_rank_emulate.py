@@ -12,6 +12,13 @@ Schedules (the third field of a config): gather_first, local_first, local_carry 
 key - no merge pass), head_parallel (heads sharded by two all-to-alls around the ordinary full-length attention; the stand-in's all-to-all is a device
 copy of the same size). The exchange model below replays each of them.
 
+  python tools/cp_rank_emulate.py --cfg 2 [--worlds 8,4,2] [--rounds 2] [--steps 2] [--configs "4,auto,local_first;4,auto,local_carry"] [--out ...]
+CFG-parallel (opt-in: the two guidance branches on separate rank groups, 2 x cp ranks, each rank at B = 1) against plain context parallelism at the same
+total rank count, ALTERNATING in one process: a middle rank of cp = 8 against one of cfg 2 x cp 4, cp = 4 against cfg 2 x cp 2, cp = 2 against
+cfg 2 x cp 1 (no context parallelism at all). The stand-in is group-aware (the pair group has world 2, the CP group world cp); the pair's all-gather of
+the network output is a device copy of the real size on the stand-in's stream. The K / V bytes received per step are asserted against
+L * 2 * (S_local * B * 4096 * 2) * (cp - 1); the exchange model counts cp - 1 peers and B = 1 for the CFG-parallel arms.
+
   python tools/cp_rank_emulate.py --ab_bounded 3 [--cps 1,2,4,8] [--steps 2] [--configs "4,auto,local_first;4,auto,gather_first;4,auto,local_carry"] [--out ...]
 The logit-bound switch of the key-sharding schedules (ContextParallelAttention's `bounded`) off and on, ALTERNATING in one process after both arms are warm:
 per configuration `--ab_bounded` rounds of (off, on), each `--steps` untimed-by-events steps; then one step per arm with the kernel timers on for the per-class
@@ -45,20 +52,29 @@ class _Work:
         return True
 
 
-class FakeRank:
-    """Stand-in for the torch.distributed calls on the CP path: plays rank `rank` of `world`."""
+CP_GROUP, CFG_GROUP = "fake-cp-group", "fake-cfg-group"
 
-    def __init__(self, world, rank, dev):
-        self.world, self.rank = world, rank
+
+class FakeRank:
+    """Stand-in for the torch.distributed calls on the CP path: plays rank `rank` of `world`. Group-aware for CFG-parallel (`cfg_rank` 0 / 1: the
+    guidance branch this rank runs): CFG_GROUP is the pair, world 2; every other group is the CP group of `world` ranks. The pair's all-gather of the
+    network output is counted apart (`pair_bytes`), so `bytes` stays the K / V exchange."""
+
+    def __init__(self, world, rank, dev, cfg_rank=None):
+        self.world, self.rank, self.cfg_rank = world, rank, cfg_rank
         self.comm = torch.cuda.Stream(device=dev)
         self.bytes = 0
+        self.pair_bytes = 0
         self._orig = {}
+
+    def _size(self, group):
+        return 2 if group == CFG_GROUP else self.world
 
     def __enter__(self):
         for name in ("get_world_size", "get_rank", "get_backend", "all_gather_into_tensor", "all_to_all_single"):
             self._orig[name] = getattr(dist, name)
-        dist.get_world_size = lambda group=None: self.world
-        dist.get_rank = lambda group=None: self.rank
+        dist.get_world_size = lambda group=None: self._size(group)
+        dist.get_rank = lambda group=None: self.cfg_rank if group == CFG_GROUP else self.rank
         dist.get_backend = lambda group=None: "nccl"
         dist.all_gather_into_tensor = self._all_gather
         dist.all_to_all_single = self._all_to_all
@@ -72,10 +88,14 @@ class FakeRank:
     def _all_gather(self, out, inp, group=None, async_op=False):
         cur = torch.cuda.current_stream()
         self.comm.wait_stream(cur)  # the send buffer is produced on the launch stream
+        world = self._size(group)
         with torch.cuda.stream(self.comm):
-            out.view(self.world, -1).copy_(inp.reshape(1, -1).expand(self.world, -1))
+            out.view(world, -1).copy_(inp.reshape(1, -1).expand(world, -1))
             ev = self.comm.record_event()
-        self.bytes += (self.world - 1) * inp.numel() * inp.element_size()
+        if group == CFG_GROUP:
+            self.pair_bytes += (world - 1) * inp.numel() * inp.element_size()
+        else:
+            self.bytes += (world - 1) * inp.numel() * inp.element_size()
         w = _Work(ev)
         if not async_op:
             w.wait()
@@ -96,7 +116,38 @@ class FakeRank:
         return w
 
 
-def run_cp(cp, rank, configs, steps, blocks, dev, net):
+def _class_table(timers, steps, lib):
+    """Kernel timers of `steps` steps -> per-class rows (GEMMs by shape and epilogue, attention launches by shape and kernel), slowest first."""
+    cls = {}
+    for name, meta, tm in timers:
+        if name == "gemm_nt":
+            key = ("gemm", meta["epilogue"], meta["M"], meta["N"], meta["K"])
+            fl = 2.0 * meta["M"] * meta["N"] * meta["K"]
+        elif name == "flash_attn_fwd":
+            key = ("attn", meta["Sq"], meta["Skv"], meta["B"], meta["H"], meta.get("kernel", "?"))
+            fl = 4.0 * meta["Sq"] * meta["Skv"] * meta["H"] * 128 * meta["B"]
+        else:
+            continue
+        c = cls.setdefault(key, [0, 0.0, 0.0])
+        c[0] += 1
+        c[1] += tm.elapsed_ms()
+        c[2] += fl
+    table = []
+    for key, (n, tms, fl) in sorted(cls.items(), key=lambda kv: -kv[1][1]):
+        if tms <= 0:
+            continue
+        d = dict(kind=key[0], launches_per_step=n / steps, ms_per_step=round(tms / steps, 3), tflops=round(fl / tms / 1e9, 1))
+        if key[0] == "gemm":
+            d.update(epilogue=key[1], M=key[2], N=key[3], K=key[4], kernel=lib.g3_gemm_kernel_name(key[2], key[3], key[4], key[1]).decode(),
+                     tile_rounds=round(((key[2] + 255) // 256) * ((key[3] + 255) // 256) / 256.0, 3))
+        else:
+            d.update(Sq=key[1], Skv=key[2], B=key[3], H=key[4], kernel=key[5])
+        table.append(d)
+    return table
+
+
+def _step_inputs(net, dev):
+    """The full-size step's denoiser and inputs (the same numbers run_cp draws) -> (den, xt_full, cond, uncond)."""
     T, Hl, Wl = 16, 88, 160
     rs = np.random.RandomState(1)
     normal = lambda shape, std: torch.from_numpy((rs.standard_normal(shape) * std).astype(np.float32)).to(torch.bfloat16).to(dev)
@@ -112,12 +163,16 @@ def run_cp(cp, rank, configs, steps, blocks, dev, net):
         c = VideoExtendCondition(crossattn_emb=ctx, crossattn_mask=None, padding_mask=pad, fps=fps, video_cond_bool=True, condition_video_pose=p)
         return add_condition_video_indicator_and_video_input_mask(gt, c, 1)
 
-    cond, uncond = make_cond(pose), make_cond(torch.zeros_like(pose))
+    return den, xt_full, make_cond(pose), make_cond(torch.zeros_like(pose))
+
+
+def run_cp(cp, rank, configs, steps, blocks, dev, net):
+    den, xt_full, cond, uncond = _step_inputs(net, dev)
     results = []
     lib = _lib.load()
     with FakeRank(cp, rank, dev) as fr:
         if cp > 1:
-            net.enable_context_parallel("fake-cp-group")
+            net.enable_context_parallel(CP_GROUP)
             from gen3c_amd.parallel import split_inputs_cp
             xt0 = split_inputs_cp(xt_full, 2, net.cp_group)
         else:
@@ -143,31 +198,7 @@ def run_cp(cp, rank, configs, steps, blocks, dev, net):
             timers = ops.collected_kernel_timers()
             ops.enable_kernel_timers(False)
             assert bool(torch.isfinite(xt.float()).all())
-            cls = {}
-            for name, meta, tm in timers:
-                if name == "gemm_nt":
-                    key = ("gemm", meta["epilogue"], meta["M"], meta["N"], meta["K"])
-                    fl = 2.0 * meta["M"] * meta["N"] * meta["K"]
-                elif name == "flash_attn_fwd":
-                    key = ("attn", meta["Sq"], meta["Skv"], meta["B"], meta["H"], meta.get("kernel", "?"))
-                    fl = 4.0 * meta["Sq"] * meta["Skv"] * meta["H"] * 128 * meta["B"]
-                else:
-                    continue
-                c = cls.setdefault(key, [0, 0.0, 0.0])
-                c[0] += 1
-                c[1] += tm.elapsed_ms()
-                c[2] += fl
-            table = []
-            for key, (n, tms, fl) in sorted(cls.items(), key=lambda kv: -kv[1][1]):
-                if tms <= 0:
-                    continue
-                d = dict(kind=key[0], launches_per_step=n / steps, ms_per_step=round(tms / steps, 3), tflops=round(fl / tms / 1e9, 1))
-                if key[0] == "gemm":
-                    d.update(epilogue=key[1], M=key[2], N=key[3], K=key[4], kernel=lib.g3_gemm_kernel_name(key[2], key[3], key[4], key[1]).decode(),
-                             tile_rounds=round(((key[2] + 255) // 256) * ((key[3] + 255) // 256) / 256.0, 3))
-                else:
-                    d.update(Sq=key[1], Skv=key[2], B=key[3], H=key[4], kernel=key[5])
-                table.append(d)
+            table = _class_table(timers, steps, lib)
             wait_ms = None
             if cp > 1 and net._cp_attn.stats:
                 wait_ms = round(sum(tm.elapsed_ms() for (_k, _g, tm) in net._cp_attn.stats) / steps, 3)
@@ -186,6 +217,45 @@ def run_cp(cp, rank, configs, steps, blocks, dev, net):
     if cp > 1:
         net.disable_context_parallel()
     return results
+
+
+def _exchange_model(r, base, base_rest, layers):
+    """The exchange model of main() (described there) for one run record `r` with cp > 1: fills r["self_attention_and_cp_ms_per_layer"] and
+    r["predicted"][bandwidth] and returns one (GB/s, predicted ms/step, exposed ms/layer, exchange ms/layer, attention ms/layer, Q ms/layer) per assumed
+    rate. A CFG-parallel record (r["cfg"] == 2) is one of 2 x cp ranks at B = 1: its K / V exchange has cp - 1 peers (the bytes the run counted), the
+    HBM-bound rest of the cp = 1, B = 2 step is scaled by 1 / (2 cp), and the pair's exchange of the network output is added to every step unhidden."""
+    cp = r["cp"]
+    eff = r["effective"] or {}
+    G, sched = eff.get("head_groups", 4), eff.get("schedule", "gather_first")
+    gemm = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm")
+    cross = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "attn" and c["Skv"] <= 2048)
+    attn_layer = max(0.0, r["ms_per_step"] - gemm - cross - base_rest / (cp * r.get("cfg", 1))) / layers
+    r["self_attention_and_cp_ms_per_layer"] = round(attn_layer, 3)
+    q_ms = 0.0
+    if sched == "gather_first":  # the self-attention Q projection: one of the two plain N = 4096 launches per block (the other is the cross-attention Q)
+        q_ms = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm" and c["N"] == 4096 and c["K"] == 4096 and c["epilogue"] == 0) / 2 / layers
+    rows = []
+    for bw in (250.0, 375.0, 500.0):
+        ex_g = r["gathered_bytes_per_step"] / layers / G / (bw * 1e9) * 1e3
+        if sched == "gather_first":
+            t = q_ms
+            for g_ in range(G):
+                t = max(t, (g_ + 1) * ex_g) + attn_layer / G
+            exposed = t - (q_ms + attn_layer)
+        elif sched in ("local_first", "local_carry"):
+            t = attn_layer / cp
+            for g_ in range(G):
+                t = max(t, (g_ + 1) * ex_g) + attn_layer * (cp - 1) / cp / G
+            exposed = t - attn_layer
+        elif sched == "head_parallel":
+            exposed = ex_g  # 3 of the first group's 4 tensors + 1 of the last group's 4 = one group's exchange
+        else:
+            raise ValueError(f"exchange model: unknown schedule {sched}")
+        pred = r["ms_per_step"] + layers * exposed + r.get("cfg_exchange_bytes_per_step", 0) / (bw * 1e9) * 1e3
+        r.setdefault("predicted", {})[str(int(bw))] = dict(exchange_ms_per_layer=round(ex_g * G, 3), exposed_ms_per_layer=round(exposed, 3), ms_per_step=round(pred, 1),
+                                                           speedup=round(base["ms_per_step"] / pred, 3))
+        rows.append((bw, pred, exposed, ex_g * G, attn_layer, q_ms))
+    return rows
 
 
 def _steps_ms(den, xt, cond, uncond, steps):
@@ -351,8 +421,105 @@ def main_ab(args, dev, configs, net):
     out.with_suffix(".txt").write_text(text + "\n")
 
 
+def run_cfg_ab(world, configs, steps, rounds, blocks, dev, net):
+    """`world` ranks two ways, alternating in one process: plain context parallelism (cp = world, both guidance branches batched as B = 2) against
+    CFG-parallel (2 branches x cp = world / 2, the emulated rank runs the conditional branch at B = 1 and exchanges the network output with its pair),
+    a middle rank of each. Per configuration `rounds` rounds of (plain, CFG-parallel), each one untimed step after the switch (the switch rebuilds the
+    position tables) and `steps` timed ones; then one step per arm with the kernel timers on for the per-class table. The K / V bytes a rank receives
+    per step must be L * 2 * (S_local * B * 4096 * 2) * (cp - 1) exactly, the pair's exchange the size of the rank's latent shard."""
+    from gen3c_amd.parallel import split_inputs_cp
+    den, xt_full, cond, uncond = _step_inputs(net, dev)
+    lib = _lib.load()
+    S_all, T = 56320, 16
+    records = []
+    for (G, kern, sched) in (configs if world > 2 else configs[:1]):  # world 2: the CFG-parallel arm has no context parallelism to configure
+        arms = [dict(world=world, cfg=1, cp=world, rank=world // 2, B=2), dict(world=world, cfg=2, cp=world // 2, rank=world // 4, B=1)]
+        for rnd in range(rounds + 1):
+            for a in arms:
+                cp = a["cp"]
+                with FakeRank(cp, a["rank"], dev, cfg_rank=0 if a["cfg"] == 2 else None) as fr:
+                    try:
+                        if a["cfg"] == 2:
+                            den.enable_cfg_parallel(CFG_GROUP)
+                        if cp > 1:
+                            net.enable_context_parallel(CP_GROUP)
+                            net._cp_attn.configure(head_groups=G, kernel=kern, schedule=sched)
+                            xt0 = split_inputs_cp(xt_full, 2, net.cp_group)
+                        else:
+                            net.disable_context_parallel()
+                            xt0 = xt_full
+                        den.denoise_step(xt0, 0, cond, uncond, 1.0, 0.001, 1)  # warm-up after the switch
+                        torch.cuda.synchronize()
+                        fr.bytes = fr.pair_bytes = 0
+                        if rnd < rounds:
+                            a.setdefault("ms_per_step_rounds", []).append(round(_steps_ms(den, xt0, cond, uncond, steps), 2))
+                            n = steps
+                        else:  # event pairs around every launch: not part of the timing above
+                            ops.enable_kernel_timers(True)
+                            den.denoise_step(xt0, 1, cond, uncond, 1.0, 0.001, 1)
+                            torch.cuda.synchronize()
+                            a["classes"] = _class_table(ops.collected_kernel_timers(), 1, lib)
+                            ops.enable_kernel_timers(False)
+                            n = 1
+                        a["effective"] = dict(net._cp_attn.effective) if cp > 1 and net._cp_attn.effective else None
+                        a["gathered_bytes_per_step"], pair_bytes = fr.bytes // n, fr.pair_bytes // n
+                        if a["effective"] is None or a["effective"]["schedule"] != "head_parallel":
+                            want = blocks * 2 * (S_all // cp * a["B"] * 4096 * 2) * (cp - 1)
+                            assert a["gathered_bytes_per_step"] == want, f"{a}: received {a['gathered_bytes_per_step']} B per step, the formula gives {want}"
+                        assert pair_bytes == (16 * (T // cp) * 88 * 160 * 2 if a["cfg"] == 2 else 0), pair_bytes
+                        if a["cfg"] == 2:
+                            a["cfg_exchange_bytes_per_step"] = pair_bytes
+                    finally:
+                        den.disable_cfg_parallel()
+                        net.disable_context_parallel()
+        for a in arms:
+            r = a["ms_per_step_rounds"]
+            a.update(config=dict(head_groups=G, kernel=kern, schedule=sched) if a["cp"] > 1 else None, steps=steps, ms_per_step=round(sum(r) / len(r), 2),
+                     spread_pct=round((max(r) - min(r)) / (sum(r) / len(r)) * 100, 2))
+            records.append(a)
+        print(f"world={world} {G},{kern},{sched}: cp={world} (B=2) {arms[0]['ms_per_step_rounds']}  cfg 2 x cp={world // 2} (B=1) {arms[1]['ms_per_step_rounds']} ms/step -> "
+              f"CFG-parallel / plain {arms[1]['ms_per_step'] / arms[0]['ms_per_step']:.4f}", flush=True)
+    return records
+
+
+def main_cfg(args, dev, configs, net):
+    """--cfg 2: per total rank count of --worlds, plain CP against CFG-parallel (run_cfg_ab), then the exchange model of main() on every arm."""
+    base = run_cp(1, 0, configs, args.steps, args.blocks, dev, net)[0]
+    base_rest = base["ms_per_step"] - sum(c["ms_per_step"] for c in base["classes"] if c["kind"] in ("attn", "gemm"))
+    runs = []
+    for world in [int(w) for w in args.worlds.split(",")]:
+        assert world >= 2 and world % 2 == 0, "--worlds: total rank counts, even (2 guidance branches x cp)"
+        runs += run_cfg_ab(world, configs, args.steps, args.rounds, args.blocks, dev, net)
+    for r in runs:
+        _exchange_model(r, base, base_rest, args.blocks)
+    ms_of = lambda r, pred: sum(c["ms_per_step"] for c in r["classes"] if pred(c))
+    lines = [f"one MI355X as one rank, {args.blocks} blocks, {args.rounds} alternating rounds x {args.steps} steps; cp = 1 (B = 2) base: {base['ms_per_step']:.1f} ms/step. "
+             f"compute = measured, no exchange; predicted = compute + exposed K / V exchange (+ the pair's output exchange) at 250 / 375 / 500 GB/s into the rank: a MODEL,",
+             "no multi-GPU run exists. Kernel sums are durations of launches that overlap on two streams.", "",
+             f"{'ranks':>5} {'layout':<16} {'B':>2} {'config':<22} {'compute ms/step (rounds)':<28} {'mean':>8} {'spread %':>8} {'x cp=1':>7} {'K/V GB/step':>12} {'pair MB/step':>13} "
+             f"{'self-attn ms':>13} {'cross-attn ms':>14} {'GEMM ms':>9}  predicted ms/step (speed-up)"]
+    for r in runs:
+        c, pr = r["config"], r["predicted"]
+        lines.append(f"{r['world']:>5} {('cfg 2 x cp %d' % r['cp']) if r['cfg'] == 2 else ('cp %d' % r['cp']):<16} {r['B']:>2} "
+                     f"{('%d,%s,%s' % (c['head_groups'], c['kernel'], c['schedule'])) if c else '-':<22} {str(r['ms_per_step_rounds']):<28} {r['ms_per_step']:>8.1f} {r['spread_pct']:>8.2f} "
+                     f"{base['ms_per_step'] / r['ms_per_step']:>7.2f} {r['gathered_bytes_per_step'] / 1e9:>12.2f} {r.get('cfg_exchange_bytes_per_step', 0) / 1e6:>13.2f} "
+                     f"{ms_of(r, lambda k: k['kind'] == 'attn' and k['Skv'] > 2048):>13.1f} {ms_of(r, lambda k: k['kind'] == 'attn' and k['Skv'] <= 2048):>14.1f} "
+                     f"{ms_of(r, lambda k: k['kind'] == 'gemm'):>9.1f}  "
+                     + " / ".join(f"{pr[b]['ms_per_step']:.1f} ({pr[b]['speedup']:.2f} x)" for b in ("250", "375", "500")))
+    text = "\n".join(lines)
+    print(text)
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(dict(base=base, runs=runs, summary_text=text), indent=1))
+    out.with_suffix(".txt").write_text(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--cfg", type=int, choices=(1, 2), default=1, help="2: CFG-parallel (2 guidance branches x cp) against plain context parallelism at the same total "
+                    "rank count, arms alternating (run_cfg_ab); 1: the arms below, unchanged")
+    ap.add_argument("--worlds", default="8,4,2", help="with --cfg 2: total rank counts")
+    ap.add_argument("--rounds", type=int, default=2, help="with --cfg 2: alternating rounds")
     ap.add_argument("--ab_bounded", type=int, default=0, help="> 0: the logit-bound switch off / on alternating, this many rounds (see the module docstring)")
     ap.add_argument("--launch_iters", type=int, default=5, help="with --ab_bounded: launches per round of the launch-by-launch table (0: skip it)")
     ap.add_argument("--cps", default="1,2,4,8")
@@ -363,6 +530,11 @@ def main():
                                           "1,auto,gather_first")
     ap.add_argument("--out", default="gpurun_out/r6_cp_rank_shapes.json")
     args = ap.parse_args()
+    if args.cfg == 2:  # its own defaults: the shipped schedule plus local_carry, and a record of its own beside the default one
+        if args.configs == ap.get_default("configs"):
+            args.configs = "4,auto,local_first;4,auto,local_carry"
+        if args.out == ap.get_default("out"):
+            args.out = str(Path(args.out).with_name("cfg_parallel_rank_shapes.json"))
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
     configs = [(int(c.split(",")[0]), c.split(",")[1], c.split(",")[2]) for c in args.configs.split(";")]
@@ -371,6 +543,8 @@ def main():
     net.cross_attention_skip_zero_context = False  # the dense workload bench.py times (the record profiles/r6_cp_rank_shapes.* was taken with the product default, ~17 / cp ms less per step)
     if args.ab_bounded > 0:
         return main_ab(args, dev, configs, net)
+    if args.cfg == 2:
+        return main_cfg(args, dev, configs, net)
     allres = []
     for cp in [int(c) for c in args.cps.split(",")]:
         rank = (cp // 2 if args.rank < 0 else args.rank) if cp > 1 else 0
@@ -425,37 +599,10 @@ def main():
             cp = r["cp"]
             if cp == 1:
                 continue
-            eff = r["effective"] or {}
-            G, sched = eff.get("head_groups", 4), eff.get("schedule", "gather_first")
-            gemm = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm")
-            cross = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "attn" and c["Skv"] <= 2048)
-            attn_layer = max(0.0, r["ms_per_step"] - gemm - cross - base_rest / cp) / layers
-            r["self_attention_and_cp_ms_per_layer"] = round(attn_layer, 3)
-            q_ms = 0.0
-            if sched == "gather_first":  # the self-attention Q projection: one of the two plain N = 4096 launches per block (the other is the cross-attention Q)
-                q_ms = sum(c["ms_per_step"] for c in r["classes"] if c["kind"] == "gemm" and c["N"] == 4096 and c["K"] == 4096 and c["epilogue"] == 0) / 2 / layers
-            for bw in (250.0, 375.0, 500.0):
-                ex_g = r["gathered_bytes_per_step"] / layers / G / (bw * 1e9) * 1e3
-                if sched == "gather_first":
-                    t = q_ms
-                    for g_ in range(G):
-                        t = max(t, (g_ + 1) * ex_g) + attn_layer / G
-                    exposed = t - (q_ms + attn_layer)
-                elif sched in ("local_first", "local_carry"):
-                    t = attn_layer / cp
-                    for g_ in range(G):
-                        t = max(t, (g_ + 1) * ex_g) + attn_layer * (cp - 1) / cp / G
-                    exposed = t - attn_layer
-                elif sched == "head_parallel":
-                    exposed = ex_g  # 3 of the first group's 4 tensors + 1 of the last group's 4 = one group's exchange
-                else:
-                    raise ValueError(f"exchange model: unknown schedule {sched}")
-                pred = r["ms_per_step"] + layers * exposed
-                r.setdefault("predicted", {})[str(int(bw))] = dict(exchange_ms_per_layer=round(ex_g * G, 3), exposed_ms_per_layer=round(exposed, 3), ms_per_step=round(pred, 1),
-                                                                   speedup=round(base["ms_per_step"] / pred, 3))
+            for bw, pred, exposed, ex_layer, attn_layer, q_ms in _exchange_model(r, base, base_rest, layers):
                 key = (cp, bw)
                 if key not in best_pred or pred < best_pred[key][0]:
-                    best_pred[key] = (pred, r, exposed, ex_g * G, attn_layer, q_ms)
+                    best_pred[key] = (pred, r, exposed, ex_layer, attn_layer, q_ms)
         for (cp, bw), (pred, r, exposed, ex_layer, attn_layer, q_ms) in sorted(best_pred.items()):
             lines.append(f"cp={cp} @ {bw:.0f} GB/s: best {r['effective']}: compute {r['ms_per_step']:.1f} ms/step (measured, one GPU as rank {r['rank']}); exchange "
                          f"{r['gathered_bytes_per_step'] / 1e9:.1f} GB/step = {ex_layer:.2f} ms/layer vs attention {attn_layer:.2f} ms/layer (+ Q {q_ms:.2f}) -> exposed {exposed:.2f} ms/layer; "
