@@ -64,6 +64,12 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     p.add_argument("--cp_logit_bound", action="store_true",
                    help="with --num_gpus > 1: the key-sharding context-parallel schedules run self-attention without a running row maximum, on the "
                         "blocks' QK-norm logit bound (opt-in, default off; same as G3_CP_LOGIT_BOUND=1)")
+    p.add_argument("--self_attn_window_frames", type=int, default=None, metavar="W",
+                   help="single GPU: local self-attention - every block of 256 query tokens attends the latent frames within W of its own and the first "
+                        "--self_attn_sink_frames latent frames; the kernel skips the key tiles outside (opt-in, default off; outside the parity statement, "
+                        "picture quality with trained weights unmeasured: DESIGN.md section 11; same as G3_SELF_ATTN_WINDOW=\"W,S\")")
+    p.add_argument("--self_attn_sink_frames", type=int, default=None, metavar="S",
+                   help="with --self_attn_window_frames: the first S latent frames (the conditioning frames) are attended by every query (default 1)")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -100,6 +106,26 @@ def resolve_parallel_layout(num_gpus: int, cfg_parallel: bool, latent_frames: in
 def cfg_parallel_requested(args) -> bool:
     """--cfg_parallel, or G3_CFG_PARALLEL=1 in the environment (opt-in, default off)."""
     return bool(getattr(args, "cfg_parallel", False)) or os.environ.get("G3_CFG_PARALLEL", "0").strip() not in ("", "0")
+
+
+def self_attn_window_requested(args):
+    """--self_attn_window_frames W [--self_attn_sink_frames S], or G3_SELF_ATTN_WINDOW="W,S" (or "W") in the environment -> (W, S), S defaulting to 1;
+    None with neither (opt-in, default off). The flags win over the environment."""
+    W, s = getattr(args, "self_attn_window_frames", None), getattr(args, "self_attn_sink_frames", None)
+    if W is None:
+        if s is not None:
+            raise ValueError(f"--self_attn_sink_frames {s} needs --self_attn_window_frames")
+        env = os.environ.get("G3_SELF_ATTN_WINDOW", "").strip()
+        if not env:
+            return None
+        parts = [x.strip() for x in env.split(",")]
+        if len(parts) not in (1, 2) or not all(x.lstrip("-").isdigit() for x in parts):
+            raise ValueError(f"G3_SELF_ATTN_WINDOW={env!r}: expected \"W\" or \"W,S\" (window and sink in latent frames)")
+        W, s = int(parts[0]), int(parts[1]) if len(parts) == 2 else None
+    s = 1 if s is None else s
+    if W < 0 or s < 0:
+        raise ValueError(f"self-attention window: window frames {W} and sink frames {s} must be >= 0")
+    return W, s
 
 
 def log_ignored_flags(args, log=print) -> List[str]:
@@ -227,6 +253,10 @@ class Session:
             net.enable_context_parallel(self.cp_group)
             if getattr(args, "cp_logit_bound", False):
                 net._cp_attn.configure(bounded=True)
+        window = self_attn_window_requested(args)
+        if window is not None:
+            net.set_self_attn_window(*window)  # (with context parallelism the first forward refuses it, with the numbers)
+            print(f"[gen3c_amd] self-attention window: {window[0]} latent frame(s) either side + {window[1]} sink frame(s) (opt-in; outside the parity statement)")
         if self.cfg_size > 1:
             self.cfg_group = parallel_state.get_cfg_parallel_group()
             print(f"[gen3c_amd] --cfg_parallel: 2 guidance branches x {self.cp_size} context-parallel rank(s); this rank runs the "

@@ -75,6 +75,10 @@ struct AttnParams {
     // no-max form (flash_attn_fwd_w4b_nm_kernel, flash_attn_fwd_w4b_nm_carry_kernel; g3_self_attn_fwd_bounded_bf16, g3_self_attn_fwd_bounded_cp_bf16): the
     // caller's bound on |q.k| * scale_log2, the constant reference point of the softmax. No other kernel reads it.
     float logit_bound_log2;
+    // window form (flash_attn_fwd_w4b_win_kernel, flash_attn_fwd_w4b_nm_win_kernel; g3_self_attn_fwd_window_bf16): tokens per latent frame (a multiple of 64
+    // that divides Sq == Skv), the temporal window and the always-attended prefix in frames (the launcher clamps both to the frame count). Every
+    // workgroup derives its own key range from these and its query block; no other kernel reads them.
+    int win_frame_len, win_frames, win_sink;
 };
 
 G3_DEVICE int k_off(int row, int chunk) { return row * HD + ((chunk ^ (row & 15)) << 3); }          // [64][128]
@@ -1005,6 +1009,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 
 #include "attention_w4.hpp"
+#define W4B_WIN 0
 #define W4B_NM 0
 #define W4B_CP 0
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_kernel
@@ -1019,8 +1024,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 #undef W4B_CP
 #define W4B_CP 1
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_carry_kernel: the no-max form with the CP form (g3_self_attn_fwd_bounded_cp_bf16)
+#undef W4B_WIN
+#define W4B_WIN 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_win_kernel: the no-max form over a per-workgroup key range (g3_self_attn_fwd_window_bf16)
+#undef W4B_NM
+#define W4B_NM 0
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_win_kernel: the same with the running row maximum (bound out of range)
 #undef W4B_NM
 #undef W4B_CP
+#undef W4B_WIN
 #include "attention_w4c.hpp"  // flash_attn_fwd_w4c_nm_kernel: the plain no-max form on 16x16x32 MFMAs (g3_self_attn_fwd_bounded16_bf16)
 
 }  // namespace
@@ -1030,6 +1042,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 #include "gen3c_hip.h"  // enum g3_attn_entry
 
 struct AttnOperand { const void* ptr = nullptr; int64_t row = 0, batch = 0, head = 0; };  // element strides
+constexpr int ATTN_ENTRY_WINDOW = G3_ATTN_ENTRY_BOUNDED_CP + 1;  // g3_self_attn_fwd_window_bf16: has its own dry run, so it is no value of enum g3_attn_entry
 struct AttnCall {
     int entry = G3_ATTN_ENTRY_FWD;  // the public entry point called: it decides which checks run and whose name a refusal carries
     AttnOperand q, k, vt, o;        // o.ptr: the bf16 result; o's strides also address o_partial and carry_o
@@ -1042,6 +1055,7 @@ struct AttnCall {
     const float* carry_o = nullptr; const float* carry_lse = nullptr; int kv_skip_begin = 0, kv_skip_len = 0;
     float logit_bound = 0.f;
     int mfma16 = 0;  // g3_self_attn_fwd_bounded16_bf16: the 16x16x32 tile loop where the plain no-max kernel would run
+    int win_frame_len = 0, win_frames = 0, win_sink = 0;  // g3_self_attn_fwd_window_bf16
     void* stream = nullptr;
 };
 
@@ -1049,6 +1063,9 @@ struct AttnCall {
 struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_rows; };
 // (the row only g3_self_attn_fwd_bounded16_bf16 reaches, apart from the rows the recorded launcher decisions cover: tests/golden/attn_plan_parent.json)
 #define G3_ATTN_KERNELS16(X) X(AK_W4C_NM, W4_THREADS, W4_BQ, flash_attn_fwd_w4c_nm_kernel)
+// (the rows only g3_self_attn_fwd_window_bf16 reaches)
+#define G3_ATTN_KERNELS_WIN(X) \
+    X(AK_W4BX_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_win_kernel<true>) X(AK_W4BX_NM_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_win_kernel<true>)
 #define G3_ATTN_KERNELS(X) \
     X(AK_V1_L, NTHREADS, BQ, flash_attn_fwd_kernel<0>) X(AK_V1_S, NTHREADS, BQ, flash_attn_fwd_kernel<1>) \
     X(AK_V2_L, NTHREADS, BQ, flash_attn_fwd_v2_kernel<0>) X(AK_V2_S, NTHREADS, BQ, flash_attn_fwd_v2_kernel<1>) \
@@ -1063,8 +1080,8 @@ struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_row
     X(AK_W4BX_NM_CARRY, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_carry_kernel<true>)
 #define G3_ATTN_ID(ID, THREADS, Q_ROWS, ...) ID,
 #define G3_ATTN_ROW(ID, THREADS, Q_ROWS, ...) {#__VA_ARGS__, &__VA_ARGS__, THREADS, Q_ROWS},
-enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) G3_ATTN_KERNELS16(G3_ATTN_ID) AK_COUNT };
-static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW) G3_ATTN_KERNELS16(G3_ATTN_ROW)};
+enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) G3_ATTN_KERNELS16(G3_ATTN_ID) G3_ATTN_KERNELS_WIN(G3_ATTN_ID) AK_COUNT };
+static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW) G3_ATTN_KERNELS16(G3_ATTN_ROW) G3_ATTN_KERNELS_WIN(G3_ATTN_ROW)};
 #undef G3_ATTN_ID
 #undef G3_ATTN_ROW
 
@@ -1103,6 +1120,25 @@ static const AttnKernel& attn_kernel_for(int variant, int Skv, bool cp_form, boo
     return attn_kernels[by_variant[variant >= 1 && variant <= 11 ? variant : 4][short_ctx]];
 }
 
+// The window form's key set of query block b (the function: gen3c_hip.h; the kernel's prologue computes the same from the same numbers): keys
+// [0, sink_end) u [lo, hi). S a multiple of frame_len, W and s within [0, S / frame_len].
+static void attn_window_range(int S, int frame_len, int W, int s, int b, int& sink_end, int& lo, int& hi) {
+    const int T = S / frame_len, r0 = b * W4_BQ, r1 = (r0 + W4_BQ < S ? r0 + W4_BQ : S) - 1;
+    const int f0 = r0 / frame_len, f1 = r1 / frame_len;
+    lo = (f0 > W ? f0 - W : 0) * frame_len;
+    hi = (f1 + W + 1 < T ? f1 + W + 1 : T) * frame_len;
+    const int sink_len = s * frame_len;
+    sink_end = sink_len < lo ? sink_len : lo;
+    if (sink_len >= lo && sink_len > hi) hi = sink_len;  // a sink that reaches the window: one range from key 0, as long as the longer of the two
+}
+// the window arguments every window function takes: G3_OK, or the refusal under the caller's name
+static int attn_window_check(const char* fn, int S, int frame_len, int W, int s) {
+    if (S <= 0 || frame_len <= 0 || (S % KVB) || (frame_len % KVB) || (S % frame_len))
+        return g3_set_error(G3_ERR_ARG, "%s: S %d and frame_len %d must be positive multiples of 64, S a multiple of frame_len", fn, S, frame_len);
+    if (W < 0 || s < 0) return g3_set_error(G3_ERR_ARG, "%s: window_frames %d and sink_frames %d must be >= 0", fn, W, s);
+    return G3_OK;
+}
+
 struct AttnPlan { AttnParams p; const AttnKernel* kernel; dim3 grid; };
 constexpr size_t ATTN_SMEM = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
 
@@ -1111,8 +1147,21 @@ constexpr size_t ATTN_SMEM = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);
 static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     AttnCall c = call;  // (a skip at the front moves c.k / c.vt)
     const bool cp_form = c.entry == G3_ATTN_ENTRY_CARRY || c.entry == G3_ATTN_ENTRY_BOUNDED_CP;
-    const char* fn = cp_form ? "g3_flash_attn_fwd_carry_bf16" : c.entry == G3_ATTN_ENTRY_BOUNDED ? "g3_self_attn_fwd_bounded_bf16" : "g3_flash_attn_fwd_ex_bf16";
+    const bool window = c.entry == ATTN_ENTRY_WINDOW;
+    const char* fn = cp_form ? "g3_flash_attn_fwd_carry_bf16" : c.entry == G3_ATTN_ENTRY_BOUNDED ? "g3_self_attn_fwd_bounded_bf16" :
+                     window ? "g3_self_attn_fwd_window_bf16" : "g3_flash_attn_fwd_ex_bf16";
     uint32_t kv_skip_vt_bytes = 0;
+    if (window) {  // (Sq == Skv == S, variant 11, plain V^T, a bf16 output: the entry sets them)
+        if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || !c.o.ptr) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
+        if (int rc = attn_window_check(fn, c.Skv, c.win_frame_len, c.win_frames, c.win_sink)) return rc;
+        if (c.vt.row < c.Skv)  // (S % 64 == 0: S is its own ceil64; the kernel reads whole V^T tiles unguarded)
+            return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S) %d", fn, (long long)c.vt.row, c.Skv);
+        const int T = c.Skv / c.win_frame_len;
+        c.win_frames = c.win_frames < T ? c.win_frames : T;
+        c.win_sink = c.win_sink < T ? c.win_sink : T;
+    }
+    // a window that covers every key of every block: the call IS g3_self_attn_fwd_bounded_bf16 with variant 11 (the dense kernel, the dense epilogue)
+    const bool win_dense = window && (c.win_frames >= c.Skv / c.win_frame_len - 1 || c.win_sink >= c.Skv / c.win_frame_len);
     if (c.entry == G3_ATTN_ENTRY_KVSEG && c.vt_seg_len <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: vt_seg_len must be positive");
     if (c.entry == G3_ATTN_ENTRY_CROSS && c.kv_dense < 0) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense must be >= 0 (0 = every key through the loop)");
     if (c.entry >= G3_ATTN_ENTRY_EX) {  // the entries with a per-call variant and o_partial / lse
@@ -1188,6 +1237,9 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
             if (cp_form)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: K / V^T span (skipped keys included) exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes); "
                                                 "the 64-bit-addressing kernel has no carry form", (unsigned long long)k_max, (unsigned long long)v_max);
+            if (window)
+                return g3_set_error(G3_ERR_ARG, "%s: K / V^T span exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes)", fn,
+                                    (unsigned long long)k_max, (unsigned long long)v_max);
             if (c.vt_seg_len > 0)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: K / V^T span exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes)",
                                     (unsigned long long)k_max, (unsigned long long)v_max);
@@ -1219,6 +1271,7 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     p.carry_o = c.carry_o; p.carry_lse = c.carry_lse;
     p.kv_skip_begin = c.kv_skip_begin; p.kv_skip_len = c.kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
     p.logit_bound_log2 = attn_bound_log2(c.logit_bound);
+    p.win_frame_len = p.win_frames = p.win_sink = 0;
     // bounded logits (only the two bounded entries carry a bound): the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems
     // only; g3_self_attn_fwd_bounded_cp_bf16: also with segmented V^T, and with a carry-in state or a skipped key range. Everything else runs as it always did.
     const bool no_max = attn_bound_usable(p.logit_bound_log2) && (c.entry == G3_ATTN_ENTRY_BOUNDED_CP || (!cp_form && c.vt_seg_len == 0));
@@ -1226,6 +1279,10 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     // the 16x16x32 tile loop covers the plain no-max kernel's bf16-output launches only (that row already means: variant 11, S_kv % 64 == 0, bound in
     // range, plain V^T, no carry, no skip); everything else keeps the kernel chosen above
     if (c.mfma16 && plan.kernel == &attn_kernels[AK_W4BX_NM] && !c.o_partial) plan.kernel = &attn_kernels[AK_W4C_NM];
+    if (window && !win_dense) {  // (variant 11 here: S % 64 == 0, the V^T leading dimension and the operand span were checked above)
+        plan.kernel = &attn_kernels[no_max ? AK_W4BX_NM_WIN : AK_W4BX_WIN];
+        p.win_frame_len = c.win_frame_len; p.win_frames = c.win_frames; p.win_sink = c.win_sink;
+    }
     plan.grid = dim3((c.Sq + plan.kernel->q_rows - 1) / plan.kernel->q_rows, c.H, c.B);
     if (variant == 10 || variant == 11) {  // w4b (attention_w4b.hpp): optionally a 1-D grid that gives every XCD its own (batch, head) pairs
         p.grid_q = (int)plan.grid.x; p.n_hb = c.H * c.B;
@@ -1354,6 +1411,54 @@ extern "C" int g3_self_attn_fwd_bounded_cp_bf16(const void* q, int64_t q_row, in
     c.kv_skip_begin = kv_skip_begin; c.kv_skip_len = kv_skip_len; c.carry_o = carry_o; c.carry_lse = carry_lse;
     c.Sq = Sq; c.Skv = Skv; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
     return attn_launch(c);
+}
+
+/* ---- self-attention over a temporal frame window + sink frames: the key range per workgroup (attention_w4b.hpp, WIN); a window that covers everything IS the
+ * bounded entry with variant 11 ------------------------------------------------------------------------------------------------------------- */
+#define G3_ATTN_WINDOW_PARAMS                                                                                                                          \
+    const void *q, int64_t q_row, int64_t q_batch, int64_t q_head, const void *k, int64_t k_row, int64_t k_batch, int64_t k_head, const void *vt,      \
+        int64_t vt_row, int64_t vt_batch, int64_t vt_head, void *o, int64_t o_row, int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, \
+        float softmax_scale, float logit_bound, int frame_len, int window_frames, int sink_frames
+static AttnCall attn_window_call(G3_ATTN_WINDOW_PARAMS) {
+    AttnCall c;
+    c.entry = ATTN_ENTRY_WINDOW;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.variant = 11; c.logit_bound = logit_bound;
+    c.win_frame_len = frame_len; c.win_frames = window_frames; c.win_sink = sink_frames;
+    c.Sq = S; c.Skv = S; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale;
+    return c;
+}
+#define G3_ATTN_WINDOW_ARGS \
+    q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, o, o_row, o_batch, o_head, S, B, H, head_dim, softmax_scale, logit_bound, \
+        frame_len, window_frames, sink_frames
+extern "C" int g3_self_attn_fwd_window_bf16(G3_ATTN_WINDOW_PARAMS, void* stream) {
+    AttnCall c = attn_window_call(G3_ATTN_WINDOW_ARGS);
+    c.stream = stream;
+    return attn_launch(c);
+}
+extern "C" const char* g3_attn_window_plan_bf16(G3_ATTN_WINDOW_PARAMS) {
+    AttnPlan plan;
+    return attn_plan(attn_window_call(G3_ATTN_WINDOW_ARGS), plan) == G3_OK ? plan.kernel->name : nullptr;
+}
+#undef G3_ATTN_WINDOW_PARAMS
+#undef G3_ATTN_WINDOW_ARGS
+
+extern "C" int g3_self_attn_window_q_rows(void) { return W4_BQ; }
+
+extern "C" int g3_self_attn_window_tiles(int S, int frame_len, int window_frames, int sink_frames, int64_t* attended, int64_t* dense) {
+    if (!attended || !dense) return g3_set_error(G3_ERR_ARG, "g3_self_attn_window_tiles: null result pointer");
+    if (int rc = attn_window_check("g3_self_attn_window_tiles", S, frame_len, window_frames, sink_frames)) return rc;
+    const int T = S / frame_len, W = window_frames < T ? window_frames : T, s = sink_frames < T ? sink_frames : T;
+    const int n_blk = (S + W4_BQ - 1) / W4_BQ;
+    *dense = (int64_t)n_blk * (S / KVB);
+    *attended = 0;
+    for (int b = 0; b < n_blk; ++b) {
+        int sink_end, lo, hi;
+        attn_window_range(S, frame_len, W, s, b, sink_end, lo, hi);
+        *attended += (hi - lo + sink_end) / KVB;
+    }
+    if (W >= T - 1 || s >= T) *attended = *dense;  // the launch is the dense one
+    return G3_OK;
 }
 
 /* ---- dry run: the kernel a call to `entry` with these arguments would launch, or NULL with the call's own refusal in g3_last_error(). Never touches HIP. ---- */

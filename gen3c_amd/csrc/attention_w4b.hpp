@@ -33,6 +33,11 @@
 // NM + CP (flash_attn_fwd_w4b_nm_carry_kernel, g3_self_attn_fwd_bounded_cp_bf16 only): the no-max tile loop over the CP form's key addressing, with
 // the CP form's carry-in epilogue (m_run = the bound). Every launch of a row uses the same reference point, so a key's P does not depend on how
 // the row's keys were split over launches; the parts' (normalised O, LSE) pairs are what the merge kernel and the carry epilogue consume.
+// WIN (W4B_WIN 1 on top of W4B_CP 1: flash_attn_fwd_w4b_win_kernel, with W4B_NM 1 flash_attn_fwd_w4b_nm_win_kernel; g3_self_attn_fwd_window_bf16 only):
+// the CP form's key range PER WORKGROUP instead of per launch. Self-attention over tokens ordered (t, h, w): query block qblk attends the key frames
+// of its rows' temporal window and an always-attended prefix of sink frames (the function: gen3c_hip.h) - keys [0, sink_end) u [lo, hi), one
+// skipped range, derived in the prologue from qblk and three kernel arguments (AttnParams::win_*), wave-uniform. No table is read, nothing is
+// added to the tile loop, there is no carry-in state; the epilogue and the stores are the CP form's.
 
 #ifndef G3_ATTENTION_W4B_HELPERS
 #define G3_ATTENTION_W4B_HELPERS
@@ -213,7 +218,14 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 // starts with its operands in the ring; the four pair units that covered the head reads move into region A as half units.
 #endif  // G3_ATTENTION_W4B_HELPERS
 
-#if W4B_NM && W4B_CP
+#if W4B_WIN && !W4B_CP
+#error "the window form is built on the CP form"
+#endif
+#if W4B_NM && W4B_WIN
+#define W4B_KERNEL flash_attn_fwd_w4b_nm_win_kernel
+#elif W4B_WIN
+#define W4B_KERNEL flash_attn_fwd_w4b_win_kernel
+#elif W4B_NM && W4B_CP
 #define W4B_KERNEL flash_attn_fwd_w4b_nm_carry_kernel
 #elif W4B_NM
 #define W4B_KERNEL flash_attn_fwd_w4b_nm_kernel
@@ -226,6 +238,7 @@ template <bool XB>
 __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     constexpr bool CP = W4B_CP;
     constexpr bool NM = W4B_NM;
+    constexpr bool WIN = W4B_WIN;
     static_assert(!NM || XB, "the no-max form exists for the XB kernels only");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
@@ -259,7 +272,31 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     const float* carry_o = nullptr;
     const float* carry_lse = nullptr;
     uint32_t skip_t0 = 0u, skip_nt = 0u, v_skip = 0u;
-    if constexpr (CP) {
+    int nt = p.Skv / KVB;  // launcher: S_kv % 64 == 0
+    if constexpr (WIN) {
+        // the block's key set (launcher: Sq == Skv, a multiple of the frame length, itself a multiple of 64; win_frames, win_sink <= frames): its rows lie
+        // in frames f0..f1, the window is frames [f0 - W, f1 + W + 1) clipped to the sequence, the sink frames [0, s). A sink that reaches the window
+        // leaves one range from key 0; no sink moves the K / V^T bases to the window; otherwise the keys between the two are the CP form's skipped range.
+        const uint32_t fl = (uint32_t)p.win_frame_len, wf = (uint32_t)p.win_frames;
+        const uint32_t n_frames = (uint32_t)p.Skv / fl;
+        const uint32_t r0 = (uint32_t)qblk * (uint32_t)W4_BQ, r1 = min(r0 + (uint32_t)W4_BQ, (uint32_t)p.Sq) - 1u;
+        const uint32_t f0 = r0 / fl, f1 = r1 / fl;
+        // (wave-uniform by construction; the integer divisions run on the vector ALU, so the results are moved back to scalar registers by hand)
+        const uint32_t lo = __builtin_amdgcn_readfirstlane((f0 > wf ? f0 - wf : 0u) * fl);
+        uint32_t hi = __builtin_amdgcn_readfirstlane(min(n_frames, f1 + wf + 1u) * fl);
+        const uint32_t sink_len = (uint32_t)p.win_sink * fl, sink_end = min(sink_len, lo);
+        if (sink_len >= lo) hi = max(hi, sink_len);  // a sink that reaches the window: one range from key 0, which ends where the longer of the two ends
+        if (sink_end == 0u) {
+            Kb += (int64_t)lo * p.k_row;
+            Vb += lo;
+        } else {
+            skip_t0 = sink_end / KVB;
+            skip_nt = (lo - sink_end) / KVB;
+            v_skip = 2u * (lo - sink_end);
+        }
+        nt = (int)((hi - lo + sink_end) / KVB);
+        asm volatile("" : "+s"(nt), "+s"(skip_t0), "+s"(skip_nt), "+s"(v_skip));
+    } else if constexpr (CP) {
         carry_o = p.carry_o;
         carry_lse = p.carry_lse;
         skip_t0 = (uint32_t)p.kv_skip_begin / KVB;
@@ -344,7 +381,6 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     float ta[2] = {0.f, 0.f}, tb[2] = {0.f, 0.f};  // exp2 results of a pair unit, one set per step parity (see the note on statement boundaries)
     float pe[2][2] = {{0.f, 0.f}, {0.f, 0.f}};     // XB: row-sum accumulators of the half units (half 0; [step parity][lane of the pair])
     float xa[2], xb[2];                            // XB: exp2 results of a half unit between its two steps
-    const int nt = p.Skv / KVB;                     // launcher: S_kv % 64 == 0
 
     // ---- prologue: K(0), V(0) (and K(1)) by LDS-DMA; scores of tile 0 with C = 0, then made relative to their exact row maximum (NM: to the bound)
     dma_tile_builtin(Kbytes, dma_off, sK);

@@ -215,6 +215,7 @@ class VideoExtendGeneralDIT(nn.Module):
         init_weights: bool = True,
         linear_precision: str = "bf16",
         mxfp8_producers: str = "separate",
+        self_attn_window=None,
     ) -> None:
         super().__init__()
         # the GEN3C-Cosmos-7B configuration space (config/base/net.py:23-43 + cosmos-1-diffusion-gen3c.py:38-43);
@@ -255,6 +256,9 @@ class VideoExtendGeneralDIT(nn.Module):
         self.set_linear_precision(linear_precision)
         self.mxfp8_producers = "separate"
         self.set_mxfp8_producers(mxfp8_producers)
+        self.self_attn_window = None
+        if self_attn_window is not None:
+            self.set_self_attn_window(*self_attn_window)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
         D, Hd = model_channels, self.head_dim
@@ -362,6 +366,37 @@ class VideoExtendGeneralDIT(nn.Module):
         if precision != self.linear_precision:
             self._packed = None  # the quantised weights are part of the packed weight set
         self.linear_precision = precision
+
+    def set_self_attn_window(self, window_frames, sink_frames: int = 1) -> None:
+        """None (default, the parity path): dense self-attention. window_frames W >= 0, sink_frames s >= 0: training-free local attention - the
+        single-GPU self-attention of every block runs ops.self_attn_window with frame_len = Hp * Wp of the forward's own shape: each block of 256
+        query tokens attends the latent frames within W of its own frames and the first s latent frames (in GEN3C the conditioning frames), exact
+        softmax over those keys (ops.window_attn_mask is the function), and the kernel skips the key tiles outside. A window that covers every
+        frame of the forward (W >= frames - 1 or s >= frames) runs the dense launch. Outside the bf16 parity statement: it changes the model's
+        function, and its effect on picture quality with trained weights is unmeasured. The forward raises ValueError
+        where Hp * Wp is no multiple of 64 and under context parallelism."""
+        if window_frames is None:
+            self.self_attn_window = None
+            return
+        W, s = int(window_frames), int(sink_frames)
+        if W < 0 or s < 0:
+            raise ValueError(f"self_attn_window: window_frames {W} and sink_frames {s} must be >= 0")
+        self.self_attn_window = (W, s)
+
+    def _self_attn_window_for(self, Tp: int, Hp: int, Wp: int):
+        """The (frame_len, W, s) of this forward's self-attention launches, or None for the dense launch."""
+        if self.self_attn_window is None:
+            return None
+        W, s = self.self_attn_window
+        if self._cp_attn is not None:
+            raise ValueError(f"self_attn_window=({W}, {s}) with context parallelism over {self.cp_size} ranks: the window form is single-GPU only. Windows under "
+                             "key sharding would also cut the K / V exchange; that is later work")
+        if (Hp * Wp) % 64 != 0:
+            raise ValueError(f"self_attn_window=({W}, {s}): {Hp} x {Wp} = {Hp * Wp} tokens per latent frame is not a multiple of 64, the kernel's key tile "
+                             "(the product size is 44 x 80 = 3520 = 55 x 64)")
+        if W >= Tp - 1 or s >= Tp:
+            return None  # the window covers every frame: the dense launch
+        return (Hp * Wp, W, s)
 
     def set_mxfp8_producers(self, producers: str) -> None:
         """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16". Under "mxfp6" the setting is
@@ -606,6 +641,7 @@ class VideoExtendGeneralDIT(nn.Module):
         M = crossattn_emb.shape[1]
         nH = self.num_heads
         ca_kv, ca_dense = self._cross_attention_kv(pk, crossattn_emb)
+        fa_window = self._self_attn_window_for(Tp, Hp, Wp)
         if not self.cross_attention_skip_zero_context:
             ca_dense = 0
         for bi, blk in enumerate(pk["blocks"][: self._tune_blocks] if self._tune_blocks else pk["blocks"]):
@@ -670,7 +706,9 @@ class VideoExtendGeneralDIT(nn.Module):
                     ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)  # one pass over q | k
                     q, k = qkv[:, :D], qkv[:, D:2 * D]
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
-                if _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
+                if fa_window is not None:  # opt-in local attention (a bound out of the no-max form's range, or none: the same kernel with its running maximum)
+                    o = ops.self_attn_window(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, *fa_window)
+                elif _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
                     o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"], mfma16=_self_attn_mfma16())
                 else:
                     o = ops.flash_attn(q, k, vt, S, S, B, nH)

@@ -515,6 +515,47 @@ def self_attn_bounded(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: in
     return _attn_call("bounded16" if mfma16 else "bounded", q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, logit_bound=logit_bound)
 
 
+def self_attn_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, S: int, B: int, H: int, logit_bound: float, frame_len: int, window_frames: int,
+                     sink_frames: int, out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+    """Self-attention over a temporal frame window (opt-in local attention; g3_self_attn_fwd_window_bf16): q, k [S*B, H*128] with tokens ordered
+    (t, h, w), frame_len tokens per latent frame, vt plain [B, H, 128, ldvt]. Each block of window_q_rows() query rows attends the keys of the frames
+    within window_frames of its rows' frames and of the first sink_frames frames - window_attn_mask is the function - and the output is the exact
+    softmax over those keys. logit_bound as for self_attn_bounded (out of range: the running-maximum form of the same kernel). A window that covers
+    every key is self_attn_bounded(variant=11), bit for bit. The one-wave-per-SIMD kernel's operand rules; no fallback."""
+    return _attn_call("window", q, k, vt, S, S, B, H, out, softmax_scale, 11, False, logit_bound=logit_bound,
+                      window=(int(frame_len), int(window_frames), int(sink_frames)))
+
+
+def window_q_rows() -> int:
+    """Query rows per block of the window form's key sets (the kernel's workgroup)."""
+    return _lib.load().g3_self_attn_window_q_rows()
+
+
+def window_attn_tiles(S: int, frame_len: int, window_frames: int, sink_frames: int):
+    """(attended, dense): the (query block, 64-key tile) pairs a self_attn_window launch visits and the dense launch's count."""
+    import ctypes
+    att, dense = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().g3_self_attn_window_tiles(S, frame_len, window_frames, sink_frames, ctypes.byref(att), ctypes.byref(dense)), "g3_self_attn_window_tiles")
+    return att.value, dense.value
+
+
+def window_attn_mask(S: int, frame_len: int, window_frames: int, sink_frames: int, q_rows: Optional[int] = None) -> torch.Tensor:
+    """CPU bool [S, S]: mask[i, j] = query row i attends key j under self_attn_window - the written-down definition of the function (gen3c_hip.h).
+    With T = S / frame_len frames, the block of q_rows (default window_q_rows()) query rows that holds row i lies in frames f0..f1 and attends the
+    keys of frames [max(0, f0 - W), min(T, f1 + W + 1)) and of frames [0, min(s, T)): block-granular, a superset of row i's own window."""
+    if S <= 0 or frame_len <= 0 or S % frame_len or window_frames < 0 or sink_frames < 0:
+        raise ValueError(f"window_attn_mask: S {S} must be a positive multiple of frame_len {frame_len}, window_frames {window_frames} and sink_frames {sink_frames} >= 0")
+    q_rows = window_q_rows() if q_rows is None else q_rows
+    T = S // frame_len
+    rows = torch.arange(S)
+    r0 = rows // q_rows * q_rows
+    f0 = r0 // frame_len
+    f1 = (torch.clamp(r0 + q_rows, max=S) - 1) // frame_len
+    kf = rows // frame_len  # frame of every key
+    lo, hi = torch.clamp(f0 - window_frames, min=0), torch.clamp(f1 + window_frames + 1, max=T)
+    return ((kf[None, :] >= lo[:, None]) & (kf[None, :] < hi[:, None])) | (kf[None, :] < min(sink_frames, T))
+
+
 # The launching entry points ops uses: (enum g3_attn_entry, symbol, its arguments by name in call order - the stream follows). g3_attn_plan_bf16 takes
 # the union (_ATTN_PLAN_ARGS), so the kernel a timer records is the dry run's answer for the very arguments launched ("bounded16": g3_attn_plan16_bf16,
 # the dry run in which entry 4 stands for g3_self_attn_fwd_bounded16_bf16).
@@ -528,13 +569,16 @@ _ATTN_ENTRIES = {
     "bounded16": (4, "g3_self_attn_fwd_bounded16_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
     "carry": (5, "g3_flash_attn_fwd_carry_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("variant",)),
     "bounded_cp": (6, "g3_self_attn_fwd_bounded_cp_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("logit_bound", "variant")),
+    # (no value of enum g3_attn_entry: its dry run is g3_attn_window_plan_bf16, which takes exactly the call's arguments)
+    "window": (None, "g3_self_attn_fwd_window_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] +
+               ("logit_bound", "frame_len", "window_frames", "sink_frames")),
 }
 _ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] + ("logit_bound", "variant"))
 
 
 def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
-               logit_bound=0.0):
-    """The one marshaller of flash_attn and self_attn_bounded, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
+               logit_bound=0.0, window=None):
+    """The one marshaller of flash_attn, self_attn_bounded and self_attn_window, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
     launch and the kernel timer."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
     skv_all = Skv + skip_len  # keys the operands hold
@@ -571,6 +615,9 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
              kv_skip_len=skip_len, carry_o=co, carry_lse=cl, o=0 if partial else _dev(out, "out"), o_partial=_dev(out, "o_part", torch.float32) if partial else 0,
              lse=_dev(lse, "lse", torch.float32) if partial else 0, o_row=ldo * B, o_batch=ldo, o_head=128, Sq=Sq, Skv=Skv, kv_dense=kv_dense, B=B, H=H,
              head_dim=128, softmax_scale=float(1.0 / math.sqrt(128) if softmax_scale is None else softmax_scale), logit_bound=float(logit_bound), variant=int(variant))
+    if window is not None:
+        assert vt.dim() == 4 and Sq == Skv, "the window form takes plain V^T and Sq == Skv"
+        a.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2])
     entry_id, symbol, names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
     timer = None
@@ -586,8 +633,13 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
             meta.update(kv_dense=kv_dense, q_norm=q_norm_weight is not None)
         elif entry in ("carry", "bounded_cp"):
             meta.update(carry=carry is not None, kv_skip=skip_len)
-        plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
-        meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
+        if entry == "window":
+            attended, dense = window_attn_tiles(Sq, *window)
+            meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], tile_density=attended / dense)
+            meta["kernel"] = lib.g3_attn_window_plan_bf16(*[a[n] for n in names]).decode()
+        else:
+            plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
+            meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
         _KERNEL_TIMERS.append(("flash_attn_fwd", meta, timer))
     return (out, lse) if partial else out
 

@@ -269,6 +269,35 @@ const char* g3_attn_plan16_bf16(int entry, const void* q, int64_t q_row, int64_t
                                 const float* carry_lse, void* o, float* o_partial, float* lse, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq,
                                 int Skv, int kv_dense, int B, int H, int head_dim, float softmax_scale, float logit_bound, int variant);
 
+/* Self-attention (Sq == Skv == S) over a temporal FRAME WINDOW, for tokens ordered (t, h, w): opt-in, training-free local attention. Parameters:
+ *   frame_len      tokens per latent frame (Hp * Wp); T = S / frame_len frames
+ *   window_frames  W >= 0: a query attends the frames within W of its own
+ *   sink_frames    s >= 0: the first s frames are attended by every query (in GEN3C the first latent frames are the conditioning frames)
+ *   the query block: g3_self_attn_window_q_rows() = 256 rows, the kernel's workgroup
+ * Query block b holds rows [256 b, min(256 b + 256, S)), which lie in frames f0..f1. It attends
+ *   the keys of frames [max(0, f0 - W), min(T, f1 + W + 1))  and  the keys of frames [0, min(s, T)),
+ * and the output is the exact softmax over that key set. The key set is BLOCK-granular: a block that straddles a frame boundary attends the union
+ * of its rows' windows, a superset of each row's own window (no mask inside the kernel's tile loop; at 3 520 tokens per frame = 13.75 blocks about
+ * one block in 14 straddles). Every workgroup of flash_attn_fwd_w4b_nm_win_kernel<true> (0 < logit_bound * log2(e) <= 60, as for
+ * g3_self_attn_fwd_bounded_bf16) or flash_attn_fwd_w4b_win_kernel<true> (any other bound: the running-maximum form) derives its key range from
+ * its block index and these numbers; the operand rules are variant 11's. When the window covers every key of every block (W >= T - 1 or s >= T)
+ * the call IS g3_self_attn_fwd_bounded_bf16 with variant 11, bit for bit.
+ * G3_ERR_ARG, with nothing launched: S, frame_len not positive multiples of 64 or S no multiple of frame_len; negative W or s; a V^T leading
+ * dimension below ceil64(S); operands beyond the kernel's 32-bit byte offsets (the carry entry's arithmetic over all S keys); misaligned
+ * pointers or strides; head_dim != 128.
+ * g3_attn_window_plan_bf16: the dry run - the kernel's name, or NULL with g3_last_error() set exactly as the call sets it; no HIP call, no pointer
+ * dereferenced. g3_self_attn_window_tiles: the (query block, 64-key tile) pairs such a launch visits and the dense launch's count. */
+int g3_self_attn_fwd_window_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                 int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                 int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, float softmax_scale, float logit_bound,
+                                 int frame_len, int window_frames, int sink_frames, void* stream);
+const char* g3_attn_window_plan_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                     int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                     int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, float softmax_scale, float logit_bound,
+                                     int frame_len, int window_frames, int sink_frames);
+int g3_self_attn_window_q_rows(void);
+int g3_self_attn_window_tiles(int S, int frame_len, int window_frames, int sink_frames, int64_t* attended, int64_t* dense);
+
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);
