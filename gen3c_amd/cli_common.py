@@ -70,6 +70,10 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "picture quality with trained weights unmeasured: DESIGN.md section 11; same as G3_SELF_ATTN_WINDOW=\"W,S\")")
     p.add_argument("--self_attn_sink_frames", type=int, default=None, metavar="S",
                    help="with --self_attn_window_frames: the first S latent frames (the conditioning frames) are attended by every query (default 1)")
+    p.add_argument("--self_attn_window_cp", action="store_true",
+                   help="with --self_attn_window_frames and --num_gpus > 1: run the window under context parallelism - every rank receives only the latent frames "
+                        "within W of its own and the sink frames (the \"window_halo\" schedule) instead of refusing (opt-in, default off; same as a third field "
+                        "in G3_SELF_ATTN_WINDOW=\"W,S,cp\")")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -119,6 +123,8 @@ def self_attn_window_requested(args):
         if not env:
             return None
         parts = [x.strip() for x in env.split(",")]
+        if len(parts) == 3 and parts[2] == "cp":  # (the context-parallel switch: self_attn_window_cp_requested)
+            parts = parts[:2]
         if len(parts) not in (1, 2) or not all(x.lstrip("-").isdigit() for x in parts):
             raise ValueError(f"G3_SELF_ATTN_WINDOW={env!r}: expected \"W\" or \"W,S\" (window and sink in latent frames)")
         W, s = int(parts[0]), int(parts[1]) if len(parts) == 2 else None
@@ -126,6 +132,15 @@ def self_attn_window_requested(args):
     if W < 0 or s < 0:
         raise ValueError(f"self-attention window: window frames {W} and sink frames {s} must be >= 0")
     return W, s
+
+
+def self_attn_window_cp_requested(args) -> bool:
+    """--self_attn_window_cp, or "cp" as the third field of G3_SELF_ATTN_WINDOW="W,S,cp": the window also runs under context parallelism (opt-in inside
+    the opt-in, default off). Means nothing without a window."""
+    if getattr(args, "self_attn_window_cp", False):
+        return True
+    parts = [x.strip() for x in os.environ.get("G3_SELF_ATTN_WINDOW", "").split(",")]
+    return len(parts) == 3 and parts[2] == "cp"
 
 
 def log_ignored_flags(args, log=print) -> List[str]:
@@ -255,8 +270,10 @@ class Session:
                 net._cp_attn.configure(bounded=True)
         window = self_attn_window_requested(args)
         if window is not None:
-            net.set_self_attn_window(*window)  # (with context parallelism the first forward refuses it, with the numbers)
-            print(f"[gen3c_amd] self-attention window: {window[0]} latent frame(s) either side + {window[1]} sink frame(s) (opt-in; outside the parity statement)")
+            window_cp = self_attn_window_cp_requested(args)
+            net.set_self_attn_window(*window, context_parallel=window_cp)  # (with context parallelism and no switch the first forward refuses it, with the numbers)
+            print(f"[gen3c_amd] self-attention window: {window[0]} latent frame(s) either side + {window[1]} sink frame(s) (opt-in; outside the parity statement)"
+                  + ("; under context parallelism: the window_halo exchange" if window_cp and self.cp_size > 1 else ""))
         if self.cfg_size > 1:
             self.cfg_group = parallel_state.get_cfg_parallel_group()
             print(f"[gen3c_amd] --cfg_parallel: 2 guidance branches x {self.cp_size} context-parallel rank(s); this rank runs the "

@@ -79,6 +79,10 @@ struct AttnParams {
     // that divides Sq == Skv), the temporal window and the always-attended prefix in frames (the launcher clamps both to the frame count). Every
     // workgroup derives its own key range from these and its query block; no other kernel reads them.
     int win_frame_len, win_frames, win_sink;
+    // the key-sharded window form (g3_self_attn_fwd_window_cp_bf16) on top of these: Q's row 0 is frame win_q_frame0 of the win_total_frames of the
+    // sequence, and K / V^T hold the global frames [0, win_buf_head) ++ [win_buf_head + win_buf_gap, ...). g3_self_attn_fwd_window_bf16 is
+    // win_q_frame0 = win_buf_head = win_buf_gap = 0, win_total_frames = Skv / win_frame_len.
+    int win_q_frame0, win_total_frames, win_buf_head, win_buf_gap;
 };
 
 G3_DEVICE int k_off(int row, int chunk) { return row * HD + ((chunk ^ (row & 15)) << 3); }          // [64][128]
@@ -1043,6 +1047,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 struct AttnOperand { const void* ptr = nullptr; int64_t row = 0, batch = 0, head = 0; };  // element strides
 constexpr int ATTN_ENTRY_WINDOW = G3_ATTN_ENTRY_BOUNDED_CP + 1;  // g3_self_attn_fwd_window_bf16: has its own dry run, so it is no value of enum g3_attn_entry
+constexpr int ATTN_ENTRY_WINDOW_CP = G3_ATTN_ENTRY_BOUNDED_CP + 2;  // g3_self_attn_fwd_window_cp_bf16: likewise (g3_attn_window_cp_plan_bf16)
 struct AttnCall {
     int entry = G3_ATTN_ENTRY_FWD;  // the public entry point called: it decides which checks run and whose name a refusal carries
     AttnOperand q, k, vt, o;        // o.ptr: the bf16 result; o's strides also address o_partial and carry_o
@@ -1056,6 +1061,7 @@ struct AttnCall {
     float logit_bound = 0.f;
     int mfma16 = 0;  // g3_self_attn_fwd_bounded16_bf16: the 16x16x32 tile loop where the plain no-max kernel would run
     int win_frame_len = 0, win_frames = 0, win_sink = 0;  // g3_self_attn_fwd_window_bf16
+    int win_total_frames = 0, win_q_frame0 = 0, win_buf_head = 0, win_buf_tail0 = 0;  // g3_self_attn_fwd_window_cp_bf16: T, the query origin, a and b
     void* stream = nullptr;
 };
 
@@ -1063,7 +1069,7 @@ struct AttnCall {
 struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_rows; };
 // (the row only g3_self_attn_fwd_bounded16_bf16 reaches, apart from the rows the recorded launcher decisions cover: tests/golden/attn_plan_parent.json)
 #define G3_ATTN_KERNELS16(X) X(AK_W4C_NM, W4_THREADS, W4_BQ, flash_attn_fwd_w4c_nm_kernel)
-// (the rows only g3_self_attn_fwd_window_bf16 reaches)
+// (the rows only g3_self_attn_fwd_window_bf16 and g3_self_attn_fwd_window_cp_bf16 reach)
 #define G3_ATTN_KERNELS_WIN(X) \
     X(AK_W4BX_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_win_kernel<true>) X(AK_W4BX_NM_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_win_kernel<true>)
 #define G3_ATTN_KERNELS(X) \
@@ -1121,10 +1127,11 @@ static const AttnKernel& attn_kernel_for(int variant, int Skv, bool cp_form, boo
 }
 
 // The window form's key set of query block b (the function: gen3c_hip.h; the kernel's prologue computes the same from the same numbers): keys
-// [0, sink_end) u [lo, hi). S a multiple of frame_len, W and s within [0, S / frame_len].
-static void attn_window_range(int S, int frame_len, int W, int s, int b, int& sink_end, int& lo, int& hi) {
-    const int T = S / frame_len, r0 = b * W4_BQ, r1 = (r0 + W4_BQ < S ? r0 + W4_BQ : S) - 1;
-    const int f0 = r0 / frame_len, f1 = r1 / frame_len;
+// [0, sink_end) u [lo, hi) in GLOBAL key coordinates. The S query rows start at frame q_frame0 of the sequence's T frames (the single-GPU form:
+// q_frame0 0, T = S / frame_len); S a multiple of frame_len, W and s within [0, T].
+static void attn_window_range(int S, int frame_len, int T, int q_frame0, int W, int s, int b, int& sink_end, int& lo, int& hi) {
+    const int r0 = b * W4_BQ, r1 = (r0 + W4_BQ < S ? r0 + W4_BQ : S) - 1;
+    const int f0 = r0 / frame_len + q_frame0, f1 = r1 / frame_len + q_frame0;
     lo = (f0 > W ? f0 - W : 0) * frame_len;
     hi = (f1 + W + 1 < T ? f1 + W + 1 : T) * frame_len;
     const int sink_len = s * frame_len;
@@ -1139,6 +1146,36 @@ static int attn_window_check(const char* fn, int S, int frame_len, int W, int s)
     return G3_OK;
 }
 
+// The key-sharded window form: the S_q query rows are frames [q_frame0, q_frame0 + S_q / frame_len) of T, the K / V^T operand of S_kv_buf keys holds the
+// global frames [0, a) ++ [b, c). G3_OK with c, or the refusal. The loop over the query blocks is what keeps a wrong halo plan from becoming a read
+// outside the operand: every block's key set must lie inside the buffer (keys no block attends are allowed; the kernel skips them).
+static int attn_window_cp_check(const char* fn, int Sq, int Skv_buf, int frame_len, int T, int q_frame0, int a, int b, int W, int s, int& c_out) {
+    if (Sq <= 0 || Skv_buf <= 0 || frame_len <= 0 || (frame_len % KVB))
+        return g3_set_error(G3_ERR_ARG, "%s: Sq %d, Skv_buf %d and frame_len %d must be positive, frame_len a multiple of 64", fn, Sq, Skv_buf, frame_len);
+    if (W < 0 || s < 0) return g3_set_error(G3_ERR_ARG, "%s: window_frames %d and sink_frames %d must be >= 0", fn, W, s);
+    if (Sq % frame_len) return g3_set_error(G3_ERR_ARG, "%s: Sq %d is not a multiple of frame_len %d (a rank owns whole frames)", fn, Sq, frame_len);
+    if (T <= 0 || q_frame0 < 0) return g3_set_error(G3_ERR_ARG, "%s: total_frames %d must be positive and q_frame0 %d >= 0", fn, T, q_frame0);
+    if (a < 0 || a > b) return g3_set_error(G3_ERR_ARG, "%s: buf_head_frames %d and buf_tail_frame0 %d must satisfy 0 <= a <= b", fn, a, b);
+    if (q_frame0 + Sq / frame_len > T)
+        return g3_set_error(G3_ERR_ARG, "%s: the queries' frames [%d, %d) reach beyond total_frames %d", fn, q_frame0, q_frame0 + Sq / frame_len, T);
+    const int c = Skv_buf / frame_len - a + b;  // the end of the tail piece that Skv_buf implies
+    if ((Skv_buf % frame_len) || c < b || c > T)
+        return g3_set_error(G3_ERR_ARG, "%s: Skv_buf %d is not (a + c - b) * frame_len for a c in [b, total_frames]: a %d, b %d, frame_len %d, total_frames %d", fn,
+                            Skv_buf, a, b, frame_len, T);
+    const int Wc = W < T ? W : T, sc = s < T ? s : T;
+    const int64_t A = (int64_t)a * frame_len, Bk = (int64_t)b * frame_len, C = (int64_t)c * frame_len;
+    auto held = [&](int64_t x0, int64_t x1) { return x0 >= x1 || x1 <= A || (x0 >= Bk && x1 <= C) || (A == Bk && x1 <= C); };
+    for (int blk = 0; blk < (Sq + W4_BQ - 1) / W4_BQ; ++blk) {
+        int sink_end, lo, hi;
+        attn_window_range(Sq, frame_len, T, q_frame0, Wc, sc, blk, sink_end, lo, hi);
+        if (!held(0, sink_end) || !held(lo, hi))
+            return g3_set_error(G3_ERR_ARG, "%s: query block %d attends keys [0, %d) u [%d, %d), which the buffer of frames [0, %d) ++ [%d, %d) x %d keys does not hold",
+                                fn, blk, sink_end, lo, hi, a, b, c, frame_len);
+    }
+    c_out = c;
+    return G3_OK;
+}
+
 struct AttnPlan { AttnParams p; const AttnKernel* kernel; dim3 grid; };
 constexpr size_t ATTN_SMEM = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);  // 64 KiB
 
@@ -1147,21 +1184,30 @@ constexpr size_t ATTN_SMEM = (size_t)2 * (KVB * HD + HD * KVB) * sizeof(bf16_t);
 static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     AttnCall c = call;  // (a skip at the front moves c.k / c.vt)
     const bool cp_form = c.entry == G3_ATTN_ENTRY_CARRY || c.entry == G3_ATTN_ENTRY_BOUNDED_CP;
-    const bool window = c.entry == ATTN_ENTRY_WINDOW;
+    const bool window_cp = c.entry == ATTN_ENTRY_WINDOW_CP;
+    const bool window = c.entry == ATTN_ENTRY_WINDOW || window_cp;
     const char* fn = cp_form ? "g3_flash_attn_fwd_carry_bf16" : c.entry == G3_ATTN_ENTRY_BOUNDED ? "g3_self_attn_fwd_bounded_bf16" :
-                     window ? "g3_self_attn_fwd_window_bf16" : "g3_flash_attn_fwd_ex_bf16";
+                     window_cp ? "g3_self_attn_fwd_window_cp_bf16" : window ? "g3_self_attn_fwd_window_bf16" : "g3_flash_attn_fwd_ex_bf16";
     uint32_t kv_skip_vt_bytes = 0;
-    if (window) {  // (Sq == Skv == S, variant 11, plain V^T, a bf16 output: the entry sets them)
+    if (window) {  // (variant 11, plain V^T, a bf16 output: the entries set them; g3_self_attn_fwd_window_bf16 also Sq == Skv == S)
         if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || !c.o.ptr) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
-        if (int rc = attn_window_check(fn, c.Skv, c.win_frame_len, c.win_frames, c.win_sink)) return rc;
+        if (window_cp) {  // (Skv = the compact buffer's keys)
+            int buf_end;
+            if (int rc = attn_window_cp_check(fn, c.Sq, c.Skv, c.win_frame_len, c.win_total_frames, c.win_q_frame0, c.win_buf_head, c.win_buf_tail0, c.win_frames,
+                                              c.win_sink, buf_end)) return rc;
+        } else {
+            if (int rc = attn_window_check(fn, c.Skv, c.win_frame_len, c.win_frames, c.win_sink)) return rc;
+            c.win_total_frames = c.Skv / c.win_frame_len;
+        }
         if (c.vt.row < c.Skv)  // (S % 64 == 0: S is its own ceil64; the kernel reads whole V^T tiles unguarded)
-            return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S) %d", fn, (long long)c.vt.row, c.Skv);
-        const int T = c.Skv / c.win_frame_len;
+            return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S) %d", fn, (long long)c.vt.row, c.Skv);  // (window_cp: S = Skv_buf)
+        const int T = c.win_total_frames;
         c.win_frames = c.win_frames < T ? c.win_frames : T;
         c.win_sink = c.win_sink < T ? c.win_sink : T;
     }
     // a window that covers every key of every block: the call IS g3_self_attn_fwd_bounded_bf16 with variant 11 (the dense kernel, the dense epilogue)
-    const bool win_dense = window && (c.win_frames >= c.Skv / c.win_frame_len - 1 || c.win_sink >= c.Skv / c.win_frame_len);
+    // (the key-sharded form always runs the window kernels: their prologue finds the whole buffer by itself)
+    const bool win_dense = window && !window_cp && (c.win_frames >= c.Skv / c.win_frame_len - 1 || c.win_sink >= c.Skv / c.win_frame_len);
     if (c.entry == G3_ATTN_ENTRY_KVSEG && c.vt_seg_len <= 0) return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_kvseg_bf16: vt_seg_len must be positive");
     if (c.entry == G3_ATTN_ENTRY_CROSS && c.kv_dense < 0) return g3_set_error(G3_ERR_ARG, "g3_cross_attn_fwd_bf16: kv_dense must be >= 0 (0 = every key through the loop)");
     if (c.entry >= G3_ATTN_ENTRY_EX) {  // the entries with a per-call variant and o_partial / lse
@@ -1272,6 +1318,7 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     p.kv_skip_begin = c.kv_skip_begin; p.kv_skip_len = c.kv_skip_len; p.kv_skip_vt_bytes = kv_skip_vt_bytes;
     p.logit_bound_log2 = attn_bound_log2(c.logit_bound);
     p.win_frame_len = p.win_frames = p.win_sink = 0;
+    p.win_q_frame0 = p.win_total_frames = p.win_buf_head = p.win_buf_gap = 0;
     // bounded logits (only the two bounded entries carry a bound): the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems
     // only; g3_self_attn_fwd_bounded_cp_bf16: also with segmented V^T, and with a carry-in state or a skipped key range. Everything else runs as it always did.
     const bool no_max = attn_bound_usable(p.logit_bound_log2) && (c.entry == G3_ATTN_ENTRY_BOUNDED_CP || (!cp_form && c.vt_seg_len == 0));
@@ -1282,6 +1329,8 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     if (window && !win_dense) {  // (variant 11 here: S % 64 == 0, the V^T leading dimension and the operand span were checked above)
         plan.kernel = &attn_kernels[no_max ? AK_W4BX_NM_WIN : AK_W4BX_WIN];
         p.win_frame_len = c.win_frame_len; p.win_frames = c.win_frames; p.win_sink = c.win_sink;
+        p.win_total_frames = c.win_total_frames;  // (g3_self_attn_fwd_window_bf16: S / frame_len, the other three 0 - every key maps to itself)
+        p.win_q_frame0 = c.win_q_frame0; p.win_buf_head = c.win_buf_head; p.win_buf_gap = c.win_buf_tail0 - c.win_buf_head;
     }
     plan.grid = dim3((c.Sq + plan.kernel->q_rows - 1) / plan.kernel->q_rows, c.H, c.B);
     if (variant == 10 || variant == 11) {  // w4b (attention_w4b.hpp): optionally a 1-D grid that gives every XCD its own (batch, head) pairs
@@ -1454,10 +1503,59 @@ extern "C" int g3_self_attn_window_tiles(int S, int frame_len, int window_frames
     *attended = 0;
     for (int b = 0; b < n_blk; ++b) {
         int sink_end, lo, hi;
-        attn_window_range(S, frame_len, W, s, b, sink_end, lo, hi);
+        attn_window_range(S, frame_len, T, 0, W, s, b, sink_end, lo, hi);
         *attended += (hi - lo + sink_end) / KVB;
     }
     if (W >= T - 1 || s >= T) *attended = *dense;  // the launch is the dense one
+    return G3_OK;
+}
+
+/* ---- the key-sharded window form: one rank's query rows over a compact K / V^T buffer of the frames [0, a) ++ [b, c) (gen3c_hip.h) ---- */
+#define G3_ATTN_WINDOW_CP_PARAMS                                                                                                                        \
+    const void *q, int64_t q_row, int64_t q_batch, int64_t q_head, const void *k, int64_t k_row, int64_t k_batch, int64_t k_head, const void *vt,       \
+        int64_t vt_row, int64_t vt_batch, int64_t vt_head, void *o, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int Skv_buf, int B, int H, \
+        int head_dim, float softmax_scale, float logit_bound, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0, \
+        int window_frames, int sink_frames
+static AttnCall attn_window_cp_call(G3_ATTN_WINDOW_CP_PARAMS) {
+    AttnCall c;
+    c.entry = ATTN_ENTRY_WINDOW_CP;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.variant = 11; c.logit_bound = logit_bound;
+    c.win_frame_len = frame_len; c.win_frames = window_frames; c.win_sink = sink_frames;
+    c.win_total_frames = total_frames; c.win_q_frame0 = q_frame0; c.win_buf_head = buf_head_frames; c.win_buf_tail0 = buf_tail_frame0;
+    c.Sq = Sq; c.Skv = Skv_buf; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale;
+    return c;
+}
+#define G3_ATTN_WINDOW_CP_ARGS                                                                                                                                  \
+    q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, o, o_row, o_batch, o_head, Sq, Skv_buf, B, H, head_dim, softmax_scale, \
+        logit_bound, frame_len, total_frames, q_frame0, buf_head_frames, buf_tail_frame0, window_frames, sink_frames
+extern "C" int g3_self_attn_fwd_window_cp_bf16(G3_ATTN_WINDOW_CP_PARAMS, void* stream) {
+    AttnCall c = attn_window_cp_call(G3_ATTN_WINDOW_CP_ARGS);
+    c.stream = stream;
+    return attn_launch(c);
+}
+extern "C" const char* g3_attn_window_cp_plan_bf16(G3_ATTN_WINDOW_CP_PARAMS) {
+    AttnPlan plan;
+    return attn_plan(attn_window_cp_call(G3_ATTN_WINDOW_CP_ARGS), plan) == G3_OK ? plan.kernel->name : nullptr;
+}
+#undef G3_ATTN_WINDOW_CP_PARAMS
+#undef G3_ATTN_WINDOW_CP_ARGS
+
+extern "C" int g3_self_attn_window_cp_tiles(int Sq, int Skv_buf, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0,
+                                            int window_frames, int sink_frames, int64_t* attended, int64_t* dense) {
+    if (!attended || !dense) return g3_set_error(G3_ERR_ARG, "g3_self_attn_window_cp_tiles: null result pointer");
+    int buf_end;
+    if (int rc = attn_window_cp_check("g3_self_attn_window_cp_tiles", Sq, Skv_buf, frame_len, total_frames, q_frame0, buf_head_frames, buf_tail_frame0,
+                                      window_frames, sink_frames, buf_end)) return rc;
+    const int T = total_frames, W = window_frames < T ? window_frames : T, s = sink_frames < T ? sink_frames : T;
+    const int n_blk = (Sq + W4_BQ - 1) / W4_BQ;
+    *dense = (int64_t)n_blk * ((int64_t)T * frame_len / KVB);  // this rank's query blocks against every key of the sequence
+    *attended = 0;
+    for (int b = 0; b < n_blk; ++b) {
+        int sink_end, lo, hi;
+        attn_window_range(Sq, frame_len, T, q_frame0, W, s, b, sink_end, lo, hi);
+        *attended += (hi - lo + sink_end) / KVB;
+    }
     return G3_OK;
 }
 

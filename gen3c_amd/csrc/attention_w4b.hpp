@@ -33,11 +33,17 @@
 // NM + CP (flash_attn_fwd_w4b_nm_carry_kernel, g3_self_attn_fwd_bounded_cp_bf16 only): the no-max tile loop over the CP form's key addressing, with
 // the CP form's carry-in epilogue (m_run = the bound). Every launch of a row uses the same reference point, so a key's P does not depend on how
 // the row's keys were split over launches; the parts' (normalised O, LSE) pairs are what the merge kernel and the carry epilogue consume.
-// WIN (W4B_WIN 1 on top of W4B_CP 1: flash_attn_fwd_w4b_win_kernel, with W4B_NM 1 flash_attn_fwd_w4b_nm_win_kernel; g3_self_attn_fwd_window_bf16 only):
-// the CP form's key range PER WORKGROUP instead of per launch. Self-attention over tokens ordered (t, h, w): query block qblk attends the key frames
-// of its rows' temporal window and an always-attended prefix of sink frames (the function: gen3c_hip.h) - keys [0, sink_end) u [lo, hi), one
+// WIN (W4B_WIN 1 on top of W4B_CP 1: flash_attn_fwd_w4b_win_kernel, with W4B_NM 1 flash_attn_fwd_w4b_nm_win_kernel; g3_self_attn_fwd_window_bf16 and
+// g3_self_attn_fwd_window_cp_bf16 only): the CP form's key range PER WORKGROUP instead of per launch. Self-attention over tokens ordered (t, h, w):
+// query block qblk attends the key frames of its rows' temporal window and an always-attended prefix of sink frames (the function: gen3c_hip.h) - keys [0, sink_end) u [lo, hi), one
 // skipped range, derived in the prologue from qblk and three kernel arguments (AttnParams::win_*), wave-uniform. No table is read, nothing is
 // added to the tile loop, there is no carry-in state; the epilogue and the stores are the CP form's.
+// The key-sharded form of the same two kernels (g3_self_attn_fwd_window_cp_bf16, four more AttnParams::win_* numbers): Q is one rank's S_local rows,
+// row 0 being frame win_q_frame0 of win_total_frames, and K / V^T a compact buffer of the global frames [0, a) ++ [b, c). The range is computed in
+// global key coordinates as above and then mapped into the buffer; the buffer's own gap shortens (or removes) the skipped range. Query blocks are
+// the rank's own rows [256 b, 256 b + 256): where r * S_local is a multiple of 256 they are the single-GPU blocks and the function is the single-GPU
+// one; otherwise the blocks that straddle a frame boundary differ, and with them (about one block in 14 at 3 520 tokens per frame) the function
+// depends on the number of ranks.
 
 #ifndef G3_ATTENTION_W4B_HELPERS
 #define G3_ATTENTION_W4B_HELPERS
@@ -274,18 +280,25 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     uint32_t skip_t0 = 0u, skip_nt = 0u, v_skip = 0u;
     int nt = p.Skv / KVB;  // launcher: S_kv % 64 == 0
     if constexpr (WIN) {
-        // the block's key set (launcher: Sq == Skv, a multiple of the frame length, itself a multiple of 64; win_frames, win_sink <= frames): its rows lie
-        // in frames f0..f1, the window is frames [f0 - W, f1 + W + 1) clipped to the sequence, the sink frames [0, s). A sink that reaches the window
-        // leaves one range from key 0; no sink moves the K / V^T bases to the window; otherwise the keys between the two are the CP form's skipped range.
+        // the block's key set (launcher: the frame length a multiple of 64 that divides Sq; win_frames, win_sink <= frames): its rows lie in frames
+        // f0..f1 of the win_total_frames of the sequence (row 0 of Q is frame win_q_frame0), the window is frames [f0 - W, f1 + W + 1) clipped to the
+        // sequence, the sink frames [0, s). A sink that reaches the window leaves one range from key 0; no sink moves the K / V^T bases to the window;
+        // otherwise the keys between the two are the CP form's skipped range.
         const uint32_t fl = (uint32_t)p.win_frame_len, wf = (uint32_t)p.win_frames;
-        const uint32_t n_frames = (uint32_t)p.Skv / fl;
+        const uint32_t n_frames = (uint32_t)p.win_total_frames, qf0 = (uint32_t)p.win_q_frame0;
         const uint32_t r0 = (uint32_t)qblk * (uint32_t)W4_BQ, r1 = min(r0 + (uint32_t)W4_BQ, (uint32_t)p.Sq) - 1u;
-        const uint32_t f0 = r0 / fl, f1 = r1 / fl;
+        const uint32_t f0 = r0 / fl + qf0, f1 = r1 / fl + qf0;
         // (wave-uniform by construction; the integer divisions run on the vector ALU, so the results are moved back to scalar registers by hand)
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((f0 > wf ? f0 - wf : 0u) * fl);
+        uint32_t lo = __builtin_amdgcn_readfirstlane((f0 > wf ? f0 - wf : 0u) * fl);
         uint32_t hi = __builtin_amdgcn_readfirstlane(min(n_frames, f1 + wf + 1u) * fl);
         const uint32_t sink_len = (uint32_t)p.win_sink * fl, sink_end = min(sink_len, lo);
         if (sink_len >= lo) hi = max(hi, sink_len);  // a sink that reaches the window: one range from key 0, which ends where the longer of the two ends
+        // global keys -> the K / V^T operand, which holds frames [0, a) ++ [b, c) (a = win_buf_head, b - a = win_buf_gap; the launcher checked that it
+        // contains the block's key set, so each range lies in one piece): a start at or past frame b and an end past frame a move down by the gap, the
+        // sink [0, sink_end) stays. Sq == Skv with a == b == 0 (g3_self_attn_fwd_window_bf16) maps every key to itself.
+        const uint32_t buf_a = (uint32_t)p.win_buf_head * fl, buf_gap = (uint32_t)p.win_buf_gap * fl;
+        lo -= lo >= buf_a + buf_gap ? buf_gap : 0u;
+        hi -= hi > buf_a ? buf_gap : 0u;
         if (sink_end == 0u) {
             Kb += (int64_t)lo * p.k_row;
             Vb += lo;

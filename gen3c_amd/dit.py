@@ -216,6 +216,7 @@ class VideoExtendGeneralDIT(nn.Module):
         linear_precision: str = "bf16",
         mxfp8_producers: str = "separate",
         self_attn_window=None,
+        self_attn_window_cp: bool = False,
     ) -> None:
         super().__init__()
         # the GEN3C-Cosmos-7B configuration space (config/base/net.py:23-43 + cosmos-1-diffusion-gen3c.py:38-43);
@@ -257,8 +258,9 @@ class VideoExtendGeneralDIT(nn.Module):
         self.mxfp8_producers = "separate"
         self.set_mxfp8_producers(mxfp8_producers)
         self.self_attn_window = None
+        self.self_attn_window_cp = False
         if self_attn_window is not None:
-            self.set_self_attn_window(*self_attn_window)
+            self.set_self_attn_window(*self_attn_window, context_parallel=self_attn_window_cp)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
         D, Hd = model_channels, self.head_dim
@@ -367,14 +369,20 @@ class VideoExtendGeneralDIT(nn.Module):
             self._packed = None  # the quantised weights are part of the packed weight set
         self.linear_precision = precision
 
-    def set_self_attn_window(self, window_frames, sink_frames: int = 1) -> None:
+    def set_self_attn_window(self, window_frames, sink_frames: int = 1, context_parallel: bool = False) -> None:
         """None (default, the parity path): dense self-attention. window_frames W >= 0, sink_frames s >= 0: training-free local attention - the
         single-GPU self-attention of every block runs ops.self_attn_window with frame_len = Hp * Wp of the forward's own shape: each block of 256
         query tokens attends the latent frames within W of its own frames and the first s latent frames (in GEN3C the conditioning frames), exact
         softmax over those keys (ops.window_attn_mask is the function), and the kernel skips the key tiles outside. A window that covers every
         frame of the forward (W >= frames - 1 or s >= frames) runs the dense launch. Outside the bf16 parity statement: it changes the model's
         function, and its effect on picture quality with trained weights is unmeasured. The forward raises ValueError
-        where Hp * Wp is no multiple of 64 and under context parallelism."""
+        where Hp * Wp is no multiple of 64 and under context parallelism.
+        context_parallel=True (opt-in inside the opt-in): under context parallelism the forward does not raise but runs ContextParallelAttention's
+        "window_halo" schedule with frame_len = Hp * Wp and the GLOBAL frame count: every rank receives only the frames within W of its own and the
+        sink frames, and makes one ops.self_attn_window_cp launch per head group. Query blocks are counted from the rank's own first row, so where
+        a rank's first row is no multiple of 256 the blocks that straddle a frame boundary - and with them the function - depend on the number of
+        ranks. A window that covers every frame of the whole sequence runs the ordinary context-parallel schedule. No effect on a single GPU."""
+        self.self_attn_window_cp = bool(context_parallel) and window_frames is not None
         if window_frames is None:
             self.self_attn_window = None
             return
@@ -384,10 +392,22 @@ class VideoExtendGeneralDIT(nn.Module):
         self.self_attn_window = (W, s)
 
     def _self_attn_window_for(self, Tp: int, Hp: int, Wp: int):
-        """The (frame_len, W, s) of this forward's self-attention launches, or None for the dense launch."""
+        """The (frame_len, W, s) of this forward's single-GPU self-attention launches, or None for the dense launch. Under context parallelism with
+        the switch (Tp = this rank's frames): configures self._cp_attn for "window_halo", or back to its own schedule, and returns None."""
+        if self.self_attn_window is None or not self.self_attn_window_cp:
+            if getattr(self._cp_attn, "window", None) is not None:
+                self._cp_attn.configure(window=None)  # (a window set by an earlier forward)
         if self.self_attn_window is None:
             return None
         W, s = self.self_attn_window
+        if self._cp_attn is not None and self.self_attn_window_cp:
+            if (Hp * Wp) % 64 != 0:
+                raise ValueError(f"self_attn_window=({W}, {s}): {Hp} x {Wp} = {Hp * Wp} tokens per latent frame is not a multiple of 64, the kernel's key tile "
+                                 "(the product size is 44 x 80 = 3520 = 55 x 64)")
+            T_all = Tp * self.cp_size
+            covers = W >= T_all - 1 or s >= T_all  # every frame of the whole sequence: the rank's ordinary schedule
+            self._cp_attn.configure(window=None if covers else (Hp * Wp, W, s))
+            return None
         if self._cp_attn is not None:
             raise ValueError(f"self_attn_window=({W}, {s}) with context parallelism over {self.cp_size} ranks: the window form is single-GPU only. Windows under "
                              "key sharding would also cut the K / V exchange; that is later work")

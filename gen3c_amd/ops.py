@@ -526,6 +526,19 @@ def self_attn_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, S: int,
                       window=(int(frame_len), int(window_frames), int(sink_frames)))
 
 
+def self_attn_window_cp(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: int, Skv_buf: int, B: int, H: int, logit_bound: float, frame_len: int,
+                        total_frames: int, q_frame0: int, buf_head_frames: int, buf_tail_frame0: int, window_frames: int, sink_frames: int,
+                        out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+    """self_attn_window for one rank under key sharding (g3_self_attn_fwd_window_cp_bf16): q [Sq*B, H*128] are the rank's own rows, global frames
+    [q_frame0, q_frame0 + Sq / frame_len) of total_frames; k [Skv_buf*B, H*128] and plain vt [B, H, 128, ldvt] are a compact buffer of the global
+    frames [0, buf_head_frames) ++ [buf_tail_frame0, c) in ascending order (parallel.window_halo_plan makes the tight one). The function is
+    window_attn_mask(..., q_row0=q_frame0 * frame_len, T_total=total_frames): where q_frame0 * frame_len is a multiple of window_q_rows() the rows
+    equal self_attn_window on the whole sequence, bit for bit. The launcher refuses a buffer that misses a key some block attends; no fallback."""
+    return _attn_call("window_cp", q, k, vt, Sq, Skv_buf, B, H, out, softmax_scale, 11, False, logit_bound=logit_bound,
+                      window=(int(frame_len), int(window_frames), int(sink_frames)),
+                      window_cp=(int(total_frames), int(q_frame0), int(buf_head_frames), int(buf_tail_frame0)))
+
+
 def window_q_rows() -> int:
     """Query rows per block of the window form's key sets (the kernel's workgroup)."""
     return _lib.load().g3_self_attn_window_q_rows()
@@ -539,10 +552,37 @@ def window_attn_tiles(S: int, frame_len: int, window_frames: int, sink_frames: i
     return att.value, dense.value
 
 
-def window_attn_mask(S: int, frame_len: int, window_frames: int, sink_frames: int, q_rows: Optional[int] = None) -> torch.Tensor:
+def window_attn_tiles_cp(Sq: int, Skv_buf: int, frame_len: int, total_frames: int, q_frame0: int, buf_head_frames: int, buf_tail_frame0: int,
+                         window_frames: int, sink_frames: int):
+    """(attended, dense) of one rank's self_attn_window_cp launch: the (query block, 64-key tile) pairs it visits, and its query blocks times the
+    tiles of the whole sequence. Raises on everything the launch refuses."""
+    import ctypes
+    att, dense = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().g3_self_attn_window_cp_tiles(Sq, Skv_buf, frame_len, total_frames, q_frame0, buf_head_frames, buf_tail_frame0, window_frames,
+                                                        sink_frames, ctypes.byref(att), ctypes.byref(dense)), "g3_self_attn_window_cp_tiles")
+    return att.value, dense.value
+
+
+def window_attn_mask(S: int, frame_len: int, window_frames: int, sink_frames: int, q_rows: Optional[int] = None, q_row0: int = 0,
+                     T_total: Optional[int] = None) -> torch.Tensor:
     """CPU bool [S, S]: mask[i, j] = query row i attends key j under self_attn_window - the written-down definition of the function (gen3c_hip.h).
     With T = S / frame_len frames, the block of q_rows (default window_q_rows()) query rows that holds row i lies in frames f0..f1 and attends the
-    keys of frames [max(0, f0 - W), min(T, f1 + W + 1)) and of frames [0, min(s, T)): block-granular, a superset of row i's own window."""
+    keys of frames [max(0, f0 - W), min(T, f1 + W + 1)) and of frames [0, min(s, T)): block-granular, a superset of row i's own window.
+    With T_total (and q_row0, a multiple of frame_len): one rank's mask under key sharding, bool [S, T_total * frame_len] - the S query rows are the
+    global rows [q_row0, q_row0 + S), blocked from the rank's own row 0, over the keys of all T_total frames (self_attn_window_cp)."""
+    if T_total is not None or q_row0:
+        if T_total is None:
+            raise ValueError("window_attn_mask: q_row0 needs T_total")
+        if S <= 0 or frame_len <= 0 or S % frame_len or q_row0 < 0 or q_row0 % frame_len or q_row0 + S > T_total * frame_len or window_frames < 0 or sink_frames < 0:
+            raise ValueError(f"window_attn_mask: S {S} and q_row0 {q_row0} must be multiples of frame_len {frame_len} (S positive) within T_total {T_total} "
+                             f"frames, window_frames {window_frames} and sink_frames {sink_frames} >= 0")
+        q_rows = window_q_rows() if q_rows is None else q_rows
+        r0 = torch.arange(S) // q_rows * q_rows
+        f0 = (r0 + q_row0) // frame_len
+        f1 = (torch.clamp(r0 + q_rows, max=S) - 1 + q_row0) // frame_len
+        kf = torch.arange(T_total * frame_len) // frame_len
+        lo, hi = torch.clamp(f0 - window_frames, min=0), torch.clamp(f1 + window_frames + 1, max=T_total)
+        return ((kf[None, :] >= lo[:, None]) & (kf[None, :] < hi[:, None])) | (kf[None, :] < min(sink_frames, T_total))
     if S <= 0 or frame_len <= 0 or S % frame_len or window_frames < 0 or sink_frames < 0:
         raise ValueError(f"window_attn_mask: S {S} must be a positive multiple of frame_len {frame_len}, window_frames {window_frames} and sink_frames {sink_frames} >= 0")
     q_rows = window_q_rows() if q_rows is None else q_rows
@@ -572,13 +612,16 @@ _ATTN_ENTRIES = {
     # (no value of enum g3_attn_entry: its dry run is g3_attn_window_plan_bf16, which takes exactly the call's arguments)
     "window": (None, "g3_self_attn_fwd_window_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] +
                ("logit_bound", "frame_len", "window_frames", "sink_frames")),
+    # (likewise: g3_attn_window_cp_plan_bf16)
+    "window_cp": (None, "g3_self_attn_fwd_window_cp_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head") + _ASHAPE +
+                  ("logit_bound", "frame_len", "total_frames", "q_frame0", "buf_head_frames", "buf_tail_frame0", "window_frames", "sink_frames")),
 }
 _ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] + ("logit_bound", "variant"))
 
 
 def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
-               logit_bound=0.0, window=None):
-    """The one marshaller of flash_attn, self_attn_bounded and self_attn_window, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
+               logit_bound=0.0, window=None, window_cp=None):
+    """The one marshaller of flash_attn, self_attn_bounded, self_attn_window and self_attn_window_cp, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
     launch and the kernel timer."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
     skv_all = Skv + skip_len  # keys the operands hold
@@ -616,8 +659,10 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
              lse=_dev(lse, "lse", torch.float32) if partial else 0, o_row=ldo * B, o_batch=ldo, o_head=128, Sq=Sq, Skv=Skv, kv_dense=kv_dense, B=B, H=H,
              head_dim=128, softmax_scale=float(1.0 / math.sqrt(128) if softmax_scale is None else softmax_scale), logit_bound=float(logit_bound), variant=int(variant))
     if window is not None:
-        assert vt.dim() == 4 and Sq == Skv, "the window form takes plain V^T and Sq == Skv"
+        assert vt.dim() == 4 and (Sq == Skv or window_cp is not None), "the window form takes plain V^T and Sq == Skv"
         a.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2])
+    if window_cp is not None:
+        a.update(total_frames=window_cp[0], q_frame0=window_cp[1], buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3])
     entry_id, symbol, names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
     timer = None
@@ -637,6 +682,11 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
             attended, dense = window_attn_tiles(Sq, *window)
             meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], tile_density=attended / dense)
             meta["kernel"] = lib.g3_attn_window_plan_bf16(*[a[n] for n in names]).decode()
+        elif entry == "window_cp":
+            attended, dense = window_attn_tiles_cp(Sq, Skv, window[0], *window_cp, window[1], window[2])
+            meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], total_frames=window_cp[0], q_frame0=window_cp[1],
+                        buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3], tile_density=attended / dense)
+            meta["kernel"] = lib.g3_attn_window_cp_plan_bf16(*[a[n] for n in names]).decode()
         else:
             plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
             meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()

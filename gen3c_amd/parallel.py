@@ -242,7 +242,41 @@ def cfg_exchange(out_local: torch.Tensor, cfg_group):
 # context-parallel self-attention
 # ------------------------------------------------------------------------------------------------------------------
 ATTN_KERNELS = {"auto": None, "w4b": 11, "wave8": 4}  # per-call kernel choice of g3_flash_attn_fwd_ex_bf16 ("auto": the even-fill rule below)
-CP_SCHEDULES = ("gather_first", "local_first", "local_carry", "head_parallel")
+CP_SCHEDULES = ("gather_first", "local_first", "local_carry", "head_parallel", "window_halo")
+
+
+def window_halo_plan(T: int, world: int, W: int, s: int) -> dict:
+    """The exchange of the frame-window self-attention under key sharding (schedule "window_halo"): T latent frames sharded contiguously, fpr = T / world
+    per rank, window W frames either side, the first s frames attended by everyone. Rank r owns frames [r fpr, (r + 1) fpr); its query blocks lie
+    inside them, so together they attend the frames [max(0, r fpr - W), min(T, (r + 1) fpr + W)) and [0, min(s, T)) - whatever the frame length.
+    Returns dict(fpr=..., buffers=[(a, b, c) per rank], sends={(p, r): [(f0, f1), ...]}, remote_frames=[per rank]):
+      buffers[r]     the rank's compact K / V buffer holds the global frames [0, a) ++ [b, c) in ascending order, and no others (a sink that reaches
+                     the window: a == b == 0, the one range [0, c))
+      sends[(p, r)]  the whole-frame pieces [f0, f1) of rank p's shard that rank r's buffer holds, ascending (at most one per buffer piece; p == r: the
+                     rank's own frames). Sender-major they are rank r's buffer: ranks own ascending frames.
+      remote_frames  frames rank r receives from others = what the exchange moves
+    Every number is derived from the four arguments."""
+    T, world, W, s = int(T), int(world), int(W), int(s)
+    if T <= 0 or world <= 0 or T % world or W < 0 or s < 0:
+        raise ValueError(f"window_halo_plan: T {T} must be a positive multiple of world {world}, W {W} and s {s} >= 0")
+    fpr = T // world
+    sink = min(s, T)
+    buffers, sends, remote = [], {}, []
+    for r in range(world):
+        lo, hi = max(0, r * fpr - W), min(T, (r + 1) * fpr + W)
+        buffers.append((0, 0, max(hi, sink)) if sink >= lo else (sink, lo, hi))
+        a, b, c = buffers[r]
+        n = 0
+        for p in range(world):
+            p0, p1 = p * fpr, (p + 1) * fpr
+            pieces = [(max(x0, p0), min(x1, p1)) for x0, x1 in ((0, a), (b, c)) if max(x0, p0) < min(x1, p1)]
+            if len(pieces) == 2 and pieces[0][1] == pieces[1][0]:  # (a == b inside p's shard)
+                pieces = [(pieces[0][0], pieces[1][1])]
+            sends[(p, r)] = pieces
+            if p != r:
+                n += sum(f1 - f0 for f0, f1 in pieces)
+        remote.append(n)
+    return dict(fpr=fpr, buffers=buffers, sends=sends, remote_frames=remote)
 
 
 def _default_backend():
@@ -262,6 +296,10 @@ def _default_backend():
         # the key-sharded forms with a logit bound (g3_self_attn_fwd_bounded_cp_bf16): what "attention", "attention_partial" and "attention_carry" take
         attention_bounded_cp=lambda q, k, vt, Sq, Skv, B, H, logit_bound, out=None, carry=None, kv_skip=None, partial=False, variant=0: ops.self_attn_bounded(
             q, k, vt, Sq, Skv, B, H, logit_bound, out=out, variant=variant, partial=partial, carry=carry, kv_skip=kv_skip),
+        # the frame window over a compact halo buffer (g3_self_attn_fwd_window_cp_bf16): schedule "window_halo". `window`: frame_len, total_frames,
+        # q_frame0, buf_head_frames, buf_tail_frame0, window_frames, sink_frames
+        attention_window_cp=lambda q, k, vt, Sq, Skv_buf, B, H, logit_bound, out, *window: ops.self_attn_window_cp(
+            q, k, vt, Sq, Skv_buf, B, H, logit_bound, *window, out=out),
         timer=ops.HipTimer,
     )
 
@@ -300,6 +338,12 @@ class ContextParallelAttention:
     g3_cp_gather_heads_bf16 writes it into the group's columns. No partials, no merge, a quarter of the exchanged bytes at cp = 8; the first group's
     exchange and the last group's return hide behind nothing. Needs H % world == 0 and a backend with "scatter_heads", "gather_heads" and
     "attention_bounded"; otherwise it runs as "local_first" (and `effective` says so). Runs at world 1 too (a self-exchange).
+    schedule "window_halo" (opt-in, with configure(window=(frame_len, W, s)); the frame-window self-attention, a different FUNCTION: DESIGN.md section
+    11): a rank needs only the frames within W of its own and the first s. Per head group the K rows and the V rows of exactly those frames travel by
+    one all-to-all with split sizes each (window_halo_plan; a rank's own frames are its split to itself), so the receive buffer IS the compact buffer
+    in global ascending order. finish(): wait, transpose the compact V, one g3_self_attn_fwd_window_cp_bf16 launch per group straight into its output
+    columns. No partials, no merge, no carry; only the first group's exchange is exposed. Needs S_local a multiple of frame_len and a backend with
+    "attention_window_cp"; anything else raises (no other schedule computes this function). Runs at world 1 too.
 
     bounded (opt-in, default off): with a caller's `logit_bound` > 0 the three key-sharding schedules run every attention launch through the backend's
     "attention_bounded_cp" - the no-running-max forms of the one-wave-per-SIMD kernel, g3_self_attn_fwd_bounded_cp_bf16 - where the layer's kernel is
@@ -325,6 +369,8 @@ class ContextParallelAttention:
         self.schedule = schedule
         self.kernel = kernel
         self.bounded = bool(bounded)
+        self.window = None  # (frame_len, W, s) of schedule "window_halo"
+        self._schedule_without_window = "gather_first" if schedule == "window_halo" else schedule
         # head_parallel only (its launches see all keys of their heads at once, as the single-GPU call): ask "attention_bounded" for the 16x16x32 tile
         # loop (ops.self_attn_bounded(mfma16=True)). The DiT sets it from dit._SELF_ATTN_MFMA16; the backend is passed the keyword only when it is on.
         self.mfma16 = False
@@ -333,12 +379,26 @@ class ContextParallelAttention:
         self.effective_bounded = False  # set by finish(): the key-sharding schedules' launches went through "attention_bounded_cp" (see `bounded`)
         self.bytes_gathered = 0  # received from the other ranks since construction / the last reset (bench.py's "cp" object)
 
-    def configure(self, head_groups: Optional[int] = None, schedule: Optional[str] = None, kernel: Optional[str] = None, bounded: Optional[bool] = None):
+    def configure(self, head_groups: Optional[int] = None, schedule: Optional[str] = None, kernel: Optional[str] = None, bounded: Optional[bool] = None,
+                  window=False):
+        """window=(frame_len, W, s): select schedule "window_halo" with these numbers; window=None: back to the schedule configured before it."""
         if head_groups is not None:
             self.head_groups = int(head_groups)
         if schedule is not None:
             assert schedule in CP_SCHEDULES
             self.schedule = schedule
+            if schedule != "window_halo":
+                self._schedule_without_window = schedule
+        if window is None:
+            self.window = None
+            if self.schedule == "window_halo":
+                self.schedule = self._schedule_without_window
+        elif window is not False:
+            fl, W, s = (int(x) for x in window)
+            if fl <= 0 or W < 0 or s < 0:
+                raise ValueError(f"window_halo: frame_len {fl} must be positive, window frames {W} and sink frames {s} >= 0")
+            self.window = (fl, W, s)
+            self.schedule = "window_halo"
         if kernel is not None:
             assert kernel in ATTN_KERNELS
             self.kernel = kernel
@@ -355,6 +415,8 @@ class ContextParallelAttention:
         latent frames; otherwise V is gathered row-major and transposed after the exchange).
         "head_parallel" sends q together with k and v, so nothing goes out here: k and v are kept for finish()."""
         be = self.backend or _default_backend()
+        if self.schedule == "window_halo":
+            return self._start_window_halo(be, k, v, S_local, B, H)
         if self.schedule == "head_parallel" and H % self.world == 0 and all(n in be for n in ("scatter_heads", "gather_heads", "attention_bounded")):
             # nothing can go out before q exists: one scatter launch fills the q, k and v send buffers of a head group (finish())
             return dict(head_parallel=True, k=k, v=v, S_local=S_local, B=B, H=H, rows=S_local * B, be=be)
@@ -405,14 +467,83 @@ class ContextParallelAttention:
             tm.stop()
             self.stats.append(("wait", g, tm))
 
-    def _all_to_all(self, recv: torch.Tensor, send: torch.Tensor):
-        """Async single-tensor all-to-all of equal chunks (send / recv: contiguous [world, ...]) -> a Work. Device tensors on a gloo group (tests
-        and tools/cp_check.py with several ranks on one GPU; the product path is RCCL) are staged through host memory: only the single-tensor
-        all-to-all on CPU tensors is relied on with gloo."""
+    def _all_to_all(self, recv: torch.Tensor, send: torch.Tensor, recv_splits=None, send_splits=None):
+        """Async single-tensor all-to-all of equal chunks (send / recv: contiguous [world, ...]) or, with split sizes, of per-rank row counts along
+        dim 0 -> a Work. Device tensors on a gloo group (tests and tools/cp_check.py with several ranks on one GPU; the product path is RCCL) are
+        staged through host memory: only the single-tensor all-to-all on CPU tensors is relied on with gloo."""
+        splits = {} if recv_splits is None else dict(output_split_sizes=recv_splits, input_split_sizes=send_splits)
         if send.is_cuda and dist.get_backend(self.group) == "gloo":
             host = torch.empty(recv.shape, dtype=recv.dtype)
-            return _HostStagedWork(dist.all_to_all_single(host, send.cpu(), group=self.group, async_op=True), host, recv)
-        return dist.all_to_all_single(recv, send, group=self.group, async_op=True)
+            return _HostStagedWork(dist.all_to_all_single(host, send.cpu(), group=self.group, async_op=True, **splits), host, recv)
+        return dist.all_to_all_single(recv, send, group=self.group, async_op=True, **splits)
+
+    def _start_window_halo(self, be, k: torch.Tensor, v: torch.Tensor, S_local: int, B: int, H: int):
+        if self.window is None:
+            raise ValueError('schedule "window_halo" needs configure(window=(frame_len, W, s))')
+        if "attention_window_cp" not in be:
+            raise ValueError('schedule "window_halo": the backend has no "attention_window_cp", and no other schedule computes the window function')
+        fl, Wf, sf = self.window
+        if S_local % fl:
+            raise ValueError(f"window_halo: S_local {S_local} is not a multiple of frame_len {fl} (a rank owns whole latent frames)")
+        P, r = self.world, self.rank
+        fpr = S_local // fl
+        plan = window_halo_plan(fpr * P, P, Wf, sf)
+        a, b, c = plan["buffers"][r]
+        rpf = fl * B  # rows of a frame: contiguous in the (s, b) row order
+        frames = lambda pieces: sum(f1 - f0 for f0, f1 in pieces)
+        send_splits = [frames(plan["sends"][(r, d)]) * rpf for d in range(P)]
+        recv_splits = [frames(plan["sends"][(p, r)]) * rpf for p in range(P)]
+        assert sum(recv_splits) == (a + c - b) * rpf
+        # destination-major row slices of this rank's shard (frame f = local rows [(f - r fpr) rpf, (f + 1 - r fpr) rpf))
+        slices = [slice((f0 - r * fpr) * rpf, (f1 - r * fpr) * rpf) for d in range(P) for f0, f1 in plan["sends"][(r, d)]]
+        G = self.head_groups
+        while H % G != 0:
+            G -= 1
+        Hg = H // G
+        W = Hg * 128
+        works = []
+        for g in range(G):
+            bufs = []
+            for t in (k, v):
+                send = torch.cat([t[sl, g * W:(g + 1) * W] for sl in slices], 0)  # the one pack pass: K / V rows by destination
+                recv = torch.empty((sum(recv_splits), W), dtype=t.dtype, device=t.device)
+                bufs.append((self._all_to_all(recv, send, recv_splits, send_splits), recv, send))
+            self.bytes_gathered += 2 * plan["remote_frames"][r] * rpf * W * k.element_size()
+            works.append(bufs)
+        return dict(window_halo=True, works=works, S_local=S_local, B=B, H=H, Hg=Hg, W=W, rows=S_local * B, be=be, frame_len=fl, window=(Wf, sf),
+                    total_frames=fpr * P, q_frame0=r * fpr, buffer=(a, b, c), Skv_buf=(a + c - b) * fl)
+
+    def _finish_window_halo(self, q: torch.Tensor, pending: dict, logit_bound: float) -> torch.Tensor:
+        be, W, Hg, B, S_local, works = (pending[n] for n in ("be", "W", "Hg", "B", "S_local", "works"))
+        (a, b, _c), Skv_buf, (Wf, sf) = pending["buffer"], pending["Skv_buf"], pending["window"]
+        self.effective = dict(schedule="window_halo", kernel="w4b", head_groups=len(works))
+        out = torch.empty((pending["rows"], pending["H"] * 128), dtype=q.dtype, device=q.device)
+        two_streams = q.is_cuda and len(works) >= 2
+        main = side = q_ready = None
+        if two_streams:
+            main = torch.cuda.current_stream(q.device)
+            side = self._side_stream(q.device)
+            q_ready = main.record_event()  # q (and `out`) were produced / allocated on the main stream
+        # Lifetime contract (as in finish()): the send and receive buffers stay referenced by `pending` until every launch below is enqueued; `keep`
+        # does the same for the transposed V^T buffers, which only kernels launched through ctypes read.
+        keep = []
+        try:
+            for g, ((wk, kr, _ks), (wv, vr, _vs)) in enumerate(works):
+                st = main if (not two_streams or g % 2 == 0) else side
+                with (torch.cuda.stream(st) if two_streams else _NullCtx()):
+                    if two_streams and st is side:
+                        st.wait_event(q_ready)
+                    self._wait(be, g, wv)
+                    vt = be["transpose_v"](vr, Skv_buf, B, Hg)  # plain V^T of the compact buffer
+                    keep.append(vt)
+                    self._wait(be, g, wk)
+                    be["attention_window_cp"](q[:, g * W:(g + 1) * W], kr, vt, S_local, Skv_buf, B, Hg, logit_bound, out[:, g * W:(g + 1) * W],
+                                              pending["frame_len"], pending["total_frames"], pending["q_frame0"], a, b, Wf, sf)
+        finally:
+            if two_streams:
+                main.wait_stream(side)
+        del keep
+        return out
 
     def _finish_head_parallel(self, q: torch.Tensor, pending: dict, logit_bound: float) -> torch.Tensor:
         be, B, S_local, H, rows, k, v = (pending[n] for n in ("be", "B", "S_local", "H", "rows", "k", "v"))
@@ -489,6 +620,8 @@ class ContextParallelAttention:
         self.effective_bounded = False
         if pending.get("head_parallel"):
             return self._finish_head_parallel(q, pending, logit_bound)
+        if pending.get("window_halo"):
+            return self._finish_window_halo(q, pending, logit_bound)
         be, W, Hg, B, S_local = pending["be"], pending["W"], pending["Hg"], pending["B"], pending["S_local"]
         S_all = S_local * self.world
         out = torch.empty((pending["rows"], pending["H"] * 128), dtype=q.dtype, device=q.device)

@@ -298,6 +298,36 @@ const char* g3_attn_window_plan_bf16(const void* q, int64_t q_row, int64_t q_bat
 int g3_self_attn_window_q_rows(void);
 int g3_self_attn_window_tiles(int S, int frame_len, int window_frames, int sink_frames, int64_t* attended, int64_t* dense);
 
+/* The frame window under KEY SHARDING (context parallelism; opt-in inside the opt-in): the same two kernels, one launch per rank. Parameters beyond
+ * g3_self_attn_fwd_window_bf16's:
+ *   Sq               this rank's query rows, whole frames: frames [q_frame0, q_frame0 + Sq / frame_len) of the sequence's total_frames
+ *   Skv_buf          keys in the COMPACT K / V^T operand, which holds the global frames [0, a) ++ [b, c) in ascending order,
+ *                    a = buf_head_frames <= b = buf_tail_frame0, c = Skv_buf / frame_len - a + b (a == b: the one range [0, c)); V^T is plain
+ * Query block blk holds the rank's rows [256 blk, min(256 blk + 256, Sq)), global frames f0..f1, and attends the frames [max(0, f0 - W),
+ * min(total_frames, f1 + W + 1)) and [0, min(s, total_frames)) exactly as above; the prologue computes that key set in global coordinates and maps
+ * it into the buffer (a key at or past frame b moves down by b - a frames). Where the rank's first row is a multiple of 256 in the whole sequence,
+ * the blocks are the single-GPU blocks and the output is g3_self_attn_fwd_window_bf16's, bit for bit. Otherwise the blocks that straddle a frame
+ * boundary are different blocks, so for those rows (about one block in 14 at 3 520 tokens per frame) the function depends on the number of ranks.
+ * Always the window kernels, also when the window covers everything. Keys in the buffer that no block attends are allowed; the kernel skips them.
+ * G3_ERR_ARG, with nothing launched and one message each: everything g3_self_attn_fwd_window_bf16 refuses (with Skv_buf in the place of S for the V^T
+ * leading dimension and the 32-bit offsets); Sq no multiple of frame_len; total_frames <= 0 or q_frame0 < 0; not 0 <= a <= b;
+ * q_frame0 + Sq / frame_len > total_frames; Skv_buf not (a + c - b) * frame_len for a c in [b, total_frames]; a buffer that does not hold the key
+ * set of some query block (the host walks the blocks: this is what keeps a wrong exchange plan from becoming a read outside the operand).
+ * g3_attn_window_cp_plan_bf16: the dry run, as g3_attn_window_plan_bf16. g3_self_attn_window_cp_tiles: the (query block, 64-key tile) pairs this
+ * rank's launch visits, and its query blocks times the tiles of the whole sequence; the same refusals. */
+int g3_self_attn_fwd_window_cp_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                    int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                    int64_t o_batch, int64_t o_head, int Sq, int Skv_buf, int B, int H, int head_dim, float softmax_scale,
+                                    float logit_bound, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0,
+                                    int window_frames, int sink_frames, void* stream);
+const char* g3_attn_window_cp_plan_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                        int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                        int64_t o_batch, int64_t o_head, int Sq, int Skv_buf, int B, int H, int head_dim, float softmax_scale,
+                                        float logit_bound, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0,
+                                        int window_frames, int sink_frames);
+int g3_self_attn_window_cp_tiles(int Sq, int Skv_buf, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0,
+                                 int window_frames, int sink_frames, int64_t* attended, int64_t* dense);
+
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);

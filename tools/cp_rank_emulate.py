@@ -20,6 +20,12 @@ the network output is a device copy of the real size on the stand-in's stream. T
 L * 2 * (S_local * B * 4096 * 2) * (cp - 1); the exchange model counts cp - 1 peers and B = 1 for the CFG-parallel arms.
 
   python tools/cp_rank_emulate.py --ab_bounded 3 [--cps 1,2,4,8] [--steps 2] [--configs "4,auto,local_first;4,auto,gather_first;4,auto,local_carry"] [--out ...]
+  python tools/cp_rank_emulate.py --window 2,1 [--cps 8,4] [--rounds 2] [--steps 2] [--configs "4,auto,local_first"] [--out FILE]
+The frame window under context parallelism (the DiT's opt-in switch; ContextParallelAttention's "window_halo") against the dense schedule, ALTERNATING in
+one process: rank 0, a middle rank and the last rank of each cp through the product path. Prints per rank the step ms of both arms, the self-attention
+ms per layer, the visited and dense (query block, tile) pairs and the received bytes (asserted against parallel.window_halo_plan); the step is paced by
+the slowest rank, so the maximum over the ranks is the line to read. The stand-in's split-size all-to-all is a device copy of the received size.
+
 The logit-bound switch of the key-sharding schedules (ContextParallelAttention's `bounded`) off and on, ALTERNATING in one process after both arms are warm:
 per configuration `--ab_bounded` rounds of (off, on), each `--steps` untimed-by-events steps; then one step per arm with the kernel timers on for the per-class
 table. The off arm is the behaviour without the switch. Then, launch by launch on one stream, the partial / carry / kvseg launches at each cp's rank shapes
@@ -102,14 +108,25 @@ class FakeRank:
         return w
 
 
-    def _all_to_all(self, out, inp, group=None, async_op=False):
-        """A device copy of the same size on the stand-in's stream: 1 / world of it stays on the rank, the rest is what a real exchange would deliver."""
+    def _all_to_all(self, out, inp, output_split_sizes=None, input_split_sizes=None, group=None, async_op=False):
+        """A device copy of the same size on the stand-in's stream: 1 / world of it stays on the rank, the rest is what a real exchange would deliver.
+        With split sizes (the window_halo exchange: rows along dim 0) the receive buffer is filled from the send buffer piece by piece, and what the
+        other ranks' splits hold is counted."""
         cur = torch.cuda.current_stream()
         self.comm.wait_stream(cur)
         with torch.cuda.stream(self.comm):
-            out.copy_(inp)
+            if output_split_sizes is None:
+                out.copy_(inp)
+            else:
+                assert sum(output_split_sizes) == out.shape[0] and sum(input_split_sizes) == inp.shape[0] and output_split_sizes[self.rank] == input_split_sizes[self.rank]
+                for off in range(0, out.shape[0], inp.shape[0]):
+                    n = min(inp.shape[0], out.shape[0] - off)
+                    out[off:off + n].copy_(inp[:n])
             ev = self.comm.record_event()
-        self.bytes += (self.world - 1) * (inp.numel() // self.world) * inp.element_size()
+        if output_split_sizes is None:
+            self.bytes += (self.world - 1) * (inp.numel() // self.world) * inp.element_size()
+        else:
+            self.bytes += (out.shape[0] - output_split_sizes[self.rank]) * (out.numel() // out.shape[0]) * out.element_size()
         w = _Work(ev)
         if not async_op:
             w.wait()
@@ -514,8 +531,100 @@ def main_cfg(args, dev, configs, net):
     out.with_suffix(".txt").write_text(text + "\n")
 
 
+def run_window(cp, rank, window, config, steps, rounds, blocks, dev, net):
+    """Rank `rank` of `cp` two ways, alternating in one process after both arms are warm: the dense context-parallel schedule `config`, and the frame
+    window (W, s) under context parallelism - the "window_halo" schedule through the product path (the DiT's switch). Per arm `rounds` rounds of one
+    untimed step after the switch and `steps` timed ones; then one step per arm with the kernel timers on for the self-attention launches. The bytes the
+    halo arm receives per step are asserted against parallel.window_halo_plan."""
+    from gen3c_amd.parallel import split_inputs_cp, window_halo_plan
+    den, xt_full, cond, uncond = _step_inputs(net, dev)
+    lib = _lib.load()
+    W, s = window
+    G, kern, sched = config
+    T, fl, S_all = 16, 3520, 56320
+    plan = window_halo_plan(T, cp, W, s)
+    a, b, c = plan["buffers"][rank]
+    tiles = ops.window_attn_tiles_cp(S_all // cp, (a + c - b) * fl, fl, T, rank * (T // cp), a, b, W, s)
+    arms = {"dense": dict(ms=[]), "halo": dict(ms=[])}
+    with FakeRank(cp, rank, dev) as fr:
+        try:
+            net.enable_context_parallel(CP_GROUP)
+            net._cp_attn.configure(head_groups=G, kernel=kern, schedule=sched)
+            xt0 = split_inputs_cp(xt_full, 2, net.cp_group)
+            for rnd in range(rounds + 1):
+                for name, arm in arms.items():
+                    net.set_self_attn_window(*((W, s) if name == "halo" else (None,)), context_parallel=name == "halo")
+                    den.denoise_step(xt0, 0, cond, uncond, 1.0, 0.001, 1)  # warm-up after the switch
+                    torch.cuda.synchronize()
+                    fr.bytes = 0
+                    if rnd < rounds:
+                        arm["ms"].append(round(_steps_ms(den, xt0, cond, uncond, steps), 2))
+                        n = steps
+                    else:  # event pairs around every launch: not part of the timing above
+                        ops.enable_kernel_timers(True)
+                        den.denoise_step(xt0, 1, cond, uncond, 1.0, 0.001, 1)
+                        torch.cuda.synchronize()
+                        table = _class_table(ops.collected_kernel_timers(), 1, lib)
+                        ops.enable_kernel_timers(False)
+                        sa = [k for k in table if k["kind"] == "attn" and k["Skv"] > 2048]
+                        arm["self_attention_ms_per_layer"] = round(sum(k["ms_per_step"] for k in sa) / blocks, 3)  # (launches on two streams overlap: summed)
+                        arm["self_attention_kernels"] = sorted({k["kernel"] for k in sa})
+                        n = 1
+                    arm["effective"] = dict(net._cp_attn.effective)
+                    arm["received_bytes_per_step"] = fr.bytes // n
+            want = blocks * 2 * plan["remote_frames"][rank] * fl * 2 * 4096 * 2  # K and V rows of the remote frames, B = 2, bf16
+            assert arms["halo"]["effective"]["schedule"] == "window_halo" and arms["halo"]["received_bytes_per_step"] == want, (arms["halo"], want)
+        finally:
+            net.set_self_attn_window(None)
+            net.disable_context_parallel()
+    for arm in arms.values():
+        arm["ms_per_step"] = round(sum(arm["ms"]) / len(arm["ms"]), 2)
+        arm["spread_pct"] = round((max(arm["ms"]) - min(arm["ms"])) / arm["ms_per_step"] * 100, 2)
+    rec = dict(cp=cp, rank=rank, window=[W, s], buffer=[a, b, c], dense_config=dict(head_groups=G, kernel=kern, schedule=sched), steps=steps, rounds=rounds,
+               visited_tiles=tiles[0], dense_tiles=tiles[1], dense=arms["dense"], halo=arms["halo"],
+               halo_over_dense=round(arms["halo"]["ms_per_step"] / arms["dense"]["ms_per_step"], 4))
+    print(f"cp={cp} rank={rank} window={window} buffer={(a, b, c)}: dense {arms['dense']['ms']} halo {arms['halo']['ms']} ms/step -> halo / dense {rec['halo_over_dense']}; "
+          f"tiles {tiles[0]}/{tiles[1]}; received {arms['halo']['received_bytes_per_step'] / 1e9:.2f} against {arms['dense']['received_bytes_per_step'] / 1e9:.2f} GB/step", flush=True)
+    return rec
+
+
+def main_window(args, dev, configs, net):
+    """--window W,S: rank 0, a middle rank and the last rank of cp = 8 and cp = 4 (or --cps), dense context parallelism against the window_halo arm
+    (run_window). A step is paced by its slowest rank - interior ranks visit more tiles than rank 0 - so the maximum over the ranks is reported."""
+    W, s = (int(x) for x in args.window.split(","))
+    runs = []
+    for cp in [int(c) for c in args.cps.split(",")]:
+        if cp > 1:
+            for rank in sorted({0, cp // 2, cp - 1}):
+                runs.append(run_window(cp, rank, (W, s), configs[0], args.steps, args.rounds, args.blocks, dev, net))
+    lines = [f"one MI355X as one rank, {args.blocks} blocks, B = 2, {args.rounds} alternating rounds x {args.steps} steps; window W = {W}, sink s = {s}; compute only - the "
+             "exchange is a device copy of the received size. Self-attention ms are summed durations of launches that overlap on two streams.", "",
+             f"{'cp':>3} {'rank':>4} {'buffer (a, b, c)':<17} {'dense arm':<22} {'dense ms/step (rounds)':<26} {'halo ms/step (rounds)':<26} {'halo/dense':>10} "
+             f"{'spread d / h %':>15} {'self-attn ms/layer d -> h':>26} {'tiles visited / dense':>22} {'received GB/step d -> h':>24}"]
+    for r in runs:
+        c = r["dense_config"]
+        lines.append(f"{r['cp']:>3} {r['rank']:>4} {str(tuple(r['buffer'])):<17} {'%d,%s,%s' % (c['head_groups'], c['kernel'], c['schedule']):<22} {str(r['dense']['ms']):<26} "
+                     f"{str(r['halo']['ms']):<26} {r['halo_over_dense']:>10.4f} {'%.2f / %.2f' % (r['dense']['spread_pct'], r['halo']['spread_pct']):>15} "
+                     f"{'%.3f -> %.3f' % (r['dense']['self_attention_ms_per_layer'], r['halo']['self_attention_ms_per_layer']):>26} "
+                     f"{'%d / %d' % (r['visited_tiles'], r['dense_tiles']):>22} "
+                     f"{'%.2f -> %.2f' % (r['dense']['received_bytes_per_step'] / 1e9, r['halo']['received_bytes_per_step'] / 1e9):>24}")
+    lines.append("")
+    for cp in sorted({r["cp"] for r in runs}):
+        rs = [r for r in runs if r["cp"] == cp]
+        d, h = max(r["dense"]["ms_per_step"] for r in rs), max(r["halo"]["ms_per_step"] for r in rs)
+        lines.append(f"cp={cp}: slowest emulated rank, dense {d:.1f} ms/step, halo {h:.1f} ms/step -> {h / d:.4f} (compute only)")
+    text = "\n".join(lines)
+    print(text)
+    out = Path(args.out)
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(dict(runs=runs, summary_text=text), indent=1))
+    out.with_suffix(".txt").write_text(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--window", default=None, metavar="W,S", help="the frame window under context parallelism (window_halo) against the dense schedule of the first "
+                    "--configs entry, arms alternating: rank 0, a middle rank and the last rank of every --cps entry (default 8,4); --rounds, --steps as for --cfg 2")
     ap.add_argument("--cfg", type=int, choices=(1, 2), default=1, help="2: CFG-parallel (2 guidance branches x cp) against plain context parallelism at the same total "
                     "rank count, arms alternating (run_cfg_ab); 1: the arms below, unchanged")
     ap.add_argument("--worlds", default="8,4,2", help="with --cfg 2: total rank counts")
@@ -535,12 +644,21 @@ def main():
             args.configs = "4,auto,local_first;4,auto,local_carry"
         if args.out == ap.get_default("out"):
             args.out = str(Path(args.out).with_name("cfg_parallel_rank_shapes.json"))
+    if args.window is not None:  # its own defaults: the DiT's shipped schedule as the dense arm, cp = 8 and 4, and a record of its own
+        if args.configs == ap.get_default("configs"):
+            args.configs = "4,auto,local_first"
+        if args.cps == ap.get_default("cps"):
+            args.cps = "8,4"
+        if args.out == ap.get_default("out"):
+            args.out = str(Path(args.out).with_name("attn_window_cp_emulated.json"))
     torch.set_grad_enabled(False)
     dev = torch.device("cuda:0")
     configs = [(int(c.split(",")[0]), c.split(",")[1], c.split(",")[2]) for c in args.configs.split(";")]
     net = VideoExtendGeneralDIT(in_channels=16 + 16 * 4 + 1, rope_t_extrapolation_ratio=2.0, num_blocks=args.blocks, device=dev, init_weights=False)
     net.initialize_weights(randomize_adaln=True, seed=1234)
     net.cross_attention_skip_zero_context = False  # the dense workload bench.py times (the record profiles/r6_cp_rank_shapes.* was taken with the product default, ~17 / cp ms less per step)
+    if args.window is not None:
+        return main_window(args, dev, configs, net)
     if args.ab_bounded > 0:
         return main_ab(args, dev, configs, net)
     if args.cfg == 2:
