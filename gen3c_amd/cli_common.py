@@ -54,6 +54,11 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="with an even --num_gpus: the conditional and the unconditional branch of every denoise step run on separate rank groups of "
                         "num_gpus / 2 context-parallel ranks each and exchange only the network output (opt-in, default off; same output bit for "
                         "bit; same as G3_CFG_PARALLEL=1)")
+    p.add_argument("--sampler_solver", choices=("euler", "2ab"), default="euler",
+                   help="solver of the denoise loop: euler (default, the reference's EDM-Euler loop, the parity path) or 2ab (opt-in second-order "
+                        "multistep solver that reuses the previous step's x0 prediction, no extra network call: less solver error from about 18 "
+                        "steps up, worse below; outside the parity statement, picture quality with trained weights unmeasured: DESIGN.md section "
+                        "12; same as G3_SAMPLER_SOLVER=2ab)")
     p.add_argument("--dit_precision", choices=("bf16", "mxfp8", "mxfp6"), default="bf16",
                    help="precision of the DiT's six per-block linears: bf16 (default, the parity path), mxfp8 (opt-in MXFP8 matrix cores) or mxfp6 "
                         "(opt-in MXFP6 e2m3 operands on the same matrix cores at twice the rate); both outside the parity statement, DESIGN.md "
@@ -110,6 +115,24 @@ def resolve_parallel_layout(num_gpus: int, cfg_parallel: bool, latent_frames: in
 def cfg_parallel_requested(args) -> bool:
     """--cfg_parallel, or G3_CFG_PARALLEL=1 in the environment (opt-in, default off)."""
     return bool(getattr(args, "cfg_parallel", False)) or os.environ.get("G3_CFG_PARALLEL", "0").strip() not in ("", "0")
+
+
+def sampler_solver_requested(args) -> str:
+    """--sampler_solver, or G3_SAMPLER_SOLVER in the environment when the flag is left at its default (opt-in, default "euler")."""
+    from .sampler import check_solver
+    flag = getattr(args, "sampler_solver", "euler")
+    if flag != "euler":
+        return check_solver(flag)
+    return check_solver(os.environ.get("G3_SAMPLER_SOLVER", "").strip() or "euler")
+
+
+def apply_sampler_solver(args, denoiser, log=print) -> str:
+    """Sets the requested solver on the denoiser and says once when it is not the parity path. Returns the solver's name."""
+    denoiser.solver = solver = sampler_solver_requested(args)
+    if solver != "euler":
+        log(f"[gen3c_amd] --sampler_solver {solver}: second-order multistep denoise steps from the previous step's x0 prediction; this mode is "
+            f"outside the parity statement (DESIGN.md section 12)")
+    return solver
 
 
 def self_attn_window_requested(args):
@@ -290,8 +313,9 @@ class Session:
                                          shard_group=self.shard_group if self.cfg_size > 1 else None)
         if self.cfg_group is not None:
             self.model.denoiser.enable_cfg_parallel(self.cfg_group)
+        solver = apply_sampler_solver(args, self.model.denoiser)
         self.pipe = Gen3cPipeline(self.model, guidance=args.guidance, num_steps=args.num_steps, height=H, width=W, fps=args.fps,
-                                  num_video_frames=self.chunk, seed=args.seed)
+                                  num_video_frames=self.chunk, seed=args.seed, sampler_solver=solver)
         log_ignored_flags(args)
         self.text = TextEmbedder(args, net.crossattn_emb_channels, dev)
         self.pipe.text_encoder = self.text  # Gen3cPipeline.generate(prompt="...") - the reference's keyword form - embeds through it

@@ -13,6 +13,8 @@
 // torch runs a multiply and an add as two kernels).
 #include "common.hpp"
 
+#include <cfloat>
+
 namespace {
 
 G3_DEVICE float rbf(float v) { return (float)f32_to_bf16(v); }  // one bf16 rounding
@@ -84,6 +86,45 @@ __global__ __launch_bounds__(256) void edm_step_kernel(StepArgs a) {
     }
 }
 
+// The opt-in second-order multistep solver ("2ab": the Adams-Bashforth exponential integrator of arXiv 2308.02157, the reference's
+// functional/multi_step.py::order2_fn). Everything up to and including the fp32 x0 prediction is edm_step_kernel's chain, restated here so that
+// the Euler kernel stays as it is; the x0 prediction is also stored (fp32) as the next step's history. have_prev == 0: the Euler update, the same
+// bits as edm_step_kernel. have_prev != 0: xt_next = bf16(a * x + (cb1 * x0 + cb2 * x0_prev)), each an fp32 operation of its own (no contraction),
+// a / cb1 / cb2 computed by the host in fp64 (gen3c_amd/sampler.py::res_2ab_coefficients). x0_out may be x0_prev: element i is read before it is
+// written, by the one thread that owns it. Plain 4-byte history accesses: the kernel moves 18 B per element once per 3 s step.
+struct Step2abArgs {
+    StepArgs e;
+    const float* x0_prev; float* x0_out;
+    int have_prev;
+    float a, cb1, cb2;
+};
+
+__global__ __launch_bounds__(256) void edm_step_2ab_kernel(Step2abArgs s) {
+    const StepArgs& a = s.e;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        const int t = (int)((i / a.hw) % a.T);
+        const float ind = a.indicator[t];
+        const float oc = (float)a.out_cond[i], ou = (float)a.out_uncond[i];
+        float no = rbf(oc + rbf(a.guidance * rbf(oc - ou)));
+        const float x = (float)a.new_xt[i];
+        if (ind != 0.f) {
+            const float lu = rbf(rbf((float)a.gt_latent[i] - rbf(a.c_skip_bf16 * x)) / a.c_out_bf16);
+            no = rbf(rbf(ind * lu) + rbf(rbf(1.f - ind) * no));
+        }
+        const float x0 = a.c_skip * x + rbf(a.c_out * no);
+        float next;
+        if (s.have_prev) {
+            const float hist = s.cb1 * x0 + s.cb2 * s.x0_prev[i];  // read before x0_out[i] is written: the two may be one buffer
+            next = s.a * x + hist;
+        } else {
+            const float deriv = (x - x0) * a.inv_sigma;
+            next = x + deriv * (a.sigma_next - a.sigma);
+        }
+        s.x0_out[i] = x0;
+        a.xt_next[i] = f32_to_bf16(next);
+    }
+}
+
 int grid_for(int64_t n) {
     int64_t b = (n + 255) / 256;
     return (int)(b > 256 * 8 ? 256 * 8 : b);
@@ -116,4 +157,21 @@ extern "C" int g3_edm_cfg_euler_step_bf16(const void* out_cond, const void* out_
                indicator, (bf16_t*)xt_next, n, T, hw, guidance, c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next, inv_sigma};
     hipLaunchKernelGGL(edm_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a);
     return g3_check_launch("g3_edm_cfg_euler_step_bf16");
+}
+
+extern "C" int g3_edm_cfg_2ab_step_bf16(const void* out_cond, const void* out_uncond, const void* new_xt, const void* gt_latent,
+                                        const float* indicator, void* xt_next, int64_t n, int T, int hw, float guidance,
+                                        float c_skip_bf16, float c_out_bf16, float c_skip, float c_out, float sigma, float inv_sigma,
+                                        float sigma_next, const float* x0_prev, float* x0_out, int have_prev, float a, float cb1,
+                                        float cb2, void* stream) {
+    if (!out_cond || !out_uncond || !new_xt || !gt_latent || !indicator || !xt_next || !x0_out)
+        return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_2ab_step_bf16: null operand");
+    if (n <= 0 || T <= 0 || hw <= 0 || sigma <= 0.f || !(inv_sigma > 0.f)) return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_2ab_step_bf16: bad argument");
+    if (have_prev && !x0_prev) return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_2ab_step_bf16: have_prev without x0_prev");
+    if (have_prev && !(a > 0.f && a <= FLT_MAX)) return g3_set_error(G3_ERR_ARG, "g3_edm_cfg_2ab_step_bf16: a must be finite and positive");
+    Step2abArgs s{{(const bf16_t*)out_cond, (const bf16_t*)out_uncond, (const bf16_t*)new_xt, (const bf16_t*)gt_latent, indicator,
+                   (bf16_t*)xt_next, n, T, hw, guidance, c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next, inv_sigma},
+                  x0_prev, x0_out, have_prev, a, cb1, cb2};
+    hipLaunchKernelGGL(edm_step_2ab_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, s);
+    return g3_check_launch("g3_edm_cfg_2ab_step_bf16");
 }

@@ -14,12 +14,16 @@ produce (several of them are bf16 because the loop's `sigma` is cast with `.to(*
 bf16 ones on the device; tests/test_sampler_kernels_gpu.py checks that the host gives the same numbers at every step.
 tests/sampler_ref.py states the whole dtype chain - which operand is bf16 or fp32, on the device or a CPU 0-dim scalar - and
 the kernels plus these scalars are held to it bit for bit.
+
+Opt-in and outside that statement: solver "2ab" (Gen3CDenoiser.solver) - the second-order multistep update of the reference's
+res_sampler.py in place of the Euler update, from the previous step's x0 prediction, in a third kernel (g3_edm_cfg_2ab_step_bf16).
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass, fields
-from typing import Dict, Optional
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 import torch
@@ -56,6 +60,40 @@ class EDMEulerScheduler:
         idx = (self.timesteps == timestep).nonzero()
         pos = 1 if len(idx) > 1 else 0
         return int(idx[pos].item())
+
+
+SOLVERS = ("euler", "2ab")
+
+
+def check_solver(name: str) -> str:
+    if name not in SOLVERS:
+        raise ValueError(f"sampler solver {name!r}: expected one of {SOLVERS}")
+    return name
+
+
+def res_2ab_coefficients(s: float, t: float, s1: float) -> Tuple[float, float, float]:
+    """(a, cb1, cb2) of one second-order multistep step from sigma s to sigma t with the previous step's sigma s1 (s1 > s > t > 0):
+    x_t = a * x_s + cb1 * x0_s + cb2 * x0_s1. The Adams-Bashforth exponential integrator of arXiv 2308.02157 in the reference's form
+    (functional/multi_step.py::order2_fn -> functional/runge_kutta.py::res_x0_rk2_step: time is -log sigma), in fp64 on the host."""
+    ls, lt, lm = -math.log(s), -math.log(t), -math.log(s1)
+    dt = lt - ls
+    c2 = (lm - ls) / dt
+
+    def phi1(u):
+        return math.expm1(u) / u
+
+    def phi2(u):
+        return (phi1(u) - 1.0) / u
+
+    return math.exp(-dt), dt * (phi1(-dt) - phi2(-dt) / c2), dt * phi2(-dt) / c2
+
+
+@dataclass
+class Res2abState:
+    """What solver "2ab" carries from step to step of ONE sampling loop: the previous step's fp32 x0 prediction (this rank's shard, allocated by the
+    first step, overwritten in place) and whether it holds one yet."""
+    x0: Optional[torch.Tensor] = None
+    have_prev: bool = False
 
 
 @dataclass
@@ -119,6 +157,15 @@ class Gen3CDenoiser:
         self._fused_cache = None
         self.fuse_cond_uncond = os.environ.get("G3_FUSE_COND_UNCOND", "1") != "0"  # one batched forward for the conditional and the unconditional branch of a step (False: two calls)
         self.cfg_group = None  # CFG-parallel (opt-in): the pair of ranks that run the two guidance branches of a step, see enable_cfg_parallel
+        self.solver = "euler"  # "2ab" (opt-in): second-order multistep update from the previous step's x0 prediction, outside the parity statement
+
+    @property
+    def solver(self) -> str:
+        return self._solver
+
+    @solver.setter
+    def solver(self, name: str) -> None:
+        self._solver = check_solver(name)
 
     def enable_cfg_parallel(self, group) -> None:
         """CFG-parallel: `group` is a 2-rank torch.distributed group (parallel_state.get_cfg_parallel_group()). Its rank 0 runs the conditional
@@ -195,8 +242,10 @@ class Gen3CDenoiser:
     @torch.no_grad()
     def denoise_step(self, xt: torch.Tensor, step_index: int, condition: VideoExtendCondition,
                      uncondition: VideoExtendCondition, guidance: float, condition_augment_sigma: float,
-                     seed: int) -> torch.Tensor:
-        """model_v2w.py:130-149 for scheduler step `step_index`; xt is this rank's [B,C,T_local,H,W] bf16 shard."""
+                     seed: int, *, solver_state: Optional[Res2abState] = None) -> torch.Tensor:
+        """model_v2w.py:130-149 for scheduler step `step_index`; xt is this rank's [B,C,T_local,H,W] bf16 shard. `solver_state` (None: the
+        reference's Euler update) is the loop's state under solver "2ab": the step's x0 prediction is kept in it, and a step that has a previous one
+        and does not end at sigma 0 takes the second-order update instead (the step to sigma 0 returns x0 either way: -log 0 has no 2ab form)."""
         sch = self.scheduler
         sigma32, sigma_next32 = sch.sigmas[step_index], sch.sigmas[step_index + 1]
         co = self._coefficients(sigma32, sigma_next32, condition_augment_sigma)
@@ -248,17 +297,28 @@ class Gen3CDenoiser:
         else:
             out_c = self.net(x=new_xt_scaled, timesteps=t, **condition.to_dict())
             out_u = self.net(x=new_xt_scaled, timesteps=t, **uncondition.to_dict())
-        return ops.edm_cfg_euler_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"],
-                                      co["c_skip"], co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"])
+        if solver_state is None or co["sigma_next"] == 0.0:
+            return ops.edm_cfg_euler_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"],
+                                          co["c_skip"], co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"])
+        st = solver_state
+        if st.x0 is None:
+            st.x0 = torch.empty(new_xt.shape, dtype=torch.float32, device=new_xt.device)
+        a, cb1, cb2 = res_2ab_coefficients(co["sigma"], co["sigma_next"], float(sch.sigmas[step_index - 1])) if st.have_prev else (0.0, 0.0, 0.0)
+        out = ops.edm_cfg_2ab_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"], co["c_skip"],
+                                   co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"], st.x0, st.have_prev, a, cb1, cb2)
+        st.have_prev = True
+        return out
 
     @torch.no_grad()
     def generate_samples_from_batch(self, condition: VideoExtendCondition, uncondition: VideoExtendCondition,
                                     guidance: float = 1.0, seed: int = 1, state_shape=None, n_sample: int = 1,
                                     num_steps: int = 35, condition_augment_sigma: float = 0.001,
-                                    xt: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                    xt: Optional[torch.Tensor] = None, solver: Optional[str] = None) -> torch.Tensor:
         """Sampling loop of model_v2w.py:84-155 given ready conditions. `xt` (optional) injects the initial noise
         (already multiplied by init_noise_sigma) - torch.randn on the device is not reproducible across vendors, parity
-        runs inject it (SURVEY.md 7 'RNG parity')."""
+        runs inject it (SURVEY.md 7 'RNG parity'). `solver` (None: self.solver): "euler" is the reference's loop; "2ab" (opt-in, DESIGN.md
+        section 12) keeps the x0 prediction of the previous step for the length of this call and takes second-order steps from it."""
+        solver = self.solver if solver is None else check_solver(solver)
         state_shape = list(state_shape or self.state_shape)
         self.scheduler.set_timesteps(num_steps)
         dev = condition.gt_latent.device
@@ -268,8 +328,13 @@ class Gen3CDenoiser:
         to_cp = self.net.is_context_parallel_enabled
         if to_cp:
             xt = split_inputs_cp(xt, 2, self.net.cp_group)
-        for i in range(num_steps):
-            xt = self.denoise_step(xt, i, condition, uncondition, guidance, condition_augment_sigma, seed)
+        if solver == "euler":
+            for i in range(num_steps):
+                xt = self.denoise_step(xt, i, condition, uncondition, guidance, condition_augment_sigma, seed)
+        else:
+            state = Res2abState()  # lives for this call only: a new chunk never sees the previous chunk's history
+            for i in range(num_steps):
+                xt = self.denoise_step(xt, i, condition, uncondition, guidance, condition_augment_sigma, seed, solver_state=state)
         if to_cp:
             xt = cat_outputs_cp(xt, 2, self.net.cp_group)
         return xt

@@ -435,6 +435,19 @@ int g3_edm_cfg_euler_step_bf16(const void* out_cond, const void* out_uncond, con
                                const float* indicator, void* xt_next, int64_t n, int T, int hw, float guidance,
                                float c_skip_bf16, float c_out_bf16, float c_skip, float c_out, float sigma,
                                float inv_sigma, float sigma_next, void* stream);
+/* Opt-in second-order multistep solver "2ab" (Adams-Bashforth exponential integrator, arXiv 2308.02157; the reference's
+ * functional/multi_step.py::order2_fn). The step entry's chain up to the fp32 x0 prediction, unchanged, then
+ *   have_prev == 0: the Euler update above, the same bits as g3_edm_cfg_euler_step_bf16;
+ *   have_prev != 0: xt_next = bf16(a*x + (cb1*x0 + cb2*x0_prev)), fp32, evaluated in that order without contraction. With
+ *     s = sigma, t = sigma_next, s1 = the previous step's sigma: dt = log(s/t), c2 = log(s/s1)/dt, phi1(u) = expm1(u)/u,
+ *     phi2(u) = (phi1(u)-1)/u, a = exp(-dt), cb1 = dt*(phi1(-dt) - phi2(-dt)/c2), cb2 = dt*phi2(-dt)/c2 (host, fp64, passed as fp32).
+ * Both write x0_out (f32 [n]), the next step's x0_prev. x0_out may alias x0_prev: every element is read before it is written,
+ * by the same thread. No other aliasing is allowed. Refused: null operands (x0_prev only when have_prev), bad shapes, sigma <= 0,
+ * and with have_prev a non-finite or non-positive a. */
+int g3_edm_cfg_2ab_step_bf16(const void* out_cond, const void* out_uncond, const void* new_xt, const void* gt_latent,
+                             const float* indicator, void* xt_next, int64_t n, int T, int hw, float guidance, float c_skip_bf16,
+                             float c_out_bf16, float c_skip, float c_out, float sigma, float inv_sigma, float sigma_next,
+                             const float* x0_prev, float* x0_out, int have_prev, float a, float cb1, float cb2, void* stream);
 
 /* ---- 3D-cache renderer (all f32; n "items" = (target frame, cache buffer) pairs, each h x w) -----------------------
  * Replaces forward_warp(depth1=None, world_points1=...) + bilinear_splatting + the mesh-occlusion branch
