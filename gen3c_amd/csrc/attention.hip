@@ -668,14 +668,19 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
     auto row_max = [&](const f32x16 (&S)[2]) -> float {  // two independent v_max3 chains (one per 32-kv block)
         if (G3_AB_ATTN_ABLATE & 4) return 0.f;
-        float ma = max3(S[0][0], S[0][1], S[0][2]);
-        float mb2 = max3(S[1][0], S[1][1], S[1][2]);
+        // max3 is inline asm: the compiler schedules it by its operands but does not pad it against the MFMA that writes them (XDL write -> VALU
+        // read wait states), and it hoists this chain to right behind the last QK^T MFMA of a block - the asm then read the block's scores one
+        // accumulation step short (seen in the folded kernel: a reference point 4.09 below the row maximum, never rescaled, other rows in every
+        // launch). One compiler-generated VALU read per block (v_max x, x: the value unchanged) takes the padding; the asm chain hangs off its result.
+        float ma = max3(__builtin_canonicalizef(S[0][0]), S[0][1], S[0][2]);
+        float mb2 = max3(__builtin_canonicalizef(S[1][0]), S[1][1], S[1][2]);
 #pragma unroll
         for (int r = 3; r < 15; r += 2) {
             ma = max3(ma, S[0][r], S[0][r + 1]);
             mb2 = max3(mb2, S[1][r], S[1][r + 1]);
         }
-        return xor32_max(max3(ma, mb2, max3(S[0][15], S[1][15], S[1][15]))) * (FOLD ? 1.0f : c);
+        mb2 = max3(mb2, S[1][15], S[0][15]);  // (behind block 1's read above, hence behind both blocks' MFMAs)
+        return xor32_max(max3(ma, mb2, mb2)) * (FOLD ? 1.0f : c);
     };
     auto mask_tail = [&](f32x16 (&S)[2], int kv0) {
 #pragma unroll
