@@ -128,6 +128,8 @@ SIGNATURES = {
     "g3_edm_prepare_input_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, vp],
     "g3_edm_cfg_euler_step_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, vp],
     "g3_edm_cfg_2ab_step_bf16": [vp, vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, f32, f32, f32, vp],
+    "g3_edm_cond_euler_step_bf16": [vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp],
+    "g3_edm_cond_2ab_step_bf16": [vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, f32, f32, f32, vp],
 }
 _RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_self_attn16_kernel_name": C.c_char_p, "g3_attn_plan16_bf16": C.c_char_p, "g3_attn_window_plan_bf16": C.c_char_p, "g3_attn_window_cp_plan_bf16": C.c_char_p, "g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
              "g3_warp_windows_workspace_bytes": C.c_size_t, "g3_render_workspace_bytes": C.c_size_t}

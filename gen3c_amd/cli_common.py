@@ -59,6 +59,11 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                         "multistep solver that reuses the previous step's x0 prediction, no extra network call: less solver error from about 18 "
                         "steps up, worse below; outside the parity statement, picture quality with trained weights unmeasured: DESIGN.md section "
                         "12; same as G3_SAMPLER_SOLVER=2ab)")
+    p.add_argument("--guidance_interval", type=str, default=None, metavar="LO,HI",
+                   help="classifier-free guidance only on the denoise steps with LO < sigma <= HI (sigma units, HI may be inf); a step outside the "
+                        "interval runs the conditional branch alone, one network call instead of the fused pair (opt-in, default unset: every step "
+                        "guided; outside the parity statement, picture quality with trained weights unmeasured: DESIGN.md section 13; same as "
+                        "G3_GUIDANCE_INTERVAL=\"LO,HI\")")
     p.add_argument("--dit_precision", choices=("bf16", "mxfp8", "mxfp6"), default="bf16",
                    help="precision of the DiT's six per-block linears: bf16 (default, the parity path), mxfp8 (opt-in MXFP8 matrix cores) or mxfp6 "
                         "(opt-in MXFP6 e2m3 operands on the same matrix cores at twice the rate); both outside the parity statement, DESIGN.md "
@@ -133,6 +138,34 @@ def apply_sampler_solver(args, denoiser, log=print) -> str:
         log(f"[gen3c_amd] --sampler_solver {solver}: second-order multistep denoise steps from the previous step's x0 prediction; this mode is "
             f"outside the parity statement (DESIGN.md section 12)")
     return solver
+
+
+def guidance_interval_requested(args):
+    """--guidance_interval LO,HI, or G3_GUIDANCE_INTERVAL="LO,HI" in the environment when the flag is unset -> (lo, hi) in sigma units, or None
+    with neither (opt-in, default off). HI may be inf. A value that is not two numbers with 0 <= LO < HI raises ValueError."""
+    from .sampler import check_guidance_interval
+    flag = getattr(args, "guidance_interval", None)
+    text, where = (flag, "--guidance_interval") if flag is not None else (os.environ.get("G3_GUIDANCE_INTERVAL", "").strip() or None, "G3_GUIDANCE_INTERVAL")
+    if text is None:
+        return None
+    parts = [x.strip() for x in text.split(",")]
+    try:
+        if len(parts) != 2:
+            raise ValueError
+        pair = (float(parts[0]), float(parts[1]))
+    except ValueError:
+        raise ValueError(f"{where} {text!r}: expected \"LO,HI\" in sigma units with 0 <= LO < HI (HI may be inf)") from None
+    return check_guidance_interval(pair)
+
+
+def apply_guidance_interval(args, denoiser, log=print):
+    """Sets the requested guidance interval on the denoiser and says once what the mode does. Returns the interval, or None."""
+    denoiser.guidance_interval = interval = guidance_interval_requested(args)
+    if interval is not None:
+        log(f"[gen3c_amd] --guidance_interval {interval[0]:g},{interval[1]:g}: classifier-free guidance only on the steps with {interval[0]:g} < sigma "
+            f"<= {interval[1]:g}; the other steps run the conditional branch alone, one network call each; this mode is outside the parity "
+            f"statement, picture quality unmeasured (DESIGN.md section 13)")
+    return interval
 
 
 def self_attn_window_requested(args):
@@ -314,8 +347,9 @@ class Session:
         if self.cfg_group is not None:
             self.model.denoiser.enable_cfg_parallel(self.cfg_group)
         solver = apply_sampler_solver(args, self.model.denoiser)
+        interval = apply_guidance_interval(args, self.model.denoiser)
         self.pipe = Gen3cPipeline(self.model, guidance=args.guidance, num_steps=args.num_steps, height=H, width=W, fps=args.fps,
-                                  num_video_frames=self.chunk, seed=args.seed, sampler_solver=solver)
+                                  num_video_frames=self.chunk, seed=args.seed, sampler_solver=solver, guidance_interval=interval)
         log_ignored_flags(args)
         self.text = TextEmbedder(args, net.crossattn_emb_channels, dev)
         self.pipe.text_encoder = self.text  # Gen3cPipeline.generate(prompt="...") - the reference's keyword form - embeds through it

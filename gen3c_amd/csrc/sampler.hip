@@ -125,6 +125,66 @@ __global__ __launch_bounds__(256) void edm_step_2ab_kernel(Step2abArgs s) {
     }
 }
 
+// The opt-in guidance interval (classifier-free guidance only while sigma_lo < sigma <= sigma_hi, arXiv 2404.07724): a step outside the interval has
+// no unconditional network output, net_output IS out_cond (no arithmetic on it). From the conditioning-frame replacement on, the chain of
+// edm_step_kernel / edm_step_2ab_kernel restated - the same bf16 rounding points, the same fp32 operations - so that those two kernels stay as they
+// are. cond_x0 is shared by the two kernels below and by nothing else.
+struct CondStepArgs {
+    const bf16_t* out_cond;
+    const bf16_t* new_xt; const bf16_t* gt_latent; const float* indicator;
+    bf16_t* xt_next;
+    int64_t n; int T; int hw;
+    float c_skip_bf16, c_out_bf16;
+    float c_skip, c_out;
+    float sigma, sigma_next;
+    float inv_sigma;
+};
+
+G3_DEVICE float cond_x0(const CondStepArgs& a, int64_t i, float x) {
+    const int t = (int)((i / a.hw) % a.T);
+    const float ind = a.indicator[t];
+    float no = (float)a.out_cond[i];  // net_output = out_cond
+    if (ind != 0.f) {
+        const float lu = rbf(rbf((float)a.gt_latent[i] - rbf(a.c_skip_bf16 * x)) / a.c_out_bf16);
+        no = rbf(rbf(ind * lu) + rbf(rbf(1.f - ind) * no));
+    }
+    return a.c_skip * x + rbf(a.c_out * no);
+}
+
+__global__ __launch_bounds__(256) void edm_cond_step_kernel(CondStepArgs a) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        const float x = (float)a.new_xt[i];
+        const float x0 = cond_x0(a, i, x);
+        const float deriv = (x - x0) * a.inv_sigma;
+        a.xt_next[i] = f32_to_bf16(x + deriv * (a.sigma_next - a.sigma));
+    }
+}
+
+struct CondStep2abArgs {
+    CondStepArgs e;
+    const float* x0_prev; float* x0_out;
+    int have_prev;
+    float a, cb1, cb2;
+};
+
+__global__ __launch_bounds__(256) void edm_cond_step_2ab_kernel(CondStep2abArgs s) {
+    const CondStepArgs& a = s.e;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+        const float x = (float)a.new_xt[i];
+        const float x0 = cond_x0(a, i, x);
+        float next;
+        if (s.have_prev) {
+            const float hist = s.cb1 * x0 + s.cb2 * s.x0_prev[i];  // read before x0_out[i] is written: the two may be one buffer
+            next = s.a * x + hist;
+        } else {
+            const float deriv = (x - x0) * a.inv_sigma;
+            next = x + deriv * (a.sigma_next - a.sigma);
+        }
+        s.x0_out[i] = x0;
+        a.xt_next[i] = f32_to_bf16(next);
+    }
+}
+
 int grid_for(int64_t n) {
     int64_t b = (n + 255) / 256;
     return (int)(b > 256 * 8 ? 256 * 8 : b);
@@ -174,4 +234,32 @@ extern "C" int g3_edm_cfg_2ab_step_bf16(const void* out_cond, const void* out_un
                   x0_prev, x0_out, have_prev, a, cb1, cb2};
     hipLaunchKernelGGL(edm_step_2ab_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, s);
     return g3_check_launch("g3_edm_cfg_2ab_step_bf16");
+}
+
+extern "C" int g3_edm_cond_euler_step_bf16(const void* out_cond, const void* new_xt, const void* gt_latent, const float* indicator,
+                                           void* xt_next, int64_t n, int T, int hw, float c_skip_bf16, float c_out_bf16, float c_skip,
+                                           float c_out, float sigma, float inv_sigma, float sigma_next, void* stream) {
+    if (!out_cond || !new_xt || !gt_latent || !indicator || !xt_next)
+        return g3_set_error(G3_ERR_ARG, "g3_edm_cond_euler_step_bf16: null operand");
+    if (n <= 0 || T <= 0 || hw <= 0 || sigma <= 0.f || !(inv_sigma > 0.f)) return g3_set_error(G3_ERR_ARG, "g3_edm_cond_euler_step_bf16: bad argument");
+    CondStepArgs a{(const bf16_t*)out_cond, (const bf16_t*)new_xt, (const bf16_t*)gt_latent, indicator, (bf16_t*)xt_next, n, T, hw,
+                   c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next, inv_sigma};
+    hipLaunchKernelGGL(edm_cond_step_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, a);
+    return g3_check_launch("g3_edm_cond_euler_step_bf16");
+}
+
+extern "C" int g3_edm_cond_2ab_step_bf16(const void* out_cond, const void* new_xt, const void* gt_latent, const float* indicator,
+                                         void* xt_next, int64_t n, int T, int hw, float c_skip_bf16, float c_out_bf16, float c_skip,
+                                         float c_out, float sigma, float inv_sigma, float sigma_next, const float* x0_prev, float* x0_out,
+                                         int have_prev, float a, float cb1, float cb2, void* stream) {
+    if (!out_cond || !new_xt || !gt_latent || !indicator || !xt_next || !x0_out)
+        return g3_set_error(G3_ERR_ARG, "g3_edm_cond_2ab_step_bf16: null operand");
+    if (n <= 0 || T <= 0 || hw <= 0 || sigma <= 0.f || !(inv_sigma > 0.f)) return g3_set_error(G3_ERR_ARG, "g3_edm_cond_2ab_step_bf16: bad argument");
+    if (have_prev && !x0_prev) return g3_set_error(G3_ERR_ARG, "g3_edm_cond_2ab_step_bf16: have_prev without x0_prev");
+    if (have_prev && !(a > 0.f && a <= FLT_MAX)) return g3_set_error(G3_ERR_ARG, "g3_edm_cond_2ab_step_bf16: a must be finite and positive");
+    CondStep2abArgs s{{(const bf16_t*)out_cond, (const bf16_t*)new_xt, (const bf16_t*)gt_latent, indicator, (bf16_t*)xt_next, n, T, hw,
+                       c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, sigma_next, inv_sigma},
+                      x0_prev, x0_out, have_prev, a, cb1, cb2};
+    hipLaunchKernelGGL(edm_cond_step_2ab_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, s);
+    return g3_check_launch("g3_edm_cond_2ab_step_bf16");
 }

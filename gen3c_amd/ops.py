@@ -815,6 +815,42 @@ def edm_cfg_2ab_step(out_cond, out_uncond, new_xt, gt_latent, indicator, T: int,
     return xt_next
 
 
+def edm_cond_euler_step(out_cond, new_xt, gt_latent, indicator, T: int, hw: int, c_skip_bf16: float, c_out_bf16: float, c_skip: float,
+                        c_out: float, sigma: float, inv_sigma: float, sigma_next: float):
+    """-> xt_next (bf16): the Euler step of a sigma outside the guidance interval, net_output = out_cond. See g3_edm_cond_euler_step_bf16."""
+    for t in (out_cond, new_xt, gt_latent, indicator):
+        assert t.is_contiguous()
+    assert out_cond.shape == new_xt.shape == gt_latent.shape
+    assert indicator.numel() == T and new_xt.numel() % (T * hw) == 0
+    xt_next = torch.empty_like(new_xt)
+    lib = _lib.load()
+    _lib.check(lib.g3_edm_cond_euler_step_bf16(_dev(out_cond, "out_cond"), _dev(new_xt, "new_xt"), _dev(gt_latent, "gt_latent"),
+                                               _dev(indicator, "indicator", torch.float32), _dev(xt_next, "xt_next"), new_xt.numel(), T, hw,
+                                               c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, inv_sigma, sigma_next, _stream()),
+               "g3_edm_cond_euler_step_bf16")
+    return xt_next
+
+
+def edm_cond_2ab_step(out_cond, new_xt, gt_latent, indicator, T: int, hw: int, c_skip_bf16: float, c_out_bf16: float, c_skip: float,
+                      c_out: float, sigma: float, inv_sigma: float, sigma_next: float, x0_hist, have_prev: bool, a: float, cb1: float,
+                      cb2: float, x0_out=None):
+    """-> xt_next (bf16): edm_cfg_2ab_step for a sigma outside the guidance interval, net_output = out_cond; x0_hist / x0_out as there.
+    See g3_edm_cond_2ab_step_bf16."""
+    x0_out = x0_hist if x0_out is None else x0_out
+    for t in (out_cond, new_xt, gt_latent, indicator, x0_hist, x0_out):
+        assert t.is_contiguous()
+    assert out_cond.shape == new_xt.shape == gt_latent.shape == x0_hist.shape == x0_out.shape
+    assert indicator.numel() == T and new_xt.numel() % (T * hw) == 0
+    xt_next = torch.empty_like(new_xt)
+    lib = _lib.load()
+    _lib.check(lib.g3_edm_cond_2ab_step_bf16(_dev(out_cond, "out_cond"), _dev(new_xt, "new_xt"), _dev(gt_latent, "gt_latent"),
+                                             _dev(indicator, "indicator", torch.float32), _dev(xt_next, "xt_next"), new_xt.numel(), T, hw,
+                                             c_skip_bf16, c_out_bf16, c_skip, c_out, sigma, inv_sigma, sigma_next,
+                                             _dev(x0_hist, "x0_hist", torch.float32), _dev(x0_out, "x0_out", torch.float32),
+                                             int(bool(have_prev)), a, cb1, cb2, _stream()), "g3_edm_cond_2ab_step_bf16")
+    return xt_next
+
+
 class HipTimer:
     """hipEvent pair recorded on torch's current stream through the C ABI (used by bench.py for kernel timing)."""
 

@@ -24,7 +24,7 @@ import torch
 
 from .dit import VideoExtendGeneralDIT
 from .parallel import broadcast, parallel_state
-from .sampler import Gen3CDenoiser, VideoExtendCondition, add_condition_video_indicator_and_video_input_mask, check_solver
+from .sampler import Gen3CDenoiser, VideoExtendCondition, add_condition_video_indicator_and_video_input_mask, check_guidance_interval, check_solver
 from .tokenizer import VideoTokenizer
 
 DEFAULT_AUGMENT_SIGMA = 0.001  # inference_utils.py
@@ -150,13 +150,15 @@ class DiffusionGen3CModel:
                                     is_negative_prompt: bool = False, num_steps: int = 35, condition_latent: Optional[torch.Tensor] = None,
                                     num_condition_t: Optional[int] = None, condition_augment_sigma: float = None,
                                     add_input_frames_guidance: bool = False, xt: Optional[torch.Tensor] = None,
-                                    solver: Optional[str] = None) -> torch.Tensor:
-        """model_v2w.py:84-155. `solver`: None = the denoiser's setting ("euler" unless changed), or "euler" / "2ab" (sampler.py)."""
+                                    solver: Optional[str] = None, guidance_interval=None) -> torch.Tensor:
+        """model_v2w.py:84-155. `solver`: None = the denoiser's setting ("euler" unless changed), or "euler" / "2ab" (sampler.py).
+        `guidance_interval`: None = the denoiser's setting (None unless changed: every step guided), or (lo, hi) in sigma units (sampler.py)."""
         assert condition_latent is not None, "condition_latent should be provided"
         condition, uncondition = self._get_conditions(data_batch, is_negative_prompt, condition_latent, num_condition_t, add_input_frames_guidance)
         return self.denoiser.generate_samples_from_batch(condition, uncondition, guidance=guidance, seed=seed,
                                                          state_shape=state_shape or self.state_shape, n_sample=n_sample, num_steps=num_steps,
-                                                         condition_augment_sigma=condition_augment_sigma, xt=xt, solver=solver)
+                                                         condition_augment_sigma=condition_augment_sigma, xt=xt, solver=solver,
+                                                         guidance_interval=guidance_interval)
 
 
 def compute_num_latent_frames(model: DiffusionGen3CModel, num_input_frames: int, downsample_factor: int = 8) -> int:
@@ -184,7 +186,7 @@ def create_condition_latent_from_input_frames(model: DiffusionGen3CModel, input_
 
 def generate_world_from_video(model: DiffusionGen3CModel, state_shape, is_negative_prompt: bool, data_batch: dict, guidance: float,
                               num_steps: int, seed: int, condition_latent: torch.Tensor, num_input_frames: int,
-                              xt: Optional[torch.Tensor] = None, solver: Optional[str] = None) -> torch.Tensor:
+                              xt: Optional[torch.Tensor] = None, solver: Optional[str] = None, guidance_interval=None) -> torch.Tensor:
     """inference_utils.py:542-595."""
     if condition_latent.shape[2] < state_shape[1]:
         b, c, t, h, w = condition_latent.shape
@@ -192,7 +194,7 @@ def generate_world_from_video(model: DiffusionGen3CModel, state_shape, is_negati
     return model.generate_samples_from_batch(data_batch, guidance=guidance, state_shape=state_shape, num_steps=num_steps,
                                              is_negative_prompt=is_negative_prompt, seed=seed, condition_latent=condition_latent,
                                              num_condition_t=compute_num_latent_frames(model, num_input_frames),
-                                             condition_augment_sigma=DEFAULT_AUGMENT_SIGMA, xt=xt, solver=solver)
+                                             condition_augment_sigma=DEFAULT_AUGMENT_SIGMA, xt=xt, solver=solver, guidance_interval=guidance_interval)
 
 
 class Gen3cPipeline:
@@ -200,14 +202,17 @@ class Gen3cPipeline:
     T5 embeddings and the rendered 3D-cache buffers, returns the uint8 video."""
 
     def __init__(self, model: DiffusionGen3CModel, guidance: float = 1.0, num_steps: int = 35, height: int = 704, width: int = 1280,
-                 fps: int = 24, num_video_frames: int = 121, seed: int = 1, text_encoder=None, sampler_solver: Optional[str] = None):
+                 fps: int = 24, num_video_frames: int = 121, seed: int = 1, text_encoder=None, sampler_solver: Optional[str] = None,
+                 guidance_interval=None):
         """sampler_solver: None = the denoiser's setting, or "euler" / "2ab" (opt-in second-order multistep solver).
+        guidance_interval: None = the denoiser's setting, or (lo, hi) in sigma units (opt-in: guidance only while lo < sigma <= hi).
         text_encoder: callable str -> T5 embedding [1,512,1024] (cli_common.TextEmbedder; T5-11B itself is an input of the path).
         Only generate() with string prompts needs it."""
         self.model, self.guidance, self.num_steps = model, guidance, num_steps
         self.height, self.width, self.fps, self.num_video_frames, self.seed = height, width, fps, num_video_frames, seed
         self.text_encoder = text_encoder
         self.sampler_solver = None if sampler_solver is None else check_solver(sampler_solver)
+        self.guidance_interval = check_guidance_interval(guidance_interval)
 
     @torch.no_grad()
     def generate(self, prompt, image_path, rendered_warp_images: torch.Tensor, rendered_warp_masks: torch.Tensor,
@@ -250,6 +255,7 @@ class Gen3cPipeline:
         batch["condition_state_mask"] = rendered_warp_masks.to(dev)
         # is_negative_prompt=True unconditionally, as Gen3cPipeline._run_model does (gen3c_pipeline.py:247-251)
         sample = generate_world_from_video(self.model, self.model.state_shape, True, batch, self.guidance,
-                                           self.num_steps, self.seed, condition_latent, 1, xt=xt, solver=self.sampler_solver)
+                                           self.num_steps, self.seed, condition_latent, 1, xt=xt, solver=self.sampler_solver,
+                                           guidance_interval=self.guidance_interval)
         video = (1.0 + self.model.decode(sample)).clamp(0, 2) / 2  # world_generation_pipeline.py:244-245
         return (video[0].permute(1, 2, 3, 0) * 255).to(torch.uint8).cpu().numpy()

@@ -17,13 +17,16 @@ the kernels plus these scalars are held to it bit for bit.
 
 Opt-in and outside that statement: solver "2ab" (Gen3CDenoiser.solver) - the second-order multistep update of the reference's
 res_sampler.py in place of the Euler update, from the previous step's x0 prediction, in a third kernel (g3_edm_cfg_2ab_step_bf16).
+Opt-in and outside it too: a guidance interval (Gen3CDenoiser.guidance_interval) - classifier-free guidance only while
+sigma_lo < sigma <= sigma_hi (arXiv 2404.07724); a step outside it makes ONE network call at B, the conditional one, and its update runs in a
+kernel that has no unconditional operand (g3_edm_cond_euler_step_bf16 / g3_edm_cond_2ab_step_bf16).
 """
 from __future__ import annotations
 
 import math
 import os
 from dataclasses import dataclass, fields
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -71,6 +74,30 @@ def check_solver(name: str) -> str:
     return name
 
 
+def check_guidance_interval(v) -> Optional[Tuple[float, float]]:
+    """None (guide every step, the reference's loop), or (lo, hi) in sigma units with 0 <= lo < hi; hi may be inf. -> None / (float, float)."""
+    if v is None:
+        return None
+    try:
+        lo, hi = v
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError(f"guidance interval {v!r}: expected None or (lo, hi) with 0 <= lo < hi (sigma units, hi may be inf)") from None
+    if not (0.0 <= lo < hi) or math.isinf(lo):  # (a NaN fails the comparison)
+        raise ValueError(f"guidance interval {v!r}: expected None or (lo, hi) with 0 <= lo < hi (sigma units, hi may be inf)")
+    return lo, hi
+
+
+def guided_steps(sigmas, interval) -> List[bool]:
+    """Per step of the schedule `sigmas` (the scheduler's fp32 sigmas, the final 0 included or not: a sigma of 0 is no step): does the step apply
+    classifier-free guidance? Step i does iff interval is None or lo < float(sigmas[i]) <= hi."""
+    interval = check_guidance_interval(interval)
+    sig = [float(v) for v in sigmas]
+    if sig and sig[-1] == 0.0:
+        sig = sig[:-1]
+    return [interval is None or interval[0] < v <= interval[1] for v in sig]
+
+
 def res_2ab_coefficients(s: float, t: float, s1: float) -> Tuple[float, float, float]:
     """(a, cb1, cb2) of one second-order multistep step from sigma s to sigma t with the previous step's sigma s1 (s1 > s > t > 0):
     x_t = a * x_s + cb1 * x0_s + cb2 * x0_s1. The Adams-Bashforth exponential integrator of arXiv 2308.02157 in the reference's form
@@ -94,6 +121,7 @@ class Res2abState:
     first step, overwritten in place) and whether it holds one yet."""
     x0: Optional[torch.Tensor] = None
     have_prev: bool = False
+    prev_guided: Optional[bool] = None  # under a guidance interval: whether the step that wrote x0 was guided
 
 
 @dataclass
@@ -158,6 +186,7 @@ class Gen3CDenoiser:
         self.fuse_cond_uncond = os.environ.get("G3_FUSE_COND_UNCOND", "1") != "0"  # one batched forward for the conditional and the unconditional branch of a step (False: two calls)
         self.cfg_group = None  # CFG-parallel (opt-in): the pair of ranks that run the two guidance branches of a step, see enable_cfg_parallel
         self.solver = "euler"  # "2ab" (opt-in): second-order multistep update from the previous step's x0 prediction, outside the parity statement
+        self.guidance_interval = None  # (lo, hi) (opt-in): guidance only while lo < sigma <= hi, one network call per step outside; outside the parity statement
 
     @property
     def solver(self) -> str:
@@ -166,6 +195,14 @@ class Gen3CDenoiser:
     @solver.setter
     def solver(self, name: str) -> None:
         self._solver = check_solver(name)
+
+    @property
+    def guidance_interval(self) -> Optional[Tuple[float, float]]:
+        return self._guidance_interval
+
+    @guidance_interval.setter
+    def guidance_interval(self, v) -> None:
+        self._guidance_interval = check_guidance_interval(v)
 
     def enable_cfg_parallel(self, group) -> None:
         """CFG-parallel: `group` is a 2-rank torch.distributed group (parallel_state.get_cfg_parallel_group()). Its rank 0 runs the conditional
@@ -242,10 +279,14 @@ class Gen3CDenoiser:
     @torch.no_grad()
     def denoise_step(self, xt: torch.Tensor, step_index: int, condition: VideoExtendCondition,
                      uncondition: VideoExtendCondition, guidance: float, condition_augment_sigma: float,
-                     seed: int, *, solver_state: Optional[Res2abState] = None) -> torch.Tensor:
+                     seed: int, *, solver_state: Optional[Res2abState] = None, guided: bool = True) -> torch.Tensor:
         """model_v2w.py:130-149 for scheduler step `step_index`; xt is this rank's [B,C,T_local,H,W] bf16 shard. `solver_state` (None: the
         reference's Euler update) is the loop's state under solver "2ab": the step's x0 prediction is kept in it, and a step that has a previous one
-        and does not end at sigma 0 takes the second-order update instead (the step to sigma 0 returns x0 either way: -log 0 has no 2ab form)."""
+        and does not end at sigma 0 takes the second-order update instead (the step to sigma 0 returns x0 either way: -log 0 has no 2ab form).
+        `guided` (True: the reference's step) is False for a step outside the guidance interval: ONE network call at B, the conditional one - the
+        first call of the two-call form, on every rank of a CFG-parallel pair, no exchange - and the cond entry of the solver in force; `uncondition`,
+        `guidance` and the fused-call cache are not looked at. Under "2ab" a step whose guidedness differs from the previous step's ignores the
+        history (the extrapolation assumes one smooth denoiser; the two predictions differ by g (c - u)), takes the Euler update and stores its x0."""
         sch = self.scheduler
         sigma32, sigma_next32 = sch.sigmas[step_index], sch.sigmas[step_index + 1]
         co = self._coefficients(sigma32, sigma_next32, condition_augment_sigma)
@@ -266,6 +307,21 @@ class Gen3CDenoiser:
         new_xt, new_xt_scaled = ops.edm_prepare_input(xt, gt, noise.contiguous(), ind_t, T, H * W, condition_augment_sigma,
                                                       co["c_in_aug"], co["c_in_bf16"], co["c_in_step"])
         t = sch.timesteps[step_index].to(device=xt.device, dtype=torch.bfloat16)
+        st = solver_state
+        # the history of a step on the other side of an interval boundary is another denoiser's: not used (never so without an interval)
+        have_prev = st is not None and st.have_prev and st.prev_guided in (None, guided)
+        if not guided:
+            out_c = self.net(x=new_xt_scaled, timesteps=t, **condition.to_dict())
+            if st is None or co["sigma_next"] == 0.0:
+                return ops.edm_cond_euler_step(out_c, new_xt, gt, ind_t, T, H * W, co["c_skip_bf16"], co["c_out_bf16"], co["c_skip"], co["c_out"],
+                                               co["sigma"], co["inv_sigma"], co["sigma_next"])
+            if st.x0 is None:
+                st.x0 = torch.empty(new_xt.shape, dtype=torch.float32, device=new_xt.device)
+            a, cb1, cb2 = res_2ab_coefficients(co["sigma"], co["sigma_next"], float(sch.sigmas[step_index - 1])) if have_prev else (0.0, 0.0, 0.0)
+            out = ops.edm_cond_2ab_step(out_c, new_xt, gt, ind_t, T, H * W, co["c_skip_bf16"], co["c_out_bf16"], co["c_skip"], co["c_out"],
+                                        co["sigma"], co["inv_sigma"], co["sigma_next"], st.x0, have_prev, a, cb1, cb2)
+            st.have_prev, st.prev_guided = True, False
+            return out
         fused = None
         if self.fuse_cond_uncond and self.cfg_group is None:
             # the conditions are the same objects for all steps of a chunk: build the batched arguments once (this also keeps the DiT's
@@ -300,25 +356,27 @@ class Gen3CDenoiser:
         if solver_state is None or co["sigma_next"] == 0.0:
             return ops.edm_cfg_euler_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"],
                                           co["c_skip"], co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"])
-        st = solver_state
         if st.x0 is None:
             st.x0 = torch.empty(new_xt.shape, dtype=torch.float32, device=new_xt.device)
-        a, cb1, cb2 = res_2ab_coefficients(co["sigma"], co["sigma_next"], float(sch.sigmas[step_index - 1])) if st.have_prev else (0.0, 0.0, 0.0)
+        a, cb1, cb2 = res_2ab_coefficients(co["sigma"], co["sigma_next"], float(sch.sigmas[step_index - 1])) if have_prev else (0.0, 0.0, 0.0)
         out = ops.edm_cfg_2ab_step(out_c, out_u, new_xt, gt, ind_t, T, H * W, guidance, co["c_skip_bf16"], co["c_out_bf16"], co["c_skip"],
-                                   co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"], st.x0, st.have_prev, a, cb1, cb2)
-        st.have_prev = True
+                                   co["c_out"], co["sigma"], co["inv_sigma"], co["sigma_next"], st.x0, have_prev, a, cb1, cb2)
+        st.have_prev, st.prev_guided = True, True
         return out
 
     @torch.no_grad()
     def generate_samples_from_batch(self, condition: VideoExtendCondition, uncondition: VideoExtendCondition,
                                     guidance: float = 1.0, seed: int = 1, state_shape=None, n_sample: int = 1,
                                     num_steps: int = 35, condition_augment_sigma: float = 0.001,
-                                    xt: Optional[torch.Tensor] = None, solver: Optional[str] = None) -> torch.Tensor:
+                                    xt: Optional[torch.Tensor] = None, solver: Optional[str] = None, guidance_interval=None) -> torch.Tensor:
         """Sampling loop of model_v2w.py:84-155 given ready conditions. `xt` (optional) injects the initial noise
         (already multiplied by init_noise_sigma) - torch.randn on the device is not reproducible across vendors, parity
         runs inject it (SURVEY.md 7 'RNG parity'). `solver` (None: self.solver): "euler" is the reference's loop; "2ab" (opt-in, DESIGN.md
-        section 12) keeps the x0 prediction of the previous step for the length of this call and takes second-order steps from it."""
+        section 12) keeps the x0 prediction of the previous step for the length of this call and takes second-order steps from it.
+        `guidance_interval` (None: self.guidance_interval; that None too: every step guided, the reference's loop): (lo, hi) in sigma units - the steps
+        with lo < sigma <= hi are guided, the others run the conditional branch alone (opt-in)."""
         solver = self.solver if solver is None else check_solver(solver)
+        interval = self.guidance_interval if guidance_interval is None else check_guidance_interval(guidance_interval)
         state_shape = list(state_shape or self.state_shape)
         self.scheduler.set_timesteps(num_steps)
         dev = condition.gt_latent.device
@@ -328,7 +386,11 @@ class Gen3CDenoiser:
         to_cp = self.net.is_context_parallel_enabled
         if to_cp:
             xt = split_inputs_cp(xt, 2, self.net.cp_group)
-        if solver == "euler":
+        if interval is not None:
+            state = Res2abState() if solver == "2ab" else None
+            for i, guided in enumerate(guided_steps(self.scheduler.sigmas, interval)):
+                xt = self.denoise_step(xt, i, condition, uncondition, guidance, condition_augment_sigma, seed, solver_state=state, guided=guided)
+        elif solver == "euler":
             for i in range(num_steps):
                 xt = self.denoise_step(xt, i, condition, uncondition, guidance, condition_augment_sigma, seed)
         else:

@@ -448,6 +448,20 @@ int g3_edm_cfg_2ab_step_bf16(const void* out_cond, const void* out_uncond, const
                              const float* indicator, void* xt_next, int64_t n, int T, int hw, float guidance, float c_skip_bf16,
                              float c_out_bf16, float c_skip, float c_out, float sigma, float inv_sigma, float sigma_next,
                              const float* x0_prev, float* x0_out, int have_prev, float a, float cb1, float cb2, void* stream);
+/* Opt-in guidance interval (classifier-free guidance only while sigma_lo < sigma <= sigma_hi: Kynkaanniemi et al., "Applying Guidance in a
+ * Limited Interval Improves Sample and Distribution Quality in Diffusion Models", arXiv 2404.07724; the reference's loop, model_v2w.py:130-149,
+ * guides every step). The step of a sigma outside the interval: the two entries above without out_uncond and guidance - net_output = out_cond,
+ * no arithmetic on it - and from the conditioning-frame replacement on the same chain, operation for operation and rounding for rounding
+ * (g3_edm_cfg_*_step_bf16 with guidance 0 computes the same values; it still reads an out_uncond, these do not). x0_prev / x0_out / have_prev /
+ * a / cb1 / cb2 as in g3_edm_cfg_2ab_step_bf16, x0_out may alias x0_prev. Refused like their counterparts: null operands (x0_prev only when
+ * have_prev), bad shapes, sigma <= 0, a bad inv_sigma, and with have_prev a non-finite or non-positive a. */
+int g3_edm_cond_euler_step_bf16(const void* out_cond, const void* new_xt, const void* gt_latent, const float* indicator, void* xt_next,
+                                int64_t n, int T, int hw, float c_skip_bf16, float c_out_bf16, float c_skip, float c_out, float sigma,
+                                float inv_sigma, float sigma_next, void* stream);
+int g3_edm_cond_2ab_step_bf16(const void* out_cond, const void* new_xt, const void* gt_latent, const float* indicator, void* xt_next,
+                              int64_t n, int T, int hw, float c_skip_bf16, float c_out_bf16, float c_skip, float c_out, float sigma,
+                              float inv_sigma, float sigma_next, const float* x0_prev, float* x0_out, int have_prev, float a, float cb1,
+                              float cb2, void* stream);
 
 /* ---- 3D-cache renderer (all f32; n "items" = (target frame, cache buffer) pairs, each h x w) -----------------------
  * Replaces forward_warp(depth1=None, world_points1=...) + bilinear_splatting + the mesh-occlusion branch
