@@ -39,6 +39,12 @@ struct AlignState {           // lives in the caller's workspace
     unsigned hist[NSEL][256];
     double partial[RED_BLOCKS][5];
 };
+// tests/test_align_kernels_gpu.py reads the stages back from a workspace it owns (tests/align_kernel_ref.py: workspace_layout mirrors
+// these offsets and the plane order of g3_align_depth_f32: src_inv, tgt_inv, key_s, key_t, sc, m1, v2, e behind the 256-aligned state).
+static_assert(offsetof(AlignState, count) == 0 && offsetof(AlignState, rank) == 8 && offsetof(AlignState, prefix) == 40, "AlignState layout");
+static_assert(offsetof(AlignState, weight) == 72 && offsetof(AlignState, qlo) == 88 && offsetof(AlignState, qhi) == 96, "AlignState layout");
+static_assert(offsetof(AlignState, scale) == 104 && offsetof(AlignState, bias) == 108 && offsetof(AlignState, mask_count) == 112, "AlignState layout");
+static_assert(offsetof(AlignState, hist) == 116 && offsetof(AlignState, partial) == 8312 && sizeof(AlignState) == 18552, "AlignState layout");
 
 __global__ void align_zero_state(AlignState* st) {
     unsigned* p = reinterpret_cast<unsigned*>(st);
