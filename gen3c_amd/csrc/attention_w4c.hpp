@@ -18,10 +18,15 @@
 //     which takes the 16 rows of one fragment to 16 different values: the ds_read_b128 of a fragment is conflict-free (with w4b's row & 15 it would be
 //     2-way: the rows of a fragment share bit 2). Linear LDS-DMA destination, permuted source chunk, permuted read - all three in this file.
 //     V^T keeps w4b's layout (its 16x16x32 fragment read is conflict-free as it is).
-//   * schedule: region A group = [m0] read wait QK exp QK exp [piece] QK add add QK cvt (pair units 0..15, LDS-DMA pieces on the even groups as in
-//     w4b); region B groups 0..7 carry two pair units each (16..31, needed from group 8 on), groups 8..15 none; the barrier sits in front of group 10.
+//   * schedule: region A group = [m0] read wait QK exp QK exp [piece] QK add add QK cvt (pair units 0..15, the four V^T(t+1) LDS-DMA pieces on groups 8, 10,
+//     12, 14); region B groups 0..7 carry two pair units each (16..31, needed from group 8 on), groups 8..15 none; the barrier sits in front of group 10.
 //     No statement reads a transcendental's result in the next instruction.
+//   * K is fetched one tile ahead, behind the barrier: the four K(t+3) pieces sit in four bare groups >= 10 of region B of tile t and land in the stage of
+//     K(t+1), which region A of tile t has finished with. A piece there shares its group with four MFMAs only, not with a pair unit. K(2) comes from the
+//     prologue; the tail fetches the last tile again; one vmcnt(0) in front of the epilogue drains what the last tiles left in flight.
 constexpr int W4C_D = 6;  // fragment n is read W4C_D groups before the group that consumes it
+constexpr int W4C_KG0 = 12;  // region-B groups W4C_KG0 .. + 3 carry the K pieces (tools/mfma_shape_probe.hip: arms (K10) and (K12) tie; 12..15 had the steadier runs)
+static_assert(W4C_KG0 >= 10 && W4C_KG0 + 4 <= 16, "the K pieces overwrite K(t+1)'s stage: only behind the barrier in front of group 10");
 
 // MIRRORED in tests/test_attn_w4c_layout_cpu.py (kswz, k_off, lds_dma_images = dma_off below, k_frag_addr = kaddr, v_frag_addr = vaddr): the host model
 // proves the layout from hand copies of these formulas, so an edit to w4c_kswz, w4c_k_off, dma_off, kaddr or vaddr must be made there as well.
@@ -81,14 +86,20 @@ G3_DEVICE void w4c_group_qk(uint32_t addr, f32x4& s0, f32x4& s1, f32x4& s2, f32x
 }
 
 // ---- region B group I: [read] wait ; O(d8, q0) += V^T.P0 ; [exp exp] ; O(d8, q1) ; [add add cvt] ; O(d8, q2) ; [exp exp] ; O(d8, q3) ; [add add cvt]
-template <int I, int ROFF, bool READ, int WN, bool UNITS>
-G3_DEVICE void w4c_group_pv(uint32_t addr, const u32x4& pf0, const u32x4& pf1, const u32x4& pf2, const u32x4& pf3, W4cUnit& u1, W4cUnit& u2) {
+//      DMA form (a bare group behind the barrier): [m0] read wait ; O(d8, q0) ; O(d8, q1) ; LDS-DMA piece ; O(d8, q2) ; O(d8, q3)
+template <int I, int ROFF, bool READ, int WN, bool UNITS, bool DMA>
+G3_DEVICE void w4c_group_pv(uint32_t addr, const u32x4& pf0, const u32x4& pf1, const u32x4& pf2, const u32x4& pf3, W4cUnit& u1, W4cUnit& u2, uint32_t m0v, uint32_t voff,
+                            const char* sbase) {
     constexpr int o0 = 16 * (I & 7), o1 = o0 + 4, o2 = o0 + 8, o3 = o0 + 12;  // O^T block (d8, qb) in a[4 (4 d8 + qb) : +3]
     constexpr int fa = W4B_RING0 + 4 * ((16 + I) & 15), ra = W4B_RING0 + 4 * ((16 + I + W4C_D) & 15);
 #define W4C_B_IN [pf0] "v"(pf0), [pf1] "v"(pf1), [pf2] "v"(pf2), [pf3] "v"(pf3), [wn] "n"(WN), [fa] "n"(fa), [o0] "n"(o0), [o1] "n"(o1), [o2] "n"(o2), [o3] "n"(o3)
 #define W4C_B_RD [addr] "v"(addr), [off] "n"(ROFF), [ra] "n"(ra)
     static_assert(!UNITS || READ, "the groups with pair units (0..7) always read ahead");
-    if constexpr (UNITS)
+    static_assert(!DMA || (READ && !UNITS), "a piece sits in a bare group of a tile that has a next one");
+    if constexpr (DMA)
+        asm volatile(W4B_M0 W4C_READ W4_WAIT W4C_PV(0) W4C_PV(1) W4B_DMA W4C_PV(2) W4C_PV(3)
+                     : : W4C_B_IN, W4C_B_RD, [m0v] "s"(m0v), [voff] "v"(voff), [sbase] "s"(sbase) : "memory");
+    else if constexpr (UNITS)
         asm volatile(W4C_READ W4_WAIT W4C_PV(0) W4C_EXPA(1) W4C_EXPB(1) W4C_PV(1) W4C_ADDS(1) W4C_CVT(1) W4C_PV(2) W4C_EXPA(2) W4C_EXPB(2) W4C_PV(3) W4C_ADDS(2) W4C_CVT(2)
                      : W4C_UNIT_OUT(1, u1), W4C_UNIT_OUT(2, u2) : W4C_B_IN, W4C_B_RD, W4C_UNIT_IN(1, u1), W4C_UNIT_IN(2, u2));
     else if constexpr (READ)
@@ -222,7 +233,9 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4c_nm_kernel(At
     });
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) w4c_fence_v(SA[kb][0], SA[kb][1], SA[kb][2], SA[kb][3]);
-    __syncthreads();  // K(0)'s slot is the destination of the first LDS-DMA of the tile loop (K(2)): every wave must be done reading it
+    __syncthreads();  // K(0)'s slot is the destination of the next LDS-DMA (K(2)): every wave must be done reading it
+    // K runs one tile ahead of the loop's own fetches (tile t fetches K(t+3) behind its barrier): K(2) from here, drained and published by tile 0's barrier
+    if (nt > 2) dma_tile_builtin(Kbytes + 2u * k_tile_bytes, dma_off, sK);
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb)
 #pragma unroll
@@ -285,26 +298,29 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4c_nm_kernel(At
                 uput(uc, pk);
             });
         }
-        // ---- region A: S_next = K(t+1).Q^T; pair unit I; LDS-DMA piece I / 2 on the even groups: K(t+2) pieces 0..3 -> stage of K(t), V^T(t+1) pieces 0..3 ->
-        //      stage of V^T(t-1) (as w4b)
+        // ---- region A: S_next = K(t+1).Q^T; pair unit I; the V^T(t+1) LDS-DMA pieces 0..3 on groups 8, 10, 12, 14 -> stage of V^T(t-1) (as w4b). The K pieces
+        //      are not here: a piece beside a pair unit costs the group issue cycles, and K can be fetched in the bare groups of region B (below)
         if constexpr (has_next) {
-            const int t2 = min(t + 2, nt - 1);  // past the end: re-read the last tile (its stage is not consumed any more)
-            const char* kbase = Kbytes + (uint32_t)t2 * k_tile_bytes;
             const char* vbase = Vbytes + v_off_next;
             static_for<0, 16>([&](auto ic) {
                 constexpr int I = decltype(ic)::value, kb = I & 3, qb = (I >> 2) & 3, pa = 2 * (I & 1);
                 using NR = std::integral_constant<int, I + D>;
                 using U = std::integral_constant<int, I>;
-                constexpr bool dma = (I & 1) == 0;
-                constexpr int j = I >> 1;
-                const uint32_t m0v = dma ? (j < 4 ? lds_k0 + (uint32_t)(par * KVB * HD * 2 + 256 * j * 16) : lds_v0 + (uint32_t)((par ^ 1) * HD * KVB * 2 + 256 * (j - 4) * 16)) + (uint32_t)wave * 1024u : 0u;
+                constexpr bool dma = I >= 8 && (I & 1) == 0;
+                constexpr int j = dma ? (I - 8) >> 1 : 0;
+                const uint32_t m0v = dma ? lds_v0 + (uint32_t)((par ^ 1) * HD * KVB * 2 + 256 * j * 16) + (uint32_t)wave * 1024u : 0u;
                 W4cUnit u1{ux(U{}), uy(U{}), ta[I & 1], tb[I & 1], psum[qb][pa], psum[qb][pa + 1], 0u};
-                w4c_group_qk<I, frag_off(NR{}), dma>(frag_addr(NR{}), S_next[kb][0], S_next[kb][1], S_next[kb][2], S_next[kb][3], negm, u1, m0v, dma_off[j], j < 4 ? kbase : vbase);
+                w4c_group_qk<I, frag_off(NR{}), dma>(frag_addr(NR{}), S_next[kb][0], S_next[kb][1], S_next[kb][2], S_next[kb][3], negm, u1, m0v, dma_off[4 + j], vbase);
                 uput(U{}, u1.k);
             });
             v_off_next += (uint32_t)(KVB * 2);
         }
         G3_JITTER(wave + blockIdx.x + 3, t);
+        // K one tile ahead: K(t+3) pieces 0..3 in the bare groups W4C_KG0 .. + 3 of region B, behind the barrier, into the stage of K(t+1). That stage is read in
+        // region A of this tile only; a wave waits for its last K(t+1) fragment in group 15 of region A and LDS returns reads in order, so every wave that has
+        // arrived at the barrier is done with it. The pieces have a whole tile of lead; tile t + 1's vmcnt(0) + barrier drains and publishes them together with
+        // that tile's V^T pieces. Past the end the last tile is fetched again (in bounds; nobody consumes the stage any more).
+        const char* kbase = Kbytes + (uint32_t)min(t + 3, nt - 1) * k_tile_bytes;
         // ---- region B: O^T += V^T(t).P^T, group I: key group G = I >> 3, output block d8 = I & 7; pair units 16 + 2 I, 17 + 2 I in groups 0..7
         static_for<0, 16>([&](auto ic) {
             constexpr int I = decltype(ic)::value, G = I >> 3;
@@ -318,10 +334,14 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4c_nm_kernel(At
                 // every wave has issued its last read of V^T(t) (group 9) and of K(t+1) (region A): drain this wave's LDS-DMA and publish K(t+2) / V^T(t+1).
                 // No operands: the statement shares no register with its neighbours (no pad).
                 if (!(G3_AB_ATTN_ABLATE & 64)) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                G3_JITTER(wave + blockIdx.x + 1, t);  // race screen only: between the barrier and the first piece into the stage the barrier has freed
             }
+            constexpr bool dma = has_next && I >= W4C_KG0 && I < W4C_KG0 + 4;
+            constexpr int j = dma ? I - W4C_KG0 : 0;
+            const uint32_t m0v = dma ? lds_k0 + (uint32_t)((par ^ 1) * KVB * HD * 2 + 256 * j * 16) + (uint32_t)wave * 1024u : 0u;
             W4cUnit u1{ux(U1{}), uy(U1{}), ta[0], tb[0], psum[qb][0], psum[qb][1], 0u};
             W4cUnit u2{ux(U2{}), uy(U2{}), ta[1], tb[1], psum[qb][2], psum[qb][3], 0u};
-            w4c_group_pv<I, frag_off(NR{}), rd, rd ? D : 15 - I, units>(frag_addr(NR{}), pb[G][0], pb[G][1], pb[G][2], pb[G][3], u1, u2);
+            w4c_group_pv<I, frag_off(NR{}), rd, rd ? D : 15 - I, units, dma>(frag_addr(NR{}), pb[G][0], pb[G][1], pb[G][2], pb[G][3], u1, u2, m0v, dma_off[j], kbase);
             if constexpr (units) {
                 uput(U1{}, u1.k);
                 uput(U2{}, u2.k);
@@ -345,6 +365,10 @@ __global__ __launch_bounds__(W4_THREADS, 1) void flash_attn_fwd_w4c_nm_kernel(At
         tile(SA, SB, t, False{}, P0{});
     }
 
+    // The last tile has no barrier and so no vmcnt(0): the pieces that tile nt - 2 issued behind its barrier (a re-fetch of the last K tile, which nobody
+    // reads) may still be in flight. Each wave waits for its own here, so no LDS-DMA write can land after the workgroup has given its LDS back (a workgroup's
+    // LDS is released when its last wave ends, and a wave's pieces are counted in that wave's vmcnt alone).
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     // ---- epilogue: a query's row sum is spread over the four lanes l15 + 16 g; O^T block (d8, qb) register r = output dim 16 d8 + 4 g + r of query 16 qb + l15
     w4b_fence_acc();
     static_for<0, 4>([&](auto qc) {

@@ -9,6 +9,12 @@
 //      Values are NOT meaningful (fragments are read lane-linear, LDS-DMA lands while other waves read): only the instruction mix, the
 //      dependency distances and the operand statistics are the tile's. s_memtime / s_memrealtime are stamped once around the loop and go
 //      to a buffer of their own (diagnostic program only).
+//      The 16x16x32 body takes a piece-placement parameter (where its eight LDS-DMA pieces sit), three arms:
+//        (A) all eight alone in the V^T groups 8..15, the barrier in front of group 8: the body this probe first measured;
+//        (P) the product's placement (attention_w4c.hpp before the K-ahead change): piece j / 2 beside the pair unit of even K group j, barrier in
+//            front of V^T group 10, no piece in region B;
+//        (K) K one tile ahead: the four K pieces on four bare V^T groups behind the barrier (10..13 or 12..15), the four V^T pieces beside the pair
+//            units of K groups 8, 10, 12, 14.
 // build: hipcc --offload-arch=gfx950 -O3 tools/mfma_shape_probe.hip -o tools/bin/mfma_shape_probe ; run on the GPU box, record the output
 // in profiles/mfma_shape_probe.txt.
 #include <hip/hip_runtime.h>
@@ -184,25 +190,31 @@ __device__ __forceinline__ void a32_step_pv(uint32_t addr, const u32x4& pf0, con
 }
 
 // ---- arm 16: four MFMAs per fragment. Region A group I (key block I & 3, k-step I >> 2): read wait QK(q0) exp QK(q1) exp QK(q2) add add QK(q3) cvt;
-// region B group I (k-step I >> 3, output block I & 7): groups 0..7 carry two pair units, groups 8..15 one LDS-DMA piece and no unit
+// region B group I (k-step I >> 3, output block I & 7): groups 0..7 carry two pair units, groups 8..15 no unit and, by placement, one LDS-DMA piece
 #define A16_QK(h) "v_mfma_f32_16x16x32_bf16 %[s" #h "], a[%c[fa]:%c[fa]+3], a[%c[q" #h "]:%c[q" #h "]+3], %[s" #h "]\n\t"
 #define A16_QK0(h) "v_mfma_f32_16x16x32_bf16 %[s" #h "], a[%c[fa]:%c[fa]+3], a[%c[q" #h "]:%c[q" #h "]+3], 0\n\t"
 #define A16_PV(h) "v_mfma_f32_16x16x32_bf16 a[%c[o" #h "]:%c[o" #h "]+3], a[%c[fa]:%c[fa]+3], %[pf" #h "], a[%c[o" #h "]:%c[o" #h "]+3]\n\t"
 
-template <int I, int ROFF>
-__device__ __forceinline__ void a16_group_qk(uint32_t addr, f32x4& s0, f32x4& s1, f32x4& s2, f32x4& s3, Unit& u1) {
+template <int I, int ROFF, bool DMA>
+__device__ __forceinline__ void a16_group_qk(uint32_t addr, f32x4& s0, f32x4& s1, f32x4& s2, f32x4& s3, Unit& u1, uint32_t m0v, uint32_t voff, const char* sbase) {
     constexpr int ks = I >> 2, q0 = QBASE + 4 * ks, q1 = q0 + 16, q2 = q0 + 32, q3 = q0 + 48;
     constexpr int fa = RING0 + 4 * (I & 15), ra = RING0 + 4 * ((I + RD) & 15);
 #define A16_A_IN P_RD_IN, P_UNIT_IN(1, u1), [q0] "n"(q0), [q1] "n"(q1), [q2] "n"(q2), [q3] "n"(q3)
-    if constexpr (ks == 0)
+    if constexpr (ks == 0 && DMA)  // the product's DMA group: [m0] read wait QK exp QK exp [piece] QK add add QK cvt
+        asm volatile(P_M0 P_READ P_WAIT A16_QK0(0) P_EXPA(1) A16_QK0(1) P_EXPB(1) P_DMA A16_QK0(2) P_ADDS(1) A16_QK0(3) P_CVT(1)
+                     : P_UNIT_OUT(1, u1), [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [s3] "=&v"(s3) : A16_A_IN, P_DMA_IN : "memory");
+    else if constexpr (ks == 0)
         asm volatile(P_READ P_WAIT A16_QK0(0) P_EXPA(1) A16_QK0(1) P_EXPB(1) A16_QK0(2) P_ADDS(1) A16_QK0(3) P_CVT(1)
                      : P_UNIT_OUT(1, u1), [s0] "=&v"(s0), [s1] "=&v"(s1), [s2] "=&v"(s2), [s3] "=&v"(s3) : A16_A_IN);
+    else if constexpr (DMA)
+        asm volatile(P_M0 P_READ P_WAIT A16_QK(0) P_EXPA(1) A16_QK(1) P_EXPB(1) P_DMA A16_QK(2) P_ADDS(1) A16_QK(3) P_CVT(1)
+                     : P_UNIT_OUT(1, u1), [s0] "+v"(s0), [s1] "+v"(s1), [s2] "+v"(s2), [s3] "+v"(s3) : A16_A_IN, P_DMA_IN : "memory");
     else
         asm volatile(P_READ P_WAIT A16_QK(0) P_EXPA(1) A16_QK(1) P_EXPB(1) A16_QK(2) P_ADDS(1) A16_QK(3) P_CVT(1)
                      : P_UNIT_OUT(1, u1), [s0] "+v"(s0), [s1] "+v"(s1), [s2] "+v"(s2), [s3] "+v"(s3) : A16_A_IN);
 #undef A16_A_IN
 }
-template <int I, int ROFF, bool UNITS>
+template <int I, int ROFF, bool UNITS, bool DMA>
 __device__ __forceinline__ void a16_group_pv(uint32_t addr, const u32x4& pf0, const u32x4& pf1, const u32x4& pf2, const u32x4& pf3, Unit& u1, Unit& u2, uint32_t m0v,
                                              uint32_t voff, const char* sbase) {
     constexpr int D = I & 7, o0 = 16 * D, o1 = o0 + 4, o2 = o0 + 8, o3 = o0 + 12;
@@ -211,8 +223,10 @@ __device__ __forceinline__ void a16_group_pv(uint32_t addr, const u32x4& pf0, co
     if constexpr (UNITS)
         asm volatile(P_READ P_WAIT A16_PV(0) P_EXPA(1) P_EXPB(1) A16_PV(1) P_ADDS(1) P_CVT(1) A16_PV(2) P_EXPA(2) P_EXPB(2) A16_PV(3) P_ADDS(2) P_CVT(2)
                      : P_UNIT_OUT(1, u1), P_UNIT_OUT(2, u2) : A16_B_IN, P_UNIT_IN(1, u1), P_UNIT_IN(2, u2));
-    else
+    else if constexpr (DMA)
         asm volatile(P_M0 P_READ P_WAIT A16_PV(0) A16_PV(1) P_DMA A16_PV(2) A16_PV(3) : : A16_B_IN, P_DMA_IN : "memory");
+    else
+        asm volatile(P_READ P_WAIT A16_PV(0) A16_PV(1) A16_PV(2) A16_PV(3) : : A16_B_IN);
 #undef A16_B_IN
 }
 
@@ -220,8 +234,18 @@ struct Stamps {
     unsigned long long c0, c1, r0, r1;
 };
 
-// SHAPE 32: v_mfma_f32_32x32x16_bf16 body; SHAPE 16: v_mfma_f32_16x16x32_bf16 body. `tiles` even.
-template <int SHAPE>
+// Piece placement of the 16x16x32 body. piece_a(I) / piece_b(I): the piece (0..3 K, 4..7 V^T) that K group I / V^T group I carries, -1 for none.
+enum Place { PLACE_A = 0, PLACE_P = 1, PLACE_K10 = 2, PLACE_K12 = 3 };
+template <int PLACE> constexpr int piece_a(int I) {
+    return PLACE == PLACE_P ? ((I & 1) ? -1 : I >> 1) : (PLACE == PLACE_K10 || PLACE == PLACE_K12) ? ((I >= 8 && !(I & 1)) ? 4 + ((I - 8) >> 1) : -1) : -1;
+}
+template <int PLACE> constexpr int piece_b(int I) {
+    return PLACE == PLACE_A ? (I >= 8 ? I & 7 : -1) : PLACE == PLACE_K10 ? ((I >= 10 && I < 14) ? I - 10 : -1) : PLACE == PLACE_K12 ? (I >= 12 ? I - 12 : -1) : -1;
+}
+template <int PLACE> constexpr int barrier_group() { return PLACE == PLACE_A ? 8 : 10; }  // the product's barrier sits in front of V^T group 10
+
+// SHAPE 32: v_mfma_f32_32x32x16_bf16 body; SHAPE 16: v_mfma_f32_16x16x32_bf16 body with piece placement PLACE. `tiles` even.
+template <int SHAPE, int PLACE>
 __global__ __launch_bounds__(256, 1) void tile_kernel(const char* __restrict__ src, const uint32_t* __restrict__ qsrc, const float* __restrict__ s_init, int tiles,
                                                       Stamps* __restrict__ stamps) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -270,7 +294,9 @@ __global__ __launch_bounds__(256, 1) void tile_kernel(const char* __restrict__ s
         // fragment n of the tile: K fragments 0..15, V^T fragments 16..31, the next tile's K fragments 32.. (read across the barrier)
         auto frag_off = [](auto nc) constexpr { constexpr int n = decltype(nc)::value; return n < 16 ? KS + 1024 * n : n < 32 ? VS + 1024 * (n - 16) : KSN + 1024 * (n - 32); };
         const char* tbase = src + (size_t)((t + 2) & (SRC_TILES - 1)) * (2 * KV_STAGE);  // wave-uniform source of this tile's eight pieces
-        auto piece_m0 = [&](int j) -> uint32_t { return lds0 + (uint32_t)((j < 4 ? par * KV_STAGE : 2 * KV_STAGE + (par ^ 1) * KV_STAGE) + (j & 3) * 4096) + (uint32_t)wave * 1024u; };
+        // destination of piece j: K(t+2) -> the stage of K(t), V^T(t+1) -> the stage of V^T(t-1); in the K-ahead arms K(t+3) -> the stage of K(t+1)
+        constexpr int KDST = (SHAPE == 16 && (PLACE == PLACE_K10 || PLACE == PLACE_K12)) ? (par ^ 1) * KV_STAGE : par * KV_STAGE;
+        auto piece_m0 = [&](int j) -> uint32_t { return lds0 + (uint32_t)((j < 4 ? KDST : 2 * KV_STAGE + (par ^ 1) * KV_STAGE) + (j & 3) * 4096) + (uint32_t)wave * 1024u; };
         u32x4 pb[2][4];
         if constexpr (SHAPE == 32) {
             // S[2 h + mb]: half h, 32-key block mb. Pair unit u in consumption order: slice sl = u >> 3, half h = (u >> 2) & 1, pair q = u & 3
@@ -306,29 +332,30 @@ __global__ __launch_bounds__(256, 1) void tile_kernel(const char* __restrict__ s
             auto uy = [&](auto uc) -> float { constexpr int u = decltype(uc)::value; return S_cur[2 * (u >> 4) + ((u >> 1) & 1)][4 * ((u >> 2) & 3) + 2 * (u & 1) + 1]; };
             auto uput = [&](auto uc, uint32_t pk) { constexpr int u = decltype(uc)::value; pb[u >> 4][(u >> 2) & 3][2 * ((u >> 1) & 1) + (u & 1)] = pk; };
             static_for<0, 16>([&](auto ic) {  // region A: units 0..15, one per group
-                constexpr int I = decltype(ic)::value, kb = I & 3;
+                constexpr int I = decltype(ic)::value, kb = I & 3, pj = piece_a<PLACE>(I), j = pj < 0 ? 0 : pj;
                 using U = std::integral_constant<int, I>;
                 using NR = std::integral_constant<int, I + RD>;
                 Unit u1{ux(U{}), uy(U{}), ta[I & 1], tb[I & 1], psum[2 * (I & 1)], psum[2 * (I & 1) + 1], 0u};
                 // the four query blocks of key block kb are the four quarters of S_next[kb]
                 f32x4 q0 = __builtin_shufflevector(S_next[kb], S_next[kb], 0, 1, 2, 3), q1 = __builtin_shufflevector(S_next[kb], S_next[kb], 4, 5, 6, 7);
                 f32x4 q2 = __builtin_shufflevector(S_next[kb], S_next[kb], 8, 9, 10, 11), q3 = __builtin_shufflevector(S_next[kb], S_next[kb], 12, 13, 14, 15);
-                a16_group_qk<I, frag_off(NR{})>(addr, q0, q1, q2, q3, u1);
+                a16_group_qk<I, frag_off(NR{}), (pj >= 0)>(addr, q0, q1, q2, q3, u1, pj >= 0 ? piece_m0(j) : 0u, dma_off[j], tbase);
                 S_next[kb] = __builtin_shufflevector(__builtin_shufflevector(q0, q1, 0, 1, 2, 3, 4, 5, 6, 7), __builtin_shufflevector(q2, q3, 0, 1, 2, 3, 4, 5, 6, 7), 0, 1, 2, 3, 4, 5, 6,
                                                      7, 8, 9, 10, 11, 12, 13, 14, 15);
                 uput(U{}, u1.k);
             });
-            static_for<0, 16>([&](auto ic) {  // region B: units 16..31 two per group in groups 0..7; the barrier and the pieces in groups 8..15
+            static_for<0, 16>([&](auto ic) {  // region B: units 16..31 two per group in groups 0..7; the barrier and, by placement, pieces in groups 8..15
                 constexpr int I = decltype(ic)::value;
                 constexpr bool units = I < 8;
                 using U1 = std::integral_constant<int, units ? 16 + 2 * I : 16>;
                 using U2 = std::integral_constant<int, units ? 17 + 2 * I : 17>;
                 using NR = std::integral_constant<int, 16 + I + RD>;
-                constexpr int j = I & 7;
-                if constexpr (I == 8) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                constexpr int pj = piece_b<PLACE>(I), j = pj < 0 ? 0 : pj;
+                static_assert(pj < 0 || !units, "a group with pair units carries no piece");
+                if constexpr (I == barrier_group<PLACE>()) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
                 Unit u1{ux(U1{}), uy(U1{}), ta[0], tb[0], psum[0], psum[1], 0u};
                 Unit u2{ux(U2{}), uy(U2{}), ta[1], tb[1], psum[2], psum[3], 0u};
-                a16_group_pv<I, frag_off(NR{}), units>(addr, pb[I >> 3][0], pb[I >> 3][1], pb[I >> 3][2], pb[I >> 3][3], u1, u2, units ? 0u : piece_m0(j), dma_off[j], tbase);
+                a16_group_pv<I, frag_off(NR{}), units, (pj >= 0)>(addr, pb[I >> 3][0], pb[I >> 3][1], pb[I >> 3][2], pb[I >> 3][3], u1, u2, pj >= 0 ? piece_m0(j) : 0u, dma_off[j], tbase);
                 if constexpr (units) {
                     uput(U1{}, u1.k);
                     uput(U2{}, u2.k);
@@ -449,66 +476,80 @@ static void run_wall(int tiles) {
     CHECK(hipMemcpy(dsrc, hsrc.data(), src_bytes, hipMemcpyHostToDevice));
     CHECK(hipMemcpy(dq, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
     CHECK(hipMemcpy(ds, hs.data(), hs.size() * 4, hipMemcpyHostToDevice));
-    const int ROUNDS = 3;
-    Stamps* dst[2][ROUNDS];
+    const int ROUNDS = 3, ARMS = 5;  // arm 0: 32x32x16; 1..4: 16x16x32 with placement (A), (P), (K) on groups 10..13, (K) on groups 12..15
+    const char* names[ARMS] = {"32x32x16", "16x16x32", "16 (P)", "16 (K10)", "16 (K12)"};
+    Stamps* dst[ARMS][ROUNDS];
     Stamps* dwarm;
     CHECK(hipMalloc(&dwarm, 1024 * sizeof(Stamps)));
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < ARMS; ++a)
         for (int r = 0; r < ROUNDS; ++r) CHECK(hipMalloc(&dst[a][r], 1024 * sizeof(Stamps)));
-    CHECK(hipFuncSetAttribute((const void*)tile_kernel<32>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    CHECK(hipFuncSetAttribute((const void*)tile_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-    auto launch = [&](int arm, Stamps* st) {
-        if (arm == 0) hipLaunchKernelGGL(tile_kernel<32>, dim3(WGS), dim3(256), LDS, 0, dsrc, dq, ds, tiles, st);
-        else hipLaunchKernelGGL(tile_kernel<16>, dim3(WGS), dim3(256), LDS, 0, dsrc, dq, ds, tiles, st);
-    };
-    hipEvent_t e0, e1, ev[2][ROUNDS][2];
+    using Kernel = void (*)(const char*, const uint32_t*, const float*, int, Stamps*);
+    Kernel kernels[ARMS] = {tile_kernel<32, PLACE_A>, tile_kernel<16, PLACE_A>, tile_kernel<16, PLACE_P>, tile_kernel<16, PLACE_K10>, tile_kernel<16, PLACE_K12>};
+    for (int a = 0; a < ARMS; ++a) CHECK(hipFuncSetAttribute((const void*)kernels[a], hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
+    auto launch = [&](int arm, Stamps* st) { hipLaunchKernelGGL(kernels[arm], dim3(WGS), dim3(256), LDS, 0, dsrc, dq, ds, tiles, st); };
+    hipEvent_t e0, e1, ev[ARMS][ROUNDS][2];
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
-    for (int a = 0; a < 2; ++a)
+    for (int a = 0; a < ARMS; ++a)
         for (int r = 0; r < ROUNDS; ++r) {
             CHECK(hipEventCreate(&ev[a][r][0]));
             CHECK(hipEventCreate(&ev[a][r][1]));
         }
     // one launch per arm to size the warm-up, then >= 2 s of back-to-back launches, then the timed launches in the same queue without a gap
-    float ms1[2];
-    for (int a = 0; a < 2; ++a) {
+    float ms1[ARMS], ms_all = 0.f;
+    for (int a = 0; a < ARMS; ++a) {
         CHECK(hipEventRecord(e0, 0));
         launch(a, dwarm);
         CHECK(hipEventRecord(e1, 0));
         CHECK(hipEventSynchronize(e1));
         CHECK(hipEventElapsedTime(&ms1[a], e0, e1));
+        ms_all += ms1[a];
     }
-    const int warm = (int)(2200.f / (ms1[0] + ms1[1])) + 1;
-    for (int i = 0; i < warm; ++i) launch(0, dwarm), launch(1, dwarm);
+    const int warm = (int)(2200.f / ms_all) + 1;
+    for (int i = 0; i < warm; ++i)
+        for (int a = 0; a < ARMS; ++a) launch(a, dwarm);
     for (int r = 0; r < ROUNDS; ++r)
-        for (int a = 0; a < 2; ++a) {
+        for (int a = 0; a < ARMS; ++a) {
             CHECK(hipEventRecord(ev[a][r][0], 0));
             launch(a, dst[a][r]);
             CHECK(hipEventRecord(ev[a][r][1], 0));
         }
     CHECK(hipDeviceSynchronize());
-    printf("wall: %d tiles per wave and launch, 256 workgroups x 4 waves, warm-up %d launch pairs (first launches %.2f / %.2f ms)\n", tiles, warm, ms1[0], ms1[1]);
-    ArmResult res[2][ROUNDS];
+    printf("wall: %d tiles per wave and launch, 256 workgroups x 4 waves, warm-up %d rounds of the %d arms (first launches", tiles, warm, ARMS);
+    for (int a = 0; a < ARMS; ++a) printf(" %.2f", ms1[a]);
+    printf(" ms)\n  arms: 16x16x32 = (A) all eight pieces in V^T groups 8..15; (P) the product's: piece j/2 on even K group j; (K10) / (K12) K pieces on V^T groups 10..13 /\n"
+           "  12..15 behind the barrier, V^T pieces on K groups 8, 10, 12, 14\n");
+    ArmResult res[ARMS][ROUNDS];
     for (int r = 0; r < ROUNDS; ++r)
-        for (int a = 0; a < 2; ++a) {
+        for (int a = 0; a < ARMS; ++a) {
             float ms;
             CHECK(hipEventElapsedTime(&ms, ev[a][r][0], ev[a][r][1]));
             res[a][r] = read_stamps(dst[a][r], ms, tiles);
             const double flop = (double)WGS * 4 * tiles * 64.0 * 2 * 32 * 32 * 16;
-            printf("  round %d  %-9s  wall %8.3f ms  %7.1f TFLOP/s  tile %7.1f cycles  in-kernel clock %.3f GHz\n", r, a ? "16x16x32" : "32x32x16", ms, flop / ms / 1e9, res[a][r].tile_cycles,
+            printf("  round %d  %-9s  wall %8.3f ms  %7.1f TFLOP/s  tile %7.1f cycles  in-kernel clock %.3f GHz\n", r, names[a], ms, flop / ms / 1e9, res[a][r].tile_cycles,
                    res[a][r].clock_ghz);
         }
-    float lo[2] = {1e30f, 1e30f}, hi[2] = {0.f, 0.f}, med[2];
-    for (int a = 0; a < 2; ++a) {
+    float lo[ARMS], hi[ARMS], med[ARMS];
+    for (int a = 0; a < ARMS; ++a) {
         float v[ROUNDS];
+        lo[a] = 1e30f, hi[a] = 0.f;
         for (int r = 0; r < ROUNDS; ++r) v[r] = res[a][r].ms, lo[a] = std::min(lo[a], v[r]), hi[a] = std::max(hi[a], v[r]);
         std::sort(v, v + ROUNDS);
         med[a] = v[ROUNDS / 2];
+        printf("  %-9s: median %.3f ms, spread between its runs %.2f %%\n", names[a], med[a], 100.f * (hi[a] - lo[a]) / med[a]);
     }
     const float spread = (hi[0] - lo[0]) / med[0], gain = med[0] / med[1] - 1.f;
-    printf("  32x32x16: median %.3f ms, spread between its runs %.2f %%\n  16x16x32: median %.3f ms, spread %.2f %%\n", med[0], 100.f * spread, med[1], 100.f * (hi[1] - lo[1]) / med[1]);
     printf("  16x16x32 against 32x32x16 by wall: %+.2f %% (go needs more than %.2f %% = twice the spread, and at least 5 %%): %s\n", 100.f * gain, 200.f * spread,
            (gain > 2.f * spread && gain >= 0.05f) ? "GO" : "NO-GO");
+    // piece placement: an arm beats another by wall by more than twice the spread between the slower arm's own runs
+    auto verdict = [&](int better, int base, const char* what) {
+        const float sp = (hi[base] - lo[base]) / med[base], gn = med[base] / med[better] - 1.f;
+        printf("  %s: %s against %s by wall %+.2f %% (go needs more than %.2f %% = twice the spread of %s): %s\n", what, names[better], names[base], 100.f * gn, 200.f * sp, names[base],
+               gn > 2.f * sp ? "GO" : "NO-GO");
+    };
+    verdict(3, 2, "K one tile ahead");
+    verdict(4, 2, "K one tile ahead");
+    verdict(1, med[3] < med[4] ? 3 : 4, "V^T ahead as well (third V^T stage)");
 }
 
 int main(int argc, char** argv) {

@@ -165,8 +165,9 @@ for (Sl, nseg, rank, H) in [(7040, 8, 3, 4), (256, 3, 1, 2), (64, 4, 1, 2)] if (
     del q, k, v, vt
 
 # ---- the no-max kernel on 16x16x32 MFMAs (g3_self_attn_fwd_bounded16_bf16, flash_attn_fwd_w4c_nm_kernel): the DiT step's launch, an odd tile count with a
-# ragged last query block, a single tile; q, k RMS-normalised per head so that the bound holds
-for (Sq, Skv, H) in [(56320, 56320, 4), (320, 192, 2), (256, 64, 8)] if (ONLY_W4C or not ONLY_MX) else []:
+# ragged last query block, a single tile, and 4 / 5 / 6 tiles (K one tile ahead: the first K(3) fetched behind a barrier, both loop exits after a steady pair;
+# the jitter build also sleeps between that barrier and the first piece into the stage it freed); q, k RMS-normalised per head so that the bound holds
+for (Sq, Skv, H) in [(56320, 56320, 4), (320, 192, 2), (256, 64, 8), (320, 256, 2), (320, 320, 2), (320, 384, 2)] if (ONLY_W4C or not ONLY_MX) else []:
     rms = lambda x: (x.view(x.shape[0], H, 128) * torch.rsqrt(x.view(x.shape[0], H, 128).pow(2).mean(-1, keepdim=True))).reshape(x.shape[0], H * 128)
     q = rms(torch.randn(Sq, H * 128, device=dev, generator=g)).to(torch.bfloat16)
     k = rms(torch.randn(Skv, H * 128, device=dev, generator=g)).to(torch.bfloat16)
