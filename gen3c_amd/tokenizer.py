@@ -263,6 +263,10 @@ class CausalVideoTokenizerNet(torch.nn.Module):
         main = torch.cuda.current_stream(x.device)
         streams = [main] + [self._side_stream(i, x.device) for i in range(ns - 1)]
         bufs = [(torch.zeros((HW, ldp), dtype=bf16, device=x.device), torch.zeros((C, ldp), dtype=bf16, device=x.device)) for _ in range(ns)]
+        # The GEMM stores 4 columns at a time (N % 4 == 0): at HW % 4 != 0 the scores are taken against k with zero rows up to the next multiple of
+        # 4 - the extra columns get q . 0 = 0, what the padding held already, and the softmax (n = HW) leaves them alone.
+        n4 = ops.ceil_to(HW, 4)
+        kpads = [torch.zeros((n4, C), dtype=bf16, device=x.device) for _ in range(ns)] if n4 != HW else None
         ready = main.record_event()  # q, k, v, o and the zeroed buffers exist
         for f in range(T):
             st = streams[f % ns]
@@ -270,7 +274,11 @@ class CausalVideoTokenizerNet(torch.nn.Module):
             with torch.cuda.stream(st):
                 if f < ns and st is not main:
                     st.wait_event(ready)
-                ops.gemm_nt(q[f], k[f], out=scores[:, :HW])
+                if kpads is None:
+                    ops.gemm_nt(q[f], k[f], out=scores[:, :HW])
+                else:
+                    kpads[f % ns][:HW].copy_(k[f])
+                    ops.gemm_nt(q[f], kpads[f % ns], out=scores[:, :n4])
                 _lib.check(lib.g3_softmax_rows_bf16(_ptr(scores), ldp, HW, HW, float(C) ** -0.5, _st()), "g3_softmax_rows_bf16")
                 _lib.check(lib.g3_transpose2d_bf16(_ptr(v[f]), C, _ptr(vT), ldp, HW, C, _st()), "g3_transpose2d_bf16")
                 ops.gemm_nt(scores, vT, out=o[f])  # K = ldp (zero padded columns contribute nothing)

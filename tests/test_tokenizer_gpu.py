@@ -3,7 +3,9 @@
 (channels=64 -> LDS-DMA conv path).
 
 Stated tolerance: bf16 activations through ~45 layers (GroupNorm renormalises every block): relative L2 <= 3e-2 on the
-latent and <= 4e-2 on the reconstruction against the fp32 evaluation of the same bf16 weights."""
+latent and <= 4e-2 on the reconstruction against the fp32 evaluation of the same bf16 weights.
+
+The attention kernels (d = 512 spatial, temporal, row softmax) are pinned element by element in tests/test_tokenizer_attn_kernels_gpu.py."""
 import pytest
 import torch
 
