@@ -3,7 +3,8 @@
 // Format (MXFP8 linears): a block is 32 consecutive elements along K of one row. Its shared exponent is
 //   X = floor(log2(amax_block)) - 8, stored as the E8M0 byte X + 127 clamped to 0..254 (all-zero block: byte 127, elements 0),
 // and every element is RNE(clamp(x / 2^X, -448, 448)) as OCP e4m3fn (not the MI300 fnuz variant). amax / 2^X lies in [256, 512), so the clamp
-// matters and no element is ever flushed to more than the format's own subnormal step.
+// matters and no element is ever flushed to more than the format's own subnormal step. A block that holds a NaN or an infinity leaves as the
+// E8M0 NaN - byte 0xFF, zero elements -, which the scaled matrix core turns into NaN in every output that consumes the block (mx_quant.hpp).
 //
 // GEMM: C[M,N] = epi( sum_k (a 2^Xa)(w 2^Xw) ) on v_mfma_scale_f32_32x32x64_f8f6f4, which runs e4m3 operands at twice the bf16 rate and applies
 // the block scales inside the matrix core. The structure is the bf16 kernels' direct-to-LDS form (gemm.hip, gemm_bf16_nt_kernel) at the same
@@ -48,18 +49,15 @@ __global__ __launch_bounds__(256) void quant_mxfp8_kernel(const bf16_t* __restri
     bf16x8 v = zero_bf16x8();
     if (live) v = load_bf16x8(x + (int64_t)row * ldx + 8 * c8);
     float f[8];
-    float amax = 0.0f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        f[e] = (float)v[e];
-        amax = fmaxf(amax, fabsf(f[e]));
-    }
-    amax = fmaxf(amax, wave_xor_f32(amax, 1));
-    amax = fmaxf(amax, wave_xor_f32(amax, 2));
+    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+    const uint32_t abits = mx_quad_amax_bits(f);
     if (!live) return;
-    const int X = mx_block_exponent(amax);
+    const float amax = __uint_as_float(abits);
+    const bool finite = abits < MX_INF_BITS;  // a NaN or an infinity in the block: the E8M0 NaN and zero codes (mx_quant.hpp)
+    const int X = finite ? mx_block_exponent(amax) : MX_X_NAN;
     u32x2 o = {0u, 0u};
-    if (amax != 0.0f) {
+    if (finite && amax != 0.0f) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float y = fminf(fmaxf(ldexpf(f[e], -X), -448.0f), 448.0f);
@@ -393,9 +391,10 @@ extern "C" const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int 
 // Storage: q [M][3K/4] bytes, block b of a row = bytes [24 b, 24 b + 24), element i = the 6-bit code at bits [6 i, 6 i + 6) of that 192-bit
 // little-endian string; scales [M][K/32] as for MXFP8.
 //
-// Scaled-MFMA lane maps (32x32x64, both operands e2m3). Not probed k by k as the 8-bit map was: the kernel was written to the map below and
-// it is confirmed by the exact test of tests/test_mxfp6_gpu.py (e2m3-exact data, per-(row, block) scales on both operands, asymmetric W, bf16
-// output bitwise the RNE of the fp64 result), which any other k order, bit order or scale assignment fails:
+// Scaled-MFMA lane maps (32x32x64, both operands e2m3). The kernel was written to the map below; it is probed k by k, code by code and scale
+// byte by scale byte by tests/test_mx_kernels_gpu.py (weight row n one-hot at k = n under scale bytes 127 +- 40 on both operands, up to
+// K = 16384; bf16 output bitwise the closed form) and by the exact test of tests/test_mxfp6_gpu.py, which any other k order, bit order or
+// scale assignment fails:
 // the operand is 6 VGPRs = 192 bits. Lane l = (r = l & 31, h = l >> 5) holds row r, k = 32 h + i of the 64-deep step in bits [6 i, 6 i + 6) of
 // its 192-bit little-endian operand - unlike the 8-bit map a lane half holds ONE contiguous scale block, which is exactly one stored 24-byte block,
 // so no repacking is needed. The scale of that block is the byte op_sel names in the lane's OWN scale VGPR. Each lane keeps the scale dword of
@@ -443,17 +442,14 @@ __global__ __launch_bounds__(256) void quant_mxfp6_kernel(const bf16_t* __restri
     bf16x8 v = zero_bf16x8();
     if (live) v = load_bf16x8(x + (int64_t)row * ldx + 8 * c8);
     float f[8];
-    float amax = 0.0f;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        f[e] = (float)v[e];
-        amax = fmaxf(amax, fabsf(f[e]));
-    }
-    amax = fmaxf(amax, wave_xor_f32(amax, 1));
-    amax = fmaxf(amax, wave_xor_f32(amax, 2));
-    const int X = mx6_block_exponent(amax);
+    for (int e = 0; e < 8; ++e) f[e] = (float)v[e];
+    const uint32_t abits = mx_quad_amax_bits(f);
+    const float amax = __uint_as_float(abits);
+    const bool finite = abits < MX_INF_BITS;  // a NaN or an infinity in the block: the E8M0 NaN and zero codes (mx_quant.hpp)
+    const int X = finite ? mx6_block_exponent(amax) : MX_X_NAN;
     uint32_t lo = 0u, hi = 0u;
-    if (amax != 0.0f) {
+    if (finite && amax != 0.0f) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = ldexpf(f[e], -X);
         mx6_pack8(f, lo, hi);

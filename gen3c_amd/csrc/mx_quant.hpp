@@ -15,6 +15,23 @@ G3_DEVICE uint32_t e4m3_rne(float y) {
     return ((b >> 24) & 0x80) | (uint32_t)((e + 6) * 8 + (int)q);
 }
 
+// Non-finite rule ("Non-finite inputs"; both formats): a block that holds a NaN or an infinity leaves as the E8M0 NaN - scale byte 0xFF, X = MX_X_NAN -
+// with zero codes, which the scaled matrix core turns into NaN in every output that consumes the block, as a bf16 linear would carry it.
+constexpr int MX_X_NAN = 128;
+constexpr uint32_t MX_INF_BITS = 0x7f800000u;
+
+// The block amax of a lane quad as the BIT PATTERN of |x|, through the quad's two shuffles. For non-negative floats the unsigned order of the
+// bits is the order of the values, so on finite data this is fmaxf's amax bit for bit; an infinity or a NaN (which fmaxf would drop) is the
+// largest pattern of all and comes out >= MX_INF_BITS. A dead lane passes zeros and leaves its quad's amax alone.
+G3_DEVICE uint32_t mx_quad_amax_bits(const float (&f)[8]) {
+    uint32_t m = 0u;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m = max(m, __float_as_uint(f[e]) & 0x7fffffffu);
+    m = max(m, (uint32_t)__shfl_xor((int)m, 1, 64));
+    m = max(m, (uint32_t)__shfl_xor((int)m, 2, 64));
+    return m;
+}
+
 // Shared exponent X of a block (E8M0 byte = X + 127). amax is a finite non-negative bf16 value widened to fp32.
 G3_DEVICE int mx_block_exponent(float amax) {
     if (amax == 0.0f) return 0;
@@ -24,17 +41,15 @@ G3_DEVICE int mx_block_exponent(float amax) {
 
 // A producer's lane holds 8 consecutive elements f[0..7] (bf16 values widened to fp32) of a 32-element block whose other 24 sit in the lanes
 // lane ^ 1, lane ^ 2, lane ^ 3: the block amax over the lane quad, then this lane's 8 e4m3 bytes (returned) and the block's exponent X (the quad's
-// first lane stores the byte X + 127). The arithmetic of quant_mxfp8_kernel, statement for statement. EVERY lane of the wave has to call this
-// (the shuffles); a lane without data passes zeros, which leaves its quad's amax alone.
+// first lane stores the byte X + 127; a block with a NaN or an infinity: X = MX_X_NAN, zero codes). The arithmetic of quant_mxfp8_kernel,
+// statement for statement. EVERY lane of the wave has to call this (the shuffles); a lane without data passes zeros, which leaves its quad's amax alone.
 G3_DEVICE u32x2 mx_quant_quad(const float (&f)[8], int& X) {
-    float amax = 0.0f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
-    amax = fmaxf(amax, wave_xor_f32(amax, 1));
-    amax = fmaxf(amax, wave_xor_f32(amax, 2));
-    X = mx_block_exponent(amax);
+    const uint32_t abits = mx_quad_amax_bits(f);
+    const float amax = __uint_as_float(abits);
+    const bool finite = abits < MX_INF_BITS;
+    X = finite ? mx_block_exponent(amax) : MX_X_NAN;
     u32x2 o = {0u, 0u};
-    if (amax != 0.0f) {
+    if (finite && amax != 0.0f) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const float y = fminf(fmaxf(ldexpf(f[e], -X), -448.0f), 448.0f);

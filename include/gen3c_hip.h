@@ -70,7 +70,8 @@ const char* g3_gemm_kernel_name(int M, int N, int K, int epilogue);
 /* ---- opt-in MXFP8 DiT linears (OCP MX v1.0, e4m3fn elements; outside the bf16 parity statement, DESIGN.md "MXFP8 linears") -------------
  * x [M][ldx] bf16 -> q [M][ldq] e4m3fn bytes + scales [M][lds] E8M0 bytes, one per 32 consecutive k of a row:
  *   X = floor(log2(amax of the block)) - 8, byte X + 127 clamped to 0..254; q = RNE(clamp(x / 2^X, -448, 448)); an all-zero block gets byte 127
- *   and zero elements. Needs K % 32 == 0, ldx and ldq multiples of 8 (>= K), lds >= K/32; x 16-byte, q 8-byte aligned. */
+ *   and zero elements; a block that holds a NaN or an infinity gets byte 0xFF (the E8M0 NaN) and zero elements, and every output of a GEMM
+ *   below that consumes it is NaN. Needs K % 32 == 0, ldx and ldq multiples of 8 (>= K), lds >= K/32; x 16-byte, q 8-byte aligned. */
 int g3_quant_mxfp8_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream);
 
 /* C[M,N] = epi( sum_k (aq[m][k] 2^as[m][k/32]) (wq[n][k] 2^ws[n][k/32]) ) with fp32 accumulation on the block-scaled matrix cores; operands as
@@ -101,7 +102,7 @@ const char* g3_gemm_mxfp8_mxout_kernel_name(int M, int N, int K, int epilogue);
 /* MXFP6 (OCP MX v1.0, e2m3 elements: 1 sign, 2 exponent, 3 mantissa bits, bias 1, maximum 7.5, no Inf / NaN) of a bf16 matrix:
  * x [M][ldx] bf16 -> q [M][ldq] packed 6-bit codes + scales [M][lds] E8M0 bytes, one per 32 consecutive k of a row:
  *   X = floor(log2(amax of the block)) - 2, byte X + 127 clamped to 0..254; code = RNE(clamp(x / 2^X, -7.5, 7.5)) with the sign bit of x;
- *   an all-zero block gets byte 127 and zero codes. Block b of a row is the 24 bytes [24 b, 24 b + 24) of q's row, element i of the block
+ *   an all-zero block gets byte 127 and zero codes, a block that holds a NaN or an infinity byte 0xFF (the E8M0 NaN) and zero codes. Block b of a row is the 24 bytes [24 b, 24 b + 24) of q's row, element i of the block
  *   the 6 bits [6 i, 6 i + 6) of that 192-bit little-endian string. Needs K % 32 == 0, ldx >= K and ldq >= 3K/4 multiples of 8,
  *   lds >= K/32; x 16-byte, q 8-byte aligned. */
 int g3_quant_mxfp6_bf16(const void* x, int64_t ldx, void* q, int64_t ldq, void* scales, int64_t lds, int M, int K, void* stream);

@@ -2,6 +2,7 @@
 
     e2m3: 1 sign, 2 exponent, 3 mantissa bits, bias 1: subnormals m/8, normals 2^(e-1)(1 + m/8), maximum 7.5, no Inf / NaN codes
     X = floor(log2(amax of the block)) - 2, scale byte X + 127 clamped to 0..254 (all-zero block: byte 127, codes 0)
+    a block that holds a NaN or an infinity: scale byte 0xFF (the E8M0 NaN: the whole block is NaN), codes 0
     code = RNE(clamp(x / 2^X, -7.5, 7.5)); the sign bit is the sign bit of x, so a negative value that rounds to zero is the code 0x20 (-0)
     storage: q [M, 3K/4] uint8, block b of a row = bytes [24 b, 24 b + 24), element i = bits [6 i, 6 i + 6) of that 192-bit little-endian string
 
@@ -14,6 +15,7 @@ import torch
 
 BLOCK = 32
 E2M3_MAX = 7.5
+SCALE_NAN = 0xFF
 
 
 def e2m3_values() -> torch.Tensor:
@@ -35,17 +37,19 @@ def e2m3_encode(y: torch.Tensor) -> torch.Tensor:
 
 
 def quant_mxfp6_codes(x: torch.Tensor):
-    """x [M, K] (any float dtype, finite) -> (codes [M, K] uint8 in 0..63, scales [M, K/32] uint8), on the CPU."""
+    """x [M, K] (any float dtype) -> (codes [M, K] uint8 in 0..63, scales [M, K/32] uint8), on the CPU."""
     M, K = x.shape
     assert K % BLOCK == 0
     xb = x.detach().cpu().double().reshape(M, K // BLOCK, BLOCK)
+    bad = ~torch.isfinite(xb).all(-1)  # a NaN or an infinity anywhere in the block
+    xb = torch.where(bad.unsqueeze(-1), torch.zeros_like(xb), xb)
     amax = xb.abs().amax(-1)
     _, ex = torch.frexp(amax)  # floor(log2 amax) = ex - 1 (exact for subnormals too)
     X = torch.where(amax > 0, (ex - 1 - 2).clamp(-127, 127), torch.zeros_like(ex))
     y = (xb * torch.pow(2.0, -X.double()).unsqueeze(-1)).clamp(-E2M3_MAX, E2M3_MAX)  # exact in fp64: at most 8 significant bits
     codes = e2m3_encode(y)
     codes = torch.where((amax > 0).unsqueeze(-1), codes, torch.zeros_like(codes))  # an all-zero block has zero codes, whatever its signs
-    return codes.reshape(M, K), (X + 127).to(torch.uint8)
+    return codes.reshape(M, K), torch.where(bad, torch.full_like(X, SCALE_NAN), X + 127).to(torch.uint8)
 
 
 def pack_e2m3(codes: torch.Tensor) -> torch.Tensor:
@@ -74,11 +78,12 @@ def quant_mxfp6_ref(x: torch.Tensor):
 
 
 def dequant_mxfp6(q: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
-    """Exact fp32 value of a packed MXFP6 matrix [M, 3K/4] (also exactly representable in bf16 for |X| <= 120)."""
+    """Exact fp32 value of a packed MXFP6 matrix [M, 3K/4] (also exactly representable in bf16 for |X| <= 120); a block with scale byte 0xFF is NaN."""
     codes = unpack_e2m3(q.cpu())
     M, K = codes.shape
     v = e2m3_values()[codes.long()].reshape(M, K // BLOCK, BLOCK)
     s = torch.pow(2.0, scales.cpu().double() - 127.0)
+    s = torch.where(scales.cpu() == SCALE_NAN, torch.full_like(s, float("nan")), s)  # the E8M0 NaN
     return (v * s.unsqueeze(-1)).reshape(M, K).float().to(q.device)
 
 
