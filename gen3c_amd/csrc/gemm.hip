@@ -577,6 +577,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_bf16_nt_pp_kernel(GemmParams
     if (p.wide_store) store_tile_lds<EPI>(p, acc, m0 + m_w0, n0 + n_w0, lane, smem_raw + wave * 16384);
     else store_tile<EPI>(p, acc, m0 + m_w0, n0 + n_w0, l31, g);
 }
+// The one-wave-per-SIMD kernels (gemm_w4.hpp, gemm_w4e.hpp) keep the LDS-DMA source of a tile row as a 32-bit byte offset from the tile's first row:
+// row 255 and its last 16-byte chunk must lie below 4 GiB - 255 ld 2 + 128 < 2^32 for lda and ldw. Beyond that (host: gemm_choose, w4e_applies) the
+// call runs on the ping-pong / classic kernels, which form 64-bit pointers per row - and so does one with a negative lda or ldw, which an unsigned
+// 32-bit offset cannot express either.
+static bool w4_tile_rows_addressable(const GemmParams& p) {
+    const int64_t ld_max = ((1ll << 32) - 129) / 510;
+    return p.lda >= 0 && p.lda <= ld_max && p.ldw >= 0 && p.ldw <= ld_max;
+}
 #include "gemm_w4.hpp"
 #include "gemm_w4_conv.hpp"
 #include "gemm_w4e.hpp"
@@ -667,7 +675,8 @@ int gemm_choose(const GemmParams& p, int epi, bool conv, int n_cu, int& grid) {
             const bool tf = g3_opt_gemm_tokens_first == 1 || (g3_opt_gemm_tokens_first == 2 && p.N <= 4096);
             return tf ? GK_W4E_TF_0 : GK_W4E_0;
         }
-        if (p.wide_store && p.K >= 2 * BK) {  // one wave per SIMD (gemm_w4.hpp): whole 64-wide K tiles, at least two, full-line epilogue
+        // one wave per SIMD (gemm_w4.hpp): whole 64-wide K tiles, at least two, full-line epilogue, tile rows inside the 32-bit source offsets
+        if (p.wide_store && p.K >= 2 * BK && w4_tile_rows_addressable(p)) {
             // persistent only where a workgroup gets at least two tiles (the norm / RoPE epilogue's tables do not fit beside the tile state: no such form)
             if (epi != EPI_QK_NORM_ROPE && g3_opt_gemm_persistent && grid_cu >= 8 && nblk >= 2 * grid_cu) {
                 grid = grid_cu;

@@ -14,7 +14,8 @@
 //   * the workgroup's LAST tile has no K loop to ride in: the same instruction sequences run bare (gw4e_*_flush_*), so a tile's values do not depend
 //     on its position in the workgroup's tile list.
 // Applies to (host: w4e_applies): M, N multiples of 256, K of 128, >= 38 K tiles (34 carry the epilogue), epilogues NONE / GELU / GATED_RESIDUAL with
-// gate_rows in {1, 2, 4}, full-line alignment. Everything else runs on gemm_bf16_nt_w4_kernel. Off: g3_set_option("gemm_deferred", 0).
+// gate_rows in {1, 2, 4}, full-line alignment, 8 rows of C / R and 4 of the gate inside 2 GiB, a 256-row tile of A and of W inside 4 GiB (the per-lane
+// offsets below are 32-bit). Everything else runs on gemm_bf16_nt_w4_kernel (a wider tile: on the ping-pong kernel). Off: g3_set_option("gemm_deferred", 0).
 // Arithmetic: bf16(acc) first, then the epilogue in fp32 with the operation order of store_tile_lds (which rounds the same way since round 5): bitwise
 // equal outputs across all GEMM kernels (tests/test_kernels_gpu.py).
 
@@ -426,5 +427,5 @@ static bool w4e_applies(const GemmParams& p, int epi, int n_cu) {
     if (p.tiles_m * p.tiles_n < 2 * grid) return false;  // a workgroup with one tile has nothing to defer into
     if (epi == EPI_GATED_RESIDUAL && !(p.gate_rows == 1 || p.gate_rows == 2 || p.gate_rows == 4)) return false;
     if ((int64_t)8 * p.ldc * 2 >= (1ll << 31) || (int64_t)8 * p.ldr * 2 >= (1ll << 31) || (int64_t)4 * p.ldg * 2 >= (1ll << 31)) return false;
-    return true;
+    return w4_tile_rows_addressable(p);  // vo_w / vo_t (and the prefetch offsets) are 32-bit byte offsets of rows 0 .. 255 from the tile's first
 }

@@ -300,3 +300,21 @@ def check_sweep(what: str, y: torch.Tensor, out: torch.Tensor):
 def format_row(what: str, kernel: str, worst: float, share: float, share_r: float, frac: float) -> str:
     """one line of profiles/gemm_epilogue_parity_measured.txt"""
     return f"{what:<58} {kernel:<46} worst {worst:>8.3f}  share {share:.2e}  restatement {share_r:.2e}  C E > 0.5 ulp {frac:.2%}"
+
+
+# =================================================================================================================================
+# kernel selectors shared by the kernel-level GPU files (what g3_gemm_plan_bf16 must name, {e} = the epilogue's numeral)
+# =================================================================================================================================
+CLASSIC, PP2, PP4 = "gemm_bf16_nt_kernel<{e}, true, false, false>", "gemm_bf16_nt_pp_kernel<{e}, 2, false>", "gemm_bf16_nt_pp_kernel<{e}, 4, false>"
+W4, W4P = "gemm_bf16_nt_w4_kernel<{e}, false>", "gemm_bf16_nt_w4_kernel<{e}, true>"
+W4E, W4E_TF = "gemm_bf16_nt_w4e_kernel<{e}, false>", "gemm_bf16_nt_w4e_kernel<{e}, true>"
+REG = "gemm_bf16_nt_kernel<{e}, false, false, false>"  # register staging: what K % 64 != 0 runs
+TWO_TILES = "two tiles per workgroup"  # M of the persistent shapes: from the device's CU count (two_tiles_m)
+# the options the GEMM / convolution choice reads, and their defaults (csrc/api.hip)
+OPTION_DEFAULTS = {"gemm_pingpong": 3, "gemm_regstage": 0, "gemm_unpinned": 1, "gemm_persistent": 0, "gemm_tokens_first": 2, "gemm_wide_store": 1,
+                   "gemm_deferred": 1, "conv_w4": 1}
+
+
+def two_tiles_m(cus: int) -> int:
+    """with N = 4096 (16 tiles): the smallest M that gives each workgroup of the persistent grid (one per CU, a multiple of 8) two tiles"""
+    return 256 * -(-2 * (cus // 8 * 8) // 16)

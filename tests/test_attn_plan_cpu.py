@@ -140,3 +140,53 @@ def test_kernel_table_has_one_row_per_instantiation():
     host = src[src.index('#include "gen3c_hip.h"'):]
     for _, name in rows:
         assert host.count(name) == 1, name
+
+
+def test_operand_spans_at_the_32_bit_budget_of_the_lds_dma_kernels():
+    """attn_plan: k_max = (S_kv - 1 + 128) k_row 2 + 256 and v_max = 127 vt_row 2 + (S_kv + 64) 2 + 256 (plain V^T) must not exceed 2^32 - 1 for the
+    kernels that address K / V^T with 32-bit byte offsets. One step (8 elements) below the bound every variant keeps its kernel; at it the plain and
+    the bounded entry run the 64-bit-addressing kernel (variant 2) and the carry entries refuse. Batch and head strides, and every stride of Q and
+    O, are 64-bit in all kernels: no bound."""
+    lib = _lib.load()
+    Sq, Skv, B, H = 200, 320, 2, 3
+    a = _canonical(Sq, Skv, B, H)
+    k_row = ((1 << 32) - 1 - 256) // (2 * (Skv - 1 + 128)) // 8 * 8
+    vt_row = ((1 << 32) - 1 - 256 - 2 * (Skv + 64)) // (2 * 127) // 8 * 8
+    assert (Skv + 127) * k_row * 2 + 256 < 1 << 32 <= (Skv + 127) * (k_row + 8) * 2 + 256
+    assert 127 * vt_row * 2 + (Skv + 64) * 2 + 256 < 1 << 32 <= 127 * (vt_row + 8) * 2 + (Skv + 64) * 2 + 256
+    v2 = lib.g3_flash_attn_kernel_name_ex(Sq, Skv, B, H, 2).decode()
+    assert "v2" in v2
+    for variant in (0, 4, 9, 11):
+        for entry, bound in (("ex", 0.0), ("bounded", 23.0)):
+            base = dict(a, variant=variant, logit_bound=bound)
+            same, _ = _plan(lib, entry, base)
+            assert same is not None and "v2" not in same
+            for stride, at in (("k_row", k_row), ("vt_row", vt_row)):
+                far = dict(base, **{stride: at}, **({"vt_head": 128 * at, "vt_batch": H * 128 * at} if stride == "vt_row" else {}))
+                assert _plan(lib, entry, far) == (same, None), (variant, entry, stride)
+                far[stride] = at + 8
+                assert _plan(lib, entry, far) == (v2, None), (variant, entry, stride)
+            huge = dict(base, q_row=1 << 40, q_batch=1 << 50, k_batch=1 << 50, k_head=1 << 45, vt_batch=1 << 50, vt_head=1 << 45, o_row=1 << 40, o_head=1 << 50)
+            assert _plan(lib, entry, huge) == (same, None), (variant, entry)
+    for entry in ("carry", "bounded_cp"):
+        base = dict(a, variant=11, logit_bound=23.0 if entry == "bounded_cp" else 0.0, carry_o=0x50000, carry_lse=0x60000)
+        assert _plan(lib, entry, dict(base, k_row=k_row))[0] is not None
+        name, err = _plan(lib, entry, dict(base, k_row=k_row + 8))
+        assert name is None and err.startswith("g3_flash_attn_fwd_carry_bf16: K / V^T span (skipped keys included) exceeds the kernel's 32-bit byte offsets"), err
+
+
+def test_spatial_attention_d512_refuses_at_its_two_span_bounds():
+    """g3_spatial_attn_d512_bf16 has no dry run and no fallback: hw 512 2 >= 2^32 (a K piece's offset inside a frame) and 8 ld_vt 2 >= 2^32 (a V^T
+    piece's 8 rows) are refused with G3_ERR_ARG before anything is launched. One step below either bound the operands span 4 GiB and 256 GiB, which
+    no test allocates, so the refusals are called with placeholder pointers - and ONLY where the process has no GPU: there a weakened bound
+    ends in a failed launch (another status, a failed assertion below), never in a kernel that follows the placeholders. With a GPU the launching
+    entry is not called (the loop only restates the bounds); tests/test_far_operands_gpu.py runs it on real operands on both sides of 2^31 and 2^32 bytes of V^T span."""
+    import torch
+    lib = _lib.load()
+    text = b"g3_spatial_attn_d512_bf16: a frame exceeds the 32-bit byte offsets of the LDS-DMA addressing"
+    for hw, ld_vt in ((64, 1 << 28), (64, (1 << 28) + 8), (1 << 22, 1 << 22)):
+        assert (hw * 1024 >= 1 << 32) or (16 * ld_vt >= 1 << 32)
+        if torch.cuda.is_available():
+            continue  # placeholder pointers go to a launching entry only where no GPU can follow them
+        rc = lib.g3_spatial_attn_d512_bf16(0x10000, 0x20000, 0x30000, ld_vt, 512 * ld_vt, 0x40000, 1, hw, 0.044, None)
+        assert rc == _lib.G3_ERR_ARG and lib.g3_last_error() == text, (hw, ld_vt, rc, lib.g3_last_error())

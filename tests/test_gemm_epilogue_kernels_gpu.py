@@ -25,6 +25,7 @@ import pytest
 import torch
 
 from tests import gemm_ref as gr
+from tests.gemm_ref import CLASSIC, PP2, PP4, REG, TWO_TILES, W4, W4E, W4E_TF, W4P  # (shared with tests/test_far_operands_gpu.py)
 from tests.guarded import Guarded, _dev
 from tests.test_kernels_gpu import _GEMM_OPTION_DEFAULTS
 
@@ -32,12 +33,6 @@ pytestmark = pytest.mark.gpu
 
 bf16 = torch.bfloat16
 DEFAULTS = dict(_GEMM_OPTION_DEFAULTS, gemm_wide_store=1, gemm_deferred=1)
-TWO_TILES = "two tiles per workgroup"  # M of the persistent shapes: from the device's CU count (_shape)
-
-CLASSIC, PP2, PP4 = "gemm_bf16_nt_kernel<{e}, true, false, false>", "gemm_bf16_nt_pp_kernel<{e}, 2, false>", "gemm_bf16_nt_pp_kernel<{e}, 4, false>"
-W4, W4P = "gemm_bf16_nt_w4_kernel<{e}, false>", "gemm_bf16_nt_w4_kernel<{e}, true>"
-W4E, W4E_TF = "gemm_bf16_nt_w4e_kernel<{e}, false>", "gemm_bf16_nt_w4e_kernel<{e}, true>"
-REG = "gemm_bf16_nt_kernel<{e}, false, false, false>"  # register staging: what K % 64 != 0 runs
 # epilogue copy -> (kernel the plan must name, the options that select it, its smallest shape, epilogues, gate rows, the sweep's shape)
 COPIES = {
     "store_tile/pp2": (PP2, {"gemm_wide_store": 0}, gr.SMALL, range(5), (1, 2), (256, 256, 256)),
@@ -87,7 +82,7 @@ def _shape(shape):
     L, lib = _lib()
     cus = C.c_int(0)
     L.check(lib.g3_device_info(0, C.byref(cus), None, None, 0), "g3_device_info")
-    return (256 * -(-2 * (cus.value // 8 * 8) // 16),) + tuple(shape[1:])  # with N = 4096 (16 tiles): two tiles for each of the persistent grid's workgroups
+    return (gr.two_tiles_m(cus.value),) + tuple(shape[1:])
 
 
 def _bits(t):

@@ -169,3 +169,78 @@ def test_kernel_table_has_one_row_per_instantiation():
     for header in ("gemm_w4.hpp", "gemm_w4e.hpp", "gemm_w4_conv.hpp"):
         text = (ROOT / "gen3c_amd" / "csrc" / header).read_text()
         assert "hipLaunchKernelGGL" not in text and "hipFuncSetAttribute" not in text, header
+
+
+# ---- the bounds on how far an operand may lie: the kernel chosen one step below each, and at it ----------------------------------------------------------
+LD_TILE_MAX = ((1 << 32) - 129) // 510 // 8 * 8  # the largest leading dimension (a multiple of 8) with 255 ld 2 + 128 < 2^32
+
+
+def test_one_wave_kernels_only_where_a_tile_row_offset_fits_32_bits():
+    """gemm_w4.hpp / gemm_w4e.hpp keep the LDS-DMA source of tile row r as the 32-bit byte offset r ld 2 + chunk 16, r <= 255, from the tile's first
+    row: gemm_choose takes GK_W4_0 / GK_W4_PERSIST_0 and w4e_applies the deferred kernels only where 255 ld 2 + 128 < 2^32 for lda and for ldw;
+    beyond, the call runs on the ping-pong kernel (64-bit row pointers) - under every option set that reached a one-wave kernel before."""
+    lib = _lib.load()
+    assert 255 * LD_TILE_MAX * 2 + 128 < 1 << 32 <= 255 * (LD_TILE_MAX + 8) * 2 + 128
+    pp2 = "gemm_bf16_nt_pp_kernel<{e}, 2, false>"
+    cases = [  # (options, canonical base, n_cu, kernel up to the bound)
+        ({}, (257, 264, 192, 0), 256, "gemm_bf16_nt_w4_kernel<{e}, false>"),
+        ({}, (257, 264, 192, 4), 256, "gemm_bf16_nt_w4_kernel<{e}, false>"),
+        ({"gemm_persistent": 1}, (2048, 4096, 128, 0), 64, "gemm_bf16_nt_w4_kernel<{e}, true>"),
+        ({}, (2048, 4096, 2432, 0), 64, "gemm_bf16_nt_w4e_kernel<{e}, true>"),
+        ({"gemm_tokens_first": 0}, (2048, 4096, 2432, 2), 64, "gemm_bf16_nt_w4e_kernel<{e}, false>"),
+        ({"gemm_deferred_grid": 8}, (2048, 4096, 2432, 1), 64, "gemm_bf16_nt_w4e_kernel<{e}, true>"),
+    ]
+    try:
+        for options, base, n_cu, kernel in cases:
+            set_options(lib, options)
+            a, e = canonical("nt", base), base[3]
+            for ld in ("lda", "ldw"):
+                assert plan(lib, dict(a, **{ld: LD_TILE_MAX}), n_cu)[0] == kernel.format(e=e), (options, base, ld)
+                assert plan(lib, dict(a, **{ld: LD_TILE_MAX + 8}), n_cu)[0] == pp2.format(e=e), (options, base, ld)
+            assert plan(lib, dict(a, lda=LD_TILE_MAX, ldw=LD_TILE_MAX), n_cu)[0] == kernel.format(e=e)
+        # the fused norm / RoPE entry exists on the one-wave kernel only: beyond the bound, the ping-pong kernel and the standalone passes
+        set_options(lib, {})
+        q = canonical("qk", (256, 384, 128, 2))
+        assert plan(lib, dict(q, lda=LD_TILE_MAX), 256) == ["gemm_bf16_nt_w4_kernel<5, false>", 2, 0]
+        assert plan(lib, dict(q, lda=LD_TILE_MAX + 8), 256) == ["gemm_bf16_nt_pp_kernel<0, 2, false>", 2, 3]  # then norm q, then norm k
+    finally:
+        set_options(lib, {})
+
+
+def test_the_bound_reroutes_no_shape_of_the_benchmark_or_the_dit():
+    """The block linears of the DiT bench.py measures (D = 4096, MLP 16 384, fused QKV 12 288, 56 320 tokens; 14 080 and 7040 under context
+    parallelism), with dense operands and with A a column view of the widest buffer the model keeps (the MLP's 16 384 features): every one still gets
+    the one-wave or the deferred kernel, none the ping-pong kernel the bound reroutes to. The widest row is 32 KiB, the bound 16 MiB - and for the
+    recorded calls test_plan_equals_the_recorded_launcher shows every plan unchanged."""
+    lib = _lib.load()
+    assert LD_TILE_MAX == 8421504 and all(max(args.get("lda", 0), args.get("ldw", 0)) < LD_TILE_MAX // 64 for _, entry, _, args, _ in calls() if entry in ("nt", "qk"))
+    linears = [(12288, 4096, 0), (4096, 4096, 2), (16384, 4096, 1), (4096, 16384, 2), (4096, 4096, 0), (8192, 1024, 0)]  # qkv, out, mlp up / down, cross q, cross kv
+    try:
+        set_options(lib, {})
+        for M in (56320, 14080, 7040):
+            for N, K, epi in linears:
+                for lda in (K, 16384):
+                    for n_cu in N_CU:
+                        got = plan(lib, dict(canonical("nt", (M, N, K, epi)), lda=max(lda, K)), n_cu)
+                        assert got[0].startswith(("gemm_bf16_nt_w4_kernel<", "gemm_bf16_nt_w4e_kernel<")), (M, N, K, epi, lda, n_cu, got)
+    finally:
+        set_options(lib, {})
+
+
+def test_deferred_kernel_epilogue_strides_and_conv_spans_at_their_bounds():
+    """w4e_applies: 8 ldc 2, 8 ldr 2 and 4 ldg 2 below 2^31 (the epilogue's 32-bit per-lane offsets), else the one-wave kernel. conv_w4_applies:
+    ld_in 2 < 2^31, input rows < 2^31, N ldw 2 < 2^32 (the tap slab), else the ping-pong convolution."""
+    lib = _lib.load()
+    w4e, w4, cv, pp = "gemm_bf16_nt_w4e_kernel<2, true>", "gemm_bf16_nt_w4_kernel<2, false>", "gemm_bf16_nt_w4_conv_kernel<3>", "gemm_bf16_nt_pp_kernel<3, 2, true>"
+    try:
+        set_options(lib, {})
+        a = canonical("nt", (2048, 4096, 2432, 2))
+        for ld, bound in (("ldc", 1 << 27), ("ldr", 1 << 27), ("ldg", 1 << 28)):
+            assert plan(lib, dict(a, **{ld: bound - 8}), 64)[0] == w4e, ld
+            assert plan(lib, dict(a, **{ld: bound}), 64)[0] == w4, ld
+        c = canonical("conv", (128, 128, 2, 16, 16, 1, 3, 3))
+        assert plan(lib, dict(c, lda=(1 << 30) - 8), 256)[0] == cv and plan(lib, dict(c, lda=1 << 30), 256)[0] == pp
+        assert plan(lib, dict(c, Ti=2047, Hi=1024, Wi=1024), 256)[0] == cv and plan(lib, dict(c, Ti=2048, Hi=1024, Wi=1024), 256)[0] == pp
+        assert plan(lib, dict(c, ldw=(1 << 24) - 8), 256)[0] == cv and plan(lib, dict(c, ldw=1 << 24), 256)[0] == pp  # N = 128: 128 ldw 2 = 2^32
+    finally:
+        set_options(lib, {})

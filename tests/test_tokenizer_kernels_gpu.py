@@ -55,37 +55,7 @@ def _err_names(entry):
 # =================================================================================================================================
 # convolutions
 # =================================================================================================================================
-_GEOM = {  # what the library is told: kt, kh, kw, st, sh, sw, ot, oh, ow  (gen3c_amd/tokenizer.py). The REFERENCE never sees these numbers.
-    "s3": (1, 3, 3, 1, 1, 1, 0, -1, -1), "t3": (3, 1, 1, 1, 1, 1, -2, 0, 0), "p1": (1, 1, 1, 1, 1, 1, 0, 0, 0),
-    "s3s2": (1, 3, 3, 1, 2, 2, 0, 0, 0), "t3s2": (3, 1, 1, 2, 1, 1, -2, 0, 0),
-}
-
-# name: (kind, K, N, T, H, W, epilogue, pad of ld_in, ldw, ld_out, ldr, entry, meant for the one-wave kernel)
-_CONV_CASES = {
-    "ragged_m_n": ("s3", 128, 136, 2, 9, 31, "res", 8, 8, 8, 8, "stats", True),       # M = 558: two whole M tiles and 46 rows; N = 136 of a 256 tile
-    "one_tile": ("s3", 64, 256, 1, 16, 16, "bias", 0, 0, 0, 0, "plain", True),        # M = 256, N = 256 exactly, dense as the network calls it
-    "one_tile_padded": ("s3", 64, 256, 1, 16, 16, "res", 8, 8, 8, 16, "stats", True),  # the same tile with every leading dimension padded
-    "t3_image": ("t3", 64, 16, 1, 5, 7, "none", 8, 0, 16, 0, "plain", True),          # T = 1: all three taps read frame 0; production N = 16
-    "t3_video": ("t3", 192, 192, 4, 6, 10, "res", 0, 8, 0, 8, "stats", True),
-    "t3s2_image": ("t3s2", 64, 12, 1, 4, 6, "bias", 8, 8, 8, 0, "plain", False),      # N % 8 == 4: narrow store
-    "t3s2_T2": ("t3s2", 16, 192, 2, 5, 9, "res", 8, 8, 8, 8, "plain", False),         # K = 16 (the decoder's first convolution) - direct loads
-    "t3s2_T5": ("t3s2", 192, 16, 5, 6, 10, "none", 0, 0, 8, 0, "stats", True),
-    "s3_W1": ("s3", 64, 16, 2, 5, 1, "bias", 8, 8, 8, 0, "plain", True),              # both horizontal neighbours are padding
-    "s3_W2": ("s3", 72, 4, 1, 6, 2, "bias", 8, 8, 8, 0, "plain", False),              # K = 72: a ragged second K tile; N = 4
-    "s3s2_odd": ("s3s2", 128, 260, 1, 7, 9, "bias", 8, 8, 8, 0, "plain", False),      # N = 260: second N tile of 4 columns, narrow store
-    "s3s2_even": ("s3s2", 512, 16, 2, 8, 10, "res", 8, 8, 8, 8, "stats", True),       # bottom row / right column of windows half outside
-    "s3s2_mixed": ("s3s2", 64, 192, 1, 7, 10, "none", 0, 0, 0, 0, "plain", True),
-    "p1_tiny": ("p1", 8, 4, 1, 3, 5, "none", 8, 8, 8, 0, "plain", False),
-    "p1_wide": ("p1", 512, 192, 2, 9, 15, "res", 8, 8, 8, 8, "plain", True),          # M = 270
-    "ldr_mod8_4": ("s3", 64, 16, 2, 6, 7, "res", 0, 0, 0, 4, "plain", False),         # residual rows not 16-byte addressable: wide stores off
-}
-_CONV_PATHS = {
-    "w4_gaps": dict(conv_w4=1),                      # one wave per SIMD, tap change in the MFMA gaps
-    "w4_stmt": dict(conv_w4=2),                      # one wave per SIMD, tap change between statements
-    "pingpong": dict(conv_w4=0, gemm_pingpong=3),
-    "lds_dma": dict(conv_w4=0, gemm_pingpong=0),     # gemm_bf16_nt_kernel, LDS-DMA staging
-    "direct": dict(gemm_regstage=1),                 # gemm_bf16_nt_kernel, register staging (also what K % 64 != 0 takes under any options)
-}
+_GEOM, _CONV_CASES, _CONV_PATHS = kr.CONV_GEOM, kr.CONV_CASES, kr.CONV_PATHS  # (shared with tests/test_far_operands_gpu.py)
 
 
 def _conv_params():
