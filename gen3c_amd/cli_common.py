@@ -84,6 +84,11 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="with --self_attn_window_frames and --num_gpus > 1: run the window under context parallelism - every rank receives only the latent frames "
                         "within W of its own and the sink frames (the \"window_halo\" schedule) instead of refusing (opt-in, default off; same as a third field "
                         "in G3_SELF_ATTN_WINDOW=\"W,S,cp\")")
+    p.add_argument("--self_attn_pattern", type=str, default=None, metavar="radial:WIDTH1:SINK|frame:W:S",
+                   help="single GPU: sparse self-attention over a range table - radial:WIDTH1:SINK is a spatial band of half-width WIDTH1 x the frame length at "
+                        "frame distance 1 that halves every time the distance doubles, plus the first SINK latent frames; frame:W:S is the frame window of "
+                        "--self_attn_window_frames at any frame length (720p included). Opt-in, default off; outside the parity statement, picture quality with "
+                        "trained weights unmeasured: DESIGN.md section 14; same as G3_SELF_ATTN_PATTERN. Not together with --self_attn_window_frames")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -197,6 +202,16 @@ def self_attn_window_cp_requested(args) -> bool:
         return True
     parts = [x.strip() for x in os.environ.get("G3_SELF_ATTN_WINDOW", "").split(",")]
     return len(parts) == 3 and parts[2] == "cp"
+
+
+def self_attn_pattern_requested(args):
+    """--self_attn_pattern radial:WIDTH1:SINK | frame:W:S, or the same string in G3_SELF_ATTN_PATTERN -> the DiT's spec tuple; None with neither
+    (opt-in, default off). The flag wins over the environment."""
+    from .sparse_attn import check_spec, parse_pattern
+    text = getattr(args, "self_attn_pattern", None)
+    if text is None:
+        text = os.environ.get("G3_SELF_ATTN_PATTERN", "").strip() or None
+    return check_spec(parse_pattern(text))
 
 
 def log_ignored_flags(args, log=print) -> List[str]:
@@ -330,6 +345,11 @@ class Session:
             net.set_self_attn_window(*window, context_parallel=window_cp)  # (with context parallelism and no switch the first forward refuses it, with the numbers)
             print(f"[gen3c_amd] self-attention window: {window[0]} latent frame(s) either side + {window[1]} sink frame(s) (opt-in; outside the parity statement)"
                   + ("; under context parallelism: the window_halo exchange" if window_cp and self.cp_size > 1 else ""))
+        pattern = self_attn_pattern_requested(args)
+        if pattern is not None:
+            net.set_self_attn_pattern(pattern)  # (with a window, or under context parallelism, the first forward refuses it)
+            print(f"[gen3c_amd] self-attention pattern: {pattern[0]}:{pattern[1]}:{pattern[2]} over a range table (opt-in; outside the parity statement, "
+                  "picture quality unmeasured)")
         if self.cfg_size > 1:
             self.cfg_group = parallel_state.get_cfg_parallel_group()
             print(f"[gen3c_amd] --cfg_parallel: 2 guidance branches x {self.cp_size} context-parallel rank(s); this rank runs the "

@@ -83,6 +83,12 @@ struct AttnParams {
     // sequence, and K / V^T hold the global frames [0, win_buf_head) ++ [win_buf_head + win_buf_gap, ...). g3_self_attn_fwd_window_bf16 is
     // win_q_frame0 = win_buf_head = win_buf_gap = 0, win_total_frames = Skv / win_frame_len.
     int win_q_frame0, win_total_frames, win_buf_head, win_buf_gap;
+    // range-table form (flash_attn_fwd_w4b_rng_kernel, flash_attn_fwd_w4b_nm_rng_kernel; g3_self_attn_fwd_ranges_bf16): int32 (first_key, n_keys) pairs
+    // [rng_n_patterns][grid_q][rng_max_ranges][2] and the optional pattern of every head (nullptr: pattern 0), both on the device. Every workgroup
+    // loads its own row and clamps it to the operand; no other kernel reads them.
+    const int32_t* rng_table;
+    const int32_t* rng_head_pattern;
+    int rng_n_patterns, rng_max_ranges;
 };
 
 G3_DEVICE int k_off(int row, int chunk) { return row * HD + ((chunk ^ (row & 15)) << 3); }          // [64][128]
@@ -1018,6 +1024,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 
 
 #include "attention_w4.hpp"
+#define W4B_RNG 0
 #define W4B_WIN 0
 #define W4B_NM 0
 #define W4B_CP 0
@@ -1039,9 +1046,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 #undef W4B_NM
 #define W4B_NM 0
 #include "attention_w4b.hpp"  // flash_attn_fwd_w4b_win_kernel: the same with the running row maximum (bound out of range)
+#undef W4B_WIN
+#undef W4B_RNG
+#define W4B_WIN 0
+#define W4B_RNG 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_rng_kernel: the CP form's key addressing out of a per-workgroup range table (g3_self_attn_fwd_ranges_bf16)
+#undef W4B_NM
+#define W4B_NM 1
+#include "attention_w4b.hpp"  // flash_attn_fwd_w4b_nm_rng_kernel: the same without the running row maximum (the bound in range)
 #undef W4B_NM
 #undef W4B_CP
 #undef W4B_WIN
+#undef W4B_RNG
 #include "attention_w4c.hpp"  // flash_attn_fwd_w4c_nm_kernel: the plain no-max form on 16x16x32 MFMAs (g3_self_attn_fwd_bounded16_bf16)
 
 }  // namespace
@@ -1049,10 +1065,12 @@ __global__ __launch_bounds__(NTHREADS, 2) void flash_attn_fwd_v3_kernel(AttnPara
 /* ---- host side: every public entry point fills ONE call record (AttnCall); attn_plan turns it into a refusal or into the kernel's parameters, its
  * row of the ONE kernel table and the grid; attn_launch launches that. g3_attn_plan_bf16 and the *_kernel_name functions ask the same code. ---------- */
 #include "gen3c_hip.h"  // enum g3_attn_entry
+#include <vector>
 
 struct AttnOperand { const void* ptr = nullptr; int64_t row = 0, batch = 0, head = 0; };  // element strides
 constexpr int ATTN_ENTRY_WINDOW = G3_ATTN_ENTRY_BOUNDED_CP + 1;  // g3_self_attn_fwd_window_bf16: has its own dry run, so it is no value of enum g3_attn_entry
 constexpr int ATTN_ENTRY_WINDOW_CP = G3_ATTN_ENTRY_BOUNDED_CP + 2;  // g3_self_attn_fwd_window_cp_bf16: likewise (g3_attn_window_cp_plan_bf16)
+constexpr int ATTN_ENTRY_RANGES = G3_ATTN_ENTRY_BOUNDED_CP + 3;  // g3_self_attn_fwd_ranges_bf16: likewise (g3_attn_ranges_plan_bf16)
 struct AttnCall {
     int entry = G3_ATTN_ENTRY_FWD;  // the public entry point called: it decides which checks run and whose name a refusal carries
     AttnOperand q, k, vt, o;        // o.ptr: the bf16 result; o's strides also address o_partial and carry_o
@@ -1067,6 +1085,7 @@ struct AttnCall {
     int mfma16 = 0;  // g3_self_attn_fwd_bounded16_bf16: the 16x16x32 tile loop where the plain no-max kernel would run
     int win_frame_len = 0, win_frames = 0, win_sink = 0;  // g3_self_attn_fwd_window_bf16
     int win_total_frames = 0, win_q_frame0 = 0, win_buf_head = 0, win_buf_tail0 = 0;  // g3_self_attn_fwd_window_cp_bf16: T, the query origin, a and b
+    const int32_t* ranges = nullptr; const int32_t* head_pattern = nullptr; int n_patterns = 0, max_ranges = 0;  // g3_self_attn_fwd_ranges_bf16 (device pointers)
     void* stream = nullptr;
 };
 
@@ -1077,6 +1096,9 @@ struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_row
 // (the rows only g3_self_attn_fwd_window_bf16 and g3_self_attn_fwd_window_cp_bf16 reach)
 #define G3_ATTN_KERNELS_WIN(X) \
     X(AK_W4BX_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_win_kernel<true>) X(AK_W4BX_NM_WIN, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_win_kernel<true>)
+// (the rows only g3_self_attn_fwd_ranges_bf16 reaches)
+#define G3_ATTN_KERNELS_RNG(X) \
+    X(AK_W4BX_RNG, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_rng_kernel<true>) X(AK_W4BX_NM_RNG, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_rng_kernel<true>)
 #define G3_ATTN_KERNELS(X) \
     X(AK_V1_L, NTHREADS, BQ, flash_attn_fwd_kernel<0>) X(AK_V1_S, NTHREADS, BQ, flash_attn_fwd_kernel<1>) \
     X(AK_V2_L, NTHREADS, BQ, flash_attn_fwd_v2_kernel<0>) X(AK_V2_S, NTHREADS, BQ, flash_attn_fwd_v2_kernel<1>) \
@@ -1091,8 +1113,9 @@ struct AttnKernel { const char* name; void (*fn)(AttnParams); int threads, q_row
     X(AK_W4BX_NM_CARRY, W4_THREADS, W4_BQ, flash_attn_fwd_w4b_nm_carry_kernel<true>)
 #define G3_ATTN_ID(ID, THREADS, Q_ROWS, ...) ID,
 #define G3_ATTN_ROW(ID, THREADS, Q_ROWS, ...) {#__VA_ARGS__, &__VA_ARGS__, THREADS, Q_ROWS},
-enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) G3_ATTN_KERNELS16(G3_ATTN_ID) G3_ATTN_KERNELS_WIN(G3_ATTN_ID) AK_COUNT };
-static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW) G3_ATTN_KERNELS16(G3_ATTN_ROW) G3_ATTN_KERNELS_WIN(G3_ATTN_ROW)};
+enum AttnKernelId { G3_ATTN_KERNELS(G3_ATTN_ID) G3_ATTN_KERNELS16(G3_ATTN_ID) G3_ATTN_KERNELS_WIN(G3_ATTN_ID) G3_ATTN_KERNELS_RNG(G3_ATTN_ID) AK_COUNT };
+static const AttnKernel attn_kernels[AK_COUNT] = {G3_ATTN_KERNELS(G3_ATTN_ROW) G3_ATTN_KERNELS16(G3_ATTN_ROW) G3_ATTN_KERNELS_WIN(G3_ATTN_ROW)
+                                                  G3_ATTN_KERNELS_RNG(G3_ATTN_ROW)};
 #undef G3_ATTN_ID
 #undef G3_ATTN_ROW
 
@@ -1151,6 +1174,14 @@ static int attn_window_check(const char* fn, int S, int frame_len, int W, int s)
     return G3_OK;
 }
 
+// the range-table arguments the launch and g3_attn_ranges_check share: G3_OK, or the refusal under the caller's name
+static int attn_ranges_shape_check(const char* fn, int S, int n_patterns, int max_ranges) {
+    if (S <= 0 || (S % KVB)) return g3_set_error(G3_ERR_ARG, "%s: S %d must be a positive multiple of 64", fn, S);
+    if (n_patterns < 1) return g3_set_error(G3_ERR_ARG, "%s: n_patterns %d must be >= 1", fn, n_patterns);
+    if (max_ranges < 1 || max_ranges > 64) return g3_set_error(G3_ERR_ARG, "%s: max_ranges %d outside [1, 64]", fn, max_ranges);
+    return G3_OK;
+}
+
 // The key-sharded window form: the S_q query rows are frames [q_frame0, q_frame0 + S_q / frame_len) of T, the K / V^T operand of S_kv_buf keys holds the
 // global frames [0, a) ++ [b, c). G3_OK with c, or the refusal. The loop over the query blocks is what keeps a wrong halo plan from becoming a read
 // outside the operand: every block's key set must lie inside the buffer (keys no block attends are allowed; the kernel skips them).
@@ -1191,9 +1222,19 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     const bool cp_form = c.entry == G3_ATTN_ENTRY_CARRY || c.entry == G3_ATTN_ENTRY_BOUNDED_CP;
     const bool window_cp = c.entry == ATTN_ENTRY_WINDOW_CP;
     const bool window = c.entry == ATTN_ENTRY_WINDOW || window_cp;
+    const bool ranges = c.entry == ATTN_ENTRY_RANGES;
     const char* fn = cp_form ? "g3_flash_attn_fwd_carry_bf16" : c.entry == G3_ATTN_ENTRY_BOUNDED ? "g3_self_attn_fwd_bounded_bf16" :
-                     window_cp ? "g3_self_attn_fwd_window_cp_bf16" : window ? "g3_self_attn_fwd_window_bf16" : "g3_flash_attn_fwd_ex_bf16";
+                     window_cp ? "g3_self_attn_fwd_window_cp_bf16" : window ? "g3_self_attn_fwd_window_bf16" :
+                     ranges ? "g3_self_attn_fwd_ranges_bf16" : "g3_flash_attn_fwd_ex_bf16";
     uint32_t kv_skip_vt_bytes = 0;
+    if (ranges) {  // (variant 11, plain V^T, a bf16 output, Sq == Skv == S: the entry sets them. The table's CONTENT is the device's: the kernel clamps it)
+        if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || !c.o.ptr) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
+        if (int rc = attn_ranges_shape_check(fn, c.Skv, c.n_patterns, c.max_ranges)) return rc;
+        if (!c.ranges || ((uintptr_t)c.ranges & 7)) return g3_set_error(G3_ERR_ARG, "%s: null or misaligned range table (8-byte alignment)", fn);
+        if ((uintptr_t)c.head_pattern & 3) return g3_set_error(G3_ERR_ARG, "%s: misaligned head_pattern (4-byte alignment)", fn);
+        if (c.vt.row < c.Skv)  // (S % 64 == 0: S is its own ceil64; the kernel reads whole V^T tiles unguarded)
+            return g3_set_error(G3_ERR_ARG, "%s: V^T leading dim %lld below ceil64(S) %d", fn, (long long)c.vt.row, c.Skv);
+    }
     if (window) {  // (variant 11, plain V^T, a bf16 output: the entries set them; g3_self_attn_fwd_window_bf16 also Sq == Skv == S)
         if (!c.q.ptr || !c.k.ptr || !c.vt.ptr || !c.o.ptr) return g3_set_error(G3_ERR_ARG, "%s: null operand", fn);
         if (window_cp) {  // (Skv = the compact buffer's keys)
@@ -1288,7 +1329,7 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
             if (cp_form)
                 return g3_set_error(G3_ERR_ARG, "g3_flash_attn_fwd_carry_bf16: K / V^T span (skipped keys included) exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes); "
                                                 "the 64-bit-addressing kernel has no carry form", (unsigned long long)k_max, (unsigned long long)v_max);
-            if (window)
+            if (window || ranges)
                 return g3_set_error(G3_ERR_ARG, "%s: K / V^T span exceeds the kernel's 32-bit byte offsets (k %llu, vt %llu bytes)", fn,
                                     (unsigned long long)k_max, (unsigned long long)v_max);
             if (c.vt_seg_len > 0)
@@ -1324,6 +1365,7 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
     p.logit_bound_log2 = attn_bound_log2(c.logit_bound);
     p.win_frame_len = p.win_frames = p.win_sink = 0;
     p.win_q_frame0 = p.win_total_frames = p.win_buf_head = p.win_buf_gap = 0;
+    p.rng_table = p.rng_head_pattern = nullptr; p.rng_n_patterns = p.rng_max_ranges = 0;
     // bounded logits (only the two bounded entries carry a bound): the no-max form. g3_self_attn_fwd_bounded_bf16: for the plain XB kernel's problems
     // only; g3_self_attn_fwd_bounded_cp_bf16: also with segmented V^T, and with a carry-in state or a skipped key range. Everything else runs as it always did.
     const bool no_max = attn_bound_usable(p.logit_bound_log2) && (c.entry == G3_ATTN_ENTRY_BOUNDED_CP || (!cp_form && c.vt_seg_len == 0));
@@ -1336,6 +1378,10 @@ static int attn_plan(const AttnCall& call, AttnPlan& plan) {
         p.win_frame_len = c.win_frame_len; p.win_frames = c.win_frames; p.win_sink = c.win_sink;
         p.win_total_frames = c.win_total_frames;  // (g3_self_attn_fwd_window_bf16: S / frame_len, the other three 0 - every key maps to itself)
         p.win_q_frame0 = c.win_q_frame0; p.win_buf_head = c.win_buf_head; p.win_buf_gap = c.win_buf_tail0 - c.win_buf_head;
+    }
+    if (ranges) {  // never demoted: S % 64 == 0, the V^T leading dimension and the operand span were checked above, so the variant is still the entry's 11
+        plan.kernel = &attn_kernels[no_max ? AK_W4BX_NM_RNG : AK_W4BX_RNG];
+        p.rng_table = c.ranges; p.rng_head_pattern = c.head_pattern; p.rng_n_patterns = c.n_patterns; p.rng_max_ranges = c.max_ranges;
     }
     plan.grid = dim3((c.Sq + plan.kernel->q_rows - 1) / plan.kernel->q_rows, c.H, c.B);
     if (variant == 10 || variant == 11) {  // w4b (attention_w4b.hpp): optionally a 1-D grid that gives every XCD its own (batch, head) pairs
@@ -1561,6 +1607,81 @@ extern "C" int g3_self_attn_window_cp_tiles(int Sq, int Skv_buf, int frame_len, 
         attn_window_range(Sq, frame_len, T, q_frame0, W, s, b, sink_end, lo, hi);
         *attended += (hi - lo + sink_end) / KVB;
     }
+    return G3_OK;
+}
+
+/* ---- self-attention over a range table: per (pattern, query block) a list of key ranges, the pattern picked per head (attention_w4b.hpp, RNG; the function
+ * and the table's rules: gen3c_hip.h). Always variant 11's family, never demoted ----------------------------------------------------------------- */
+#define G3_ATTN_RANGES_PARAMS                                                                                                                          \
+    const void *q, int64_t q_row, int64_t q_batch, int64_t q_head, const void *k, int64_t k_row, int64_t k_batch, int64_t k_head, const void *vt,      \
+        int64_t vt_row, int64_t vt_batch, int64_t vt_head, void *o, int64_t o_row, int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, \
+        float softmax_scale, float logit_bound, const int32_t *ranges, int n_patterns, int max_ranges, const int32_t *head_pattern
+static AttnCall attn_ranges_call(G3_ATTN_RANGES_PARAMS) {
+    AttnCall c;
+    c.entry = ATTN_ENTRY_RANGES;
+    c.q = {q, q_row, q_batch, q_head}; c.k = {k, k_row, k_batch, k_head}; c.vt = {vt, vt_row, vt_batch, vt_head}; c.o = {o, o_row, o_batch, o_head};
+    c.variant = 11; c.logit_bound = logit_bound;
+    c.ranges = ranges; c.n_patterns = n_patterns; c.max_ranges = max_ranges; c.head_pattern = head_pattern;
+    c.Sq = S; c.Skv = S; c.B = B; c.H = H; c.head_dim = head_dim; c.softmax_scale = softmax_scale;
+    return c;
+}
+#define G3_ATTN_RANGES_ARGS \
+    q, q_row, q_batch, q_head, k, k_row, k_batch, k_head, vt, vt_row, vt_batch, vt_head, o, o_row, o_batch, o_head, S, B, H, head_dim, softmax_scale, logit_bound, \
+        ranges, n_patterns, max_ranges, head_pattern
+extern "C" int g3_self_attn_fwd_ranges_bf16(G3_ATTN_RANGES_PARAMS, void* stream) {
+    AttnCall c = attn_ranges_call(G3_ATTN_RANGES_ARGS);
+    c.stream = stream;
+    return attn_launch(c);
+}
+extern "C" const char* g3_attn_ranges_plan_bf16(G3_ATTN_RANGES_PARAMS) {
+    AttnPlan plan;
+    return attn_plan(attn_ranges_call(G3_ATTN_RANGES_ARGS), plan) == G3_OK ? plan.kernel->name : nullptr;
+}
+#undef G3_ATTN_RANGES_PARAMS
+#undef G3_ATTN_RANGES_ARGS
+
+extern "C" int g3_self_attn_ranges_max(void) { return 64; }
+
+/* Pure host code: every rule of a valid table (gen3c_hip.h), and the (head, query block, 64-key tile) triples a launch over it visits. */
+extern "C" int g3_attn_ranges_check(const int32_t* ranges_host, int n_patterns, int S, int max_ranges, const int32_t* head_pattern_host, int H, int64_t* attended,
+                                    int64_t* dense) {
+    const char* fn = "g3_attn_ranges_check";
+    if (!ranges_host || !attended || !dense) return g3_set_error(G3_ERR_ARG, "%s: null table or result pointer", fn);
+    if (int rc = attn_ranges_shape_check(fn, S, n_patterns, max_ranges)) return rc;
+    if (H < 1) return g3_set_error(G3_ERR_ARG, "%s: H %d must be >= 1", fn, H);
+    for (int h = 0; head_pattern_host && h < H; ++h)
+        if (head_pattern_host[h] < 0 || head_pattern_host[h] >= n_patterns)
+            return g3_set_error(G3_ERR_ARG, "%s: head_pattern[%d] = %d outside [0, %d)", fn, h, head_pattern_host[h], n_patterns);
+    const int n_blk = (S + W4_BQ - 1) / W4_BQ;
+    std::vector<int64_t> tiles(n_patterns, 0);  // per pattern, over its blocks
+    for (int pt = 0; pt < n_patterns; ++pt)
+        for (int b = 0; b < n_blk; ++b) {
+            const int32_t* row = ranges_host + ((int64_t)pt * n_blk + b) * max_ranges * 2;
+            int64_t end = 0;  // of the previous range
+            int r = 0;
+            for (; r < max_ranges && row[2 * r + 1] != 0; ++r) {
+                const int64_t first = row[2 * r], n = row[2 * r + 1];
+                if (first < 0 || n < 0 || (first % KVB) || (n % KVB))
+                    return g3_set_error(G3_ERR_ARG, "%s: pattern %d, block %d, range %d: first_key %d and n_keys %d must be multiples of 64, first_key >= 0 and n_keys > 0",
+                                        fn, pt, b, r, (int)first, (int)n);
+                if (first < end)
+                    return g3_set_error(G3_ERR_ARG, "%s: pattern %d, block %d, range %d: first_key %d lies below the end %d of range %d (lists are ascending and disjoint)",
+                                        fn, pt, b, r, (int)first, (int)end, r - 1);
+                if (first + n > S)
+                    return g3_set_error(G3_ERR_ARG, "%s: pattern %d, block %d, range %d: keys [%d, %lld) reach beyond S %d", fn, pt, b, r, (int)first,
+                                        (long long)(first + n), S);
+                end = first + n;
+                tiles[pt] += n / KVB;
+            }
+            if (r == 0 && row[0] == 0) return g3_set_error(G3_ERR_ARG, "%s: pattern %d, block %d, range 0: the list is empty", fn, pt, b);
+            for (; r < max_ranges; ++r)
+                if (row[2 * r] != 0 || row[2 * r + 1] != 0)
+                    return g3_set_error(G3_ERR_ARG, "%s: pattern %d, block %d, range %d: (%d, %d) behind the terminator must be zero", fn, pt, b, r, row[2 * r],
+                                        row[2 * r + 1]);
+        }
+    *dense = (int64_t)H * n_blk * (S / KVB);
+    *attended = 0;
+    for (int h = 0; h < H; ++h) *attended += tiles[head_pattern_host ? head_pattern_host[h] : 0];
     return G3_OK;
 }
 

@@ -44,6 +44,17 @@
 // the rank's own rows [256 b, 256 b + 256): where r * S_local is a multiple of 256 they are the single-GPU blocks and the function is the single-GPU
 // one; otherwise the blocks that straddle a frame boundary differ, and with them (about one block in 14 at 3 520 tokens per frame) the function
 // depends on the number of ranks.
+// RNG (W4B_RNG 1 on top of W4B_CP 1: flash_attn_fwd_w4b_rng_kernel, with W4B_NM 1 flash_attn_fwd_w4b_nm_rng_kernel; g3_self_attn_fwd_ranges_bf16 only): the
+// logical-to-physical tile map of a workgroup comes from a TABLE - per (pattern, query block) an ascending list of at most 64 disjoint key ranges
+// (the function and the table's rules: gen3c_hip.h), the pattern picked per head. Prologue: lane r of every wave loads range r of the block's row,
+// converts it to (first tile, tiles) and CLAMPS it to the operand's S / 64 tiles - no address is ever formed from an unclamped table value, so a
+// corrupt table gives unspecified values in O and never an access outside K / V^T; lanes from the first empty range on hold zero, nt is the sum, an
+// empty list runs tile 0. The two table VGPRs stay resident. Tile loop: its asm statements are the plain kernel's; the compiler code at the tile head
+// keeps a cursor (range index, tiles left in the range, physical tile) for the K stream, two tiles ahead, advanced by SALU - a range change reads the
+// next range out of the two VGPRs with v_readlane at a scalar index - and the V^T stream's cursor, one tile ahead, is the K cursor's physical tile
+// of one tile earlier, taken before the K cursor advances. No memory operation enters the loop (tools/asm_audit.py holds the kernel to that, as it
+// does its siblings). Past the last logical tile the cursor stays on the last physical tile, as the plain kernel's clamp does. Plain V^T only, no
+// carry-in state, the CP form's epilogue and stores, no extra LDS.
 
 #ifndef G3_ATTENTION_W4B_HELPERS
 #define G3_ATTENTION_W4B_HELPERS
@@ -227,7 +238,14 @@ G3_DEVICE void w4b_mul_inplace(float& x, float a) { asm volatile("v_mul_f32 %0, 
 #if W4B_WIN && !W4B_CP
 #error "the window form is built on the CP form"
 #endif
-#if W4B_NM && W4B_WIN
+#if W4B_RNG && (!W4B_CP || W4B_WIN)
+#error "the range-table form is built on the CP form, without the window"
+#endif
+#if W4B_NM && W4B_RNG
+#define W4B_KERNEL flash_attn_fwd_w4b_nm_rng_kernel
+#elif W4B_RNG
+#define W4B_KERNEL flash_attn_fwd_w4b_rng_kernel
+#elif W4B_NM && W4B_WIN
 #define W4B_KERNEL flash_attn_fwd_w4b_nm_win_kernel
 #elif W4B_WIN
 #define W4B_KERNEL flash_attn_fwd_w4b_win_kernel
@@ -245,6 +263,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     constexpr bool CP = W4B_CP;
     constexpr bool NM = W4B_NM;
     constexpr bool WIN = W4B_WIN;
+    constexpr bool RNG = W4B_RNG;
     static_assert(!NM || XB, "the no-max form exists for the XB kernels only");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     bf16_t* sK = reinterpret_cast<bf16_t*>(smem_raw);  // [2][64][128]
@@ -279,7 +298,36 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     const float* carry_lse = nullptr;
     uint32_t skip_t0 = 0u, skip_nt = 0u, v_skip = 0u;
     int nt = p.Skv / KVB;  // launcher: S_kv % 64 == 0
-    if constexpr (WIN) {
+    // RNG: the block's ranges in tiles, range r in lane r (two VGPRs, resident through the tile loop), their number, and the K stream's cursor
+    uint32_t rng_first = 0u, rng_tiles = 0u, rng_n = 1u;
+    uint32_t kc_range = 0u, kc_left = 1u, kc_tile = 0u;
+    if constexpr (RNG) {
+        const uint32_t n_tiles = (uint32_t)p.Skv / KVB, max_ranges = (uint32_t)p.rng_max_ranges;
+        uint32_t pattern = 0u;
+        if (p.rng_head_pattern) pattern = min((uint32_t)p.rng_head_pattern[head], (uint32_t)p.rng_n_patterns - 1u);  // (clamped like the ranges)
+        const uint32_t row = pattern * (uint32_t)p.grid_q + (uint32_t)qblk;  // grid_q = n_qblk (launcher: the 1-D and the 3-D grid both set it)
+        if ((uint32_t)lane < max_ranges) {
+            const int2 e = reinterpret_cast<const int2*>(p.rng_table)[(int64_t)row * max_ranges + lane];
+            rng_first = min((uint32_t)e.x / KVB, n_tiles);              // the clamp: first_tile + n_tiles <= S / 64 (a negative value is a huge
+            rng_tiles = min((uint32_t)e.y / KVB, n_tiles - rng_first);  // unsigned one), whatever the table holds
+        }
+        const uint64_t empty = __ballot(rng_tiles == 0u);  // the first empty range ends the list
+        rng_n = empty ? (uint32_t)__builtin_ctzll(empty) : 64u;
+        if ((uint32_t)lane >= rng_n) rng_first = rng_tiles = 0u;
+        if (rng_n == 0u) {  // no tile at all: the one tile [0, 64)
+            rng_n = 1u;
+            if (lane == 0) rng_tiles = 1u;
+        }
+        rng_n = __builtin_amdgcn_readfirstlane(rng_n);
+        uint32_t sum = rng_tiles;  // the wave sum (a butterfly, not a loop: the first loop of this kernel is its tile loop, for tools/asm_audit.py too)
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sum += (uint32_t)__shfl_xor((int)sum, m);
+        nt = (int)__builtin_amdgcn_readfirstlane(sum);
+        kc_tile = __builtin_amdgcn_readlane(rng_first, 0);
+        kc_left = __builtin_amdgcn_readlane(rng_tiles, 0);
+        // (nt feeds the branch in front of the first LDS-DMA: the table load is retired before any LDS-DMA is issued)
+        asm volatile("" : "+s"(nt), "+s"(rng_n), "+s"(kc_tile), "+s"(kc_left), "+v"(rng_first), "+v"(rng_tiles));
+    } else if constexpr (WIN) {
         // the block's key set (launcher: the frame length a multiple of 64 that divides Sq; win_frames, win_sink <= frames): its rows lie in frames
         // f0..f1 of the win_total_frames of the sequence (row 0 of Q is frame win_q_frame0), the window is frames [f0 - W, f1 + W + 1) clipped to the
         // sequence, the sink frames [0, s). A sink that reaches the window leaves one range from key 0; no sink moves the K / V^T bases to the window;
@@ -326,6 +374,18 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     auto k_tile = [&](uint32_t t) -> uint32_t {  // physical K tile of logical tile t
         if constexpr (CP) return t + (t >= skip_t0 ? skip_nt : 0u);
         else return t;
+    };
+    // RNG: the cursor moves to the next logical tile - inside its range, or to the first tile of the next range (out of the table VGPRs); behind the
+    // last logical tile it stays where it is. Wave-uniform, SALU and two v_readlane.
+    auto rng_advance = [&]() {
+        if (kc_left > 1u) {
+            --kc_left;
+            ++kc_tile;
+        } else if (kc_range + 1u < rng_n) {
+            ++kc_range;
+            kc_tile = __builtin_amdgcn_readlane(rng_first, kc_range);
+            kc_left = __builtin_amdgcn_readlane(rng_tiles, kc_range);
+        }
     };
 
     // ---- Q fragments of both halves, pre-multiplied by scale * log2(e), into a[128:191]; O accumulators a[0:127] = 0 (as w4)
@@ -396,9 +456,18 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
     float xa[2], xb[2];                            // XB: exp2 results of a half unit between its two steps
 
     // ---- prologue: K(0), V(0) (and K(1)) by LDS-DMA; scores of tile 0 with C = 0, then made relative to their exact row maximum (NM: to the bound)
-    dma_tile_builtin(Kbytes, dma_off, sK);
-    dma_tile_builtin(Vbytes, dma_off + 4, sV);
-    if (nt > 1) dma_tile_builtin(Kbytes + k_tile(1u) * k_tile_bytes, dma_off, sK + KVB * HD);
+    if constexpr (RNG) {  // logical tiles 0 and 1 through the cursor, which then stands on tile 1: K(1)'s source here, V^T(1)'s at tile 0
+        dma_tile_builtin(Kbytes + kc_tile * k_tile_bytes, dma_off, sK);
+        dma_tile_builtin(Vbytes + kc_tile * (uint32_t)(KVB * 2), dma_off + 4, sV);
+        if (nt > 1) {
+            rng_advance();
+            dma_tile_builtin(Kbytes + kc_tile * k_tile_bytes, dma_off, sK + KVB * HD);
+        }
+    } else {
+        dma_tile_builtin(Kbytes, dma_off, sK);
+        dma_tile_builtin(Vbytes, dma_off + 4, sV);
+        if (nt > 1) dma_tile_builtin(Kbytes + k_tile(1u) * k_tile_bytes, dma_off, sK + KVB * HD);
+    }
     G3_JITTER(wave, blockIdx.x + 5);
     lds_dma_publish_barrier();
     G3_JITTER(wave + 2, blockIdx.x);
@@ -536,8 +605,16 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
         //      LDS-DMA piece I in steps 0..7: K(t+2) pieces 0..3 -> slot of K(t), V^T(t+1) pieces 0..3 -> slot of V^T(t-1)
         if constexpr (has_next) {
             const int t2 = min(t + 2, nt - 1);  // past the end: re-read the last tile (its slot is not consumed any more)
-            const char* kbase = Kbytes + k_tile((uint32_t)t2) * k_tile_bytes;
-            const char* vbase = Vbytes + v_off_next;
+            const char* kbase;
+            const char* vbase;
+            if constexpr (RNG) {  // the cursor stands on logical tile t + 1: V^T(t+1)'s source; one step on, K(t+2)'s
+                vbase = Vbytes + kc_tile * (uint32_t)(KVB * 2);
+                rng_advance();
+                kbase = Kbytes + kc_tile * k_tile_bytes;
+            } else {
+                kbase = Kbytes + k_tile((uint32_t)t2) * k_tile_bytes;
+                vbase = Vbytes + v_off_next;
+            }
             static_for<0, 16>([&](auto ic) {
                 constexpr int I = decltype(ic)::value;
                 using NR = std::integral_constant<int, I + D>;
@@ -569,7 +646,7 @@ __global__ __launch_bounds__(W4_THREADS, 1) void W4B_KERNEL(AttnParams p) {
             const bool wrap = (v_seg_pos + 1u == seg_tiles);
             v_off_next += wrap ? (uint32_t)(KVB * 2) + v_seg_jump : (uint32_t)(KVB * 2);
             v_seg_pos = wrap ? 0u : v_seg_pos + 1u;
-            if constexpr (CP) v_off_next += (uint32_t)(t + 2) == skip_t0 ? v_skip : 0u;  // whole segments: the position inside one is unchanged
+            if constexpr (CP && !RNG) v_off_next += (uint32_t)(t + 2) == skip_t0 ? v_skip : 0u;  // whole segments: the position inside one is unchanged
         }
         G3_JITTER(wave + blockIdx.x + 3, t);
         // ---- region B: O_h^T += V^T(t).P_h^T, step I: slice s = I >> 2, output block d = I & 3; pair units 20 + I in steps 0..11; the row-max

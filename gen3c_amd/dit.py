@@ -217,6 +217,7 @@ class VideoExtendGeneralDIT(nn.Module):
         mxfp8_producers: str = "separate",
         self_attn_window=None,
         self_attn_window_cp: bool = False,
+        self_attn_pattern=None,
     ) -> None:
         super().__init__()
         # the GEN3C-Cosmos-7B configuration space (config/base/net.py:23-43 + cosmos-1-diffusion-gen3c.py:38-43);
@@ -261,6 +262,9 @@ class VideoExtendGeneralDIT(nn.Module):
         self.self_attn_window_cp = False
         if self_attn_window is not None:
             self.set_self_attn_window(*self_attn_window, context_parallel=self_attn_window_cp)
+        self.self_attn_pattern = None
+        self._self_attn_tables = {}
+        self.set_self_attn_pattern(self_attn_pattern)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
         D, Hd = model_channels, self.head_dim
@@ -417,6 +421,36 @@ class VideoExtendGeneralDIT(nn.Module):
         if W >= Tp - 1 or s >= Tp:
             return None  # the window covers every frame: the dense launch
         return (Hp * Wp, W, s)
+
+    def set_self_attn_pattern(self, spec) -> None:
+        """None (default, the parity path): dense self-attention. ("radial", width1, sink_frames) | ("frame", W, s) (or the command lines' string,
+        "radial:0.25:1" / "frame:2:1"): training-free sparse attention - the single-GPU self-attention of every block runs ops.self_attn_ranges
+        over the range table gen3c_amd.sparse_attn builds for the forward's own (T, Hp * Wp), one pattern for all heads (per-head patterns stay an
+        ops-level capability: choosing heads needs trained weights, which do not exist here). The table is built, validated and uploaded once per
+        (shape, spec, device). A spec whose table covers every tile is the plain forward, bit for bit. Any frame length whose S is a multiple of 64
+        is accepted (720p's 45 x 80 = 3 600 tokens per frame included, which self_attn_window refuses). Picture quality: unmeasured (no trained
+        checkpoint). Not together with self_attn_window; not under context parallelism."""
+        from . import sparse_attn
+        self.self_attn_pattern = sparse_attn.check_spec(spec)
+
+    def _self_attn_table_for(self, Tp: int, Hp: int, Wp: int, device):
+        """The ops.AttnRangeTable of this forward's single-GPU self-attention launches, or None for the plain branch."""
+        spec = self.self_attn_pattern
+        if spec is None:
+            return None
+        if self.self_attn_window is not None:
+            raise ValueError(f"self_attn_pattern and self_attn_window are both set ({spec}, {self.self_attn_window}): choose one")
+        if self._cp_attn is not None:
+            raise ValueError(f"self_attn_pattern={spec} with context parallelism over {self.cp_size} ranks: range tables under key sharding are out of scope")
+        S = Tp * Hp * Wp
+        if S % 64 != 0:
+            raise ValueError(f"self_attn_pattern={spec}: S = {Tp} x {Hp} x {Wp} = {S} tokens is not a multiple of 64, the kernel's key tile")
+        key = (Tp, Hp * Wp, spec, str(device))
+        if key not in self._self_attn_tables:
+            from . import sparse_attn
+            table = ops.attn_range_table(sparse_attn.build_spec(spec, Tp, Hp * Wp), S, device=device)
+            self._self_attn_tables[key] = None if table.attended == table.dense else table  # every tile: the plain launch
+        return self._self_attn_tables[key]
 
     def set_mxfp8_producers(self, producers: str) -> None:
         """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16". Under "mxfp6" the setting is
@@ -662,6 +696,7 @@ class VideoExtendGeneralDIT(nn.Module):
         nH = self.num_heads
         ca_kv, ca_dense = self._cross_attention_kv(pk, crossattn_emb)
         fa_window = self._self_attn_window_for(Tp, Hp, Wp)
+        fa_table = self._self_attn_table_for(Tp, Hp, Wp, dev)
         if not self.cross_attention_skip_zero_context:
             ca_dense = 0
         for bi, blk in enumerate(pk["blocks"][: self._tune_blocks] if self._tune_blocks else pk["blocks"]):
@@ -728,6 +763,8 @@ class VideoExtendGeneralDIT(nn.Module):
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
                 if fa_window is not None:  # opt-in local attention (a bound out of the no-max form's range, or none: the same kernel with its running maximum)
                     o = ops.self_attn_window(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, *fa_window)
+                elif fa_table is not None:  # opt-in sparse attention over a range table (likewise)
+                    o = ops.self_attn_ranges(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, fa_table)
                 elif _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
                     o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"], mfma16=_self_attn_mfma16())
                 else:

@@ -539,6 +539,84 @@ def self_attn_window_cp(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, Sq: 
                       window_cp=(int(total_frames), int(q_frame0), int(buf_head_frames), int(buf_tail_frame0)))
 
 
+class AttnRangeTable:
+    """A validated range table of self_attn_ranges (attn_range_table makes it): `ranges` int32 [n_patterns, n_qblk, max_ranges, 2] and `head_pattern`
+    (int32 [H] or None) on the host, `ranges_dev` / `head_pattern_dev` their copies on the device, and (`attended`, `dense`): the (head, query
+    block, 64-key tile) triples a launch with H heads visits and the dense launch's count."""
+    __slots__ = ("ranges", "head_pattern", "ranges_dev", "head_pattern_dev", "S", "H", "n_patterns", "max_ranges", "attended", "dense")
+
+    @property
+    def tile_density(self) -> float:
+        return self.attended / self.dense
+
+
+def attn_range_table(ranges, S: int, head_pattern=None, H: Optional[int] = None, device=None) -> AttnRangeTable:
+    """ranges: a HOST int32 array [n_patterns, ceil(S / window_q_rows()), max_ranges, 2] of (first_key, n_keys) pairs (numpy or torch; the rules:
+    include/gen3c_hip.h, the builders: gen3c_amd/sparse_attn.py); head_pattern: the pattern of each of the H heads (default: pattern 0 for every
+    head, H = 1 if not given - H only scales the tile counts). Validated by g3_attn_ranges_check - a table that breaks a rule raises with the
+    pattern, block and range named - and uploaded ONCE to `device` (default: the current GPU); every self_attn_ranges launch reuses the copy."""
+    import ctypes
+    import numpy as np
+    host = ranges.cpu() if isinstance(ranges, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(ranges))
+    if host.dtype != torch.int32:
+        raise ValueError(f"attn_range_table: the table must be an int32 array, got {host.dtype}")
+    n_qblk = -(-int(S) // window_q_rows()) if S > 0 else 0
+    if host.dim() != 4 or host.shape[1] != n_qblk or host.shape[3] != 2:
+        raise ValueError(f"attn_range_table: expected [n_patterns, {n_qblk}, max_ranges, 2] for S = {S}, got {tuple(host.shape)}")
+    if not 1 <= host.shape[2] <= 64:
+        raise ValueError(f"attn_range_table: max_ranges {host.shape[2]} outside [1, 64]")
+    host = host.contiguous()
+    hp = None
+    if head_pattern is not None:
+        hp = torch.as_tensor(head_pattern, dtype=torch.int32).cpu().contiguous().flatten()
+        if H is not None and int(H) != hp.numel():
+            raise ValueError(f"attn_range_table: head_pattern has {hp.numel()} entries, H is {H}")
+        H = hp.numel()
+    H = 1 if H is None else int(H)
+    att, dense = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(_lib.load().g3_attn_ranges_check(host.data_ptr(), host.shape[0], int(S), host.shape[2], hp.data_ptr() if hp is not None else None, H,
+                                                ctypes.byref(att), ctypes.byref(dense)), "g3_attn_ranges_check")
+    t = AttnRangeTable()
+    t.ranges, t.head_pattern, t.S, t.H, t.n_patterns, t.max_ranges = host, hp, int(S), H, host.shape[0], host.shape[2]
+    t.attended, t.dense = att.value, dense.value
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    t.ranges_dev = host.to(dev)
+    t.head_pattern_dev = hp.to(dev) if hp is not None else None
+    return t
+
+
+def self_attn_ranges(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, S: int, B: int, H: int, logit_bound: float, table: AttnRangeTable,
+                     out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+    """Self-attention over a range table (opt-in sparse attention; g3_self_attn_fwd_ranges_bf16): q, k [S*B, H*128] with tokens ordered (t, h, w), vt
+    plain [B, H, 128, ldvt], table from attn_range_table for this S (and, with a head_pattern, this H). Every block of window_q_rows() query rows
+    attends the keys of its list in the pattern of its head - ranges_attn_mask is the function - and the output is the exact softmax over those
+    keys. logit_bound as for self_attn_bounded (out of range: the running-maximum form of the same kernel). The one-wave-per-SIMD kernel's
+    operand rules; no fallback."""
+    if not isinstance(table, AttnRangeTable):
+        raise ValueError("self_attn_ranges: table must come from ops.attn_range_table (which validates it)")
+    if table.S != S or (table.head_pattern is not None and table.H != H):
+        raise ValueError(f"self_attn_ranges: the table was made for S = {table.S}, H = {table.H}; the call has S = {S}, H = {H}")
+    if table.ranges_dev.device != q.device:
+        raise ValueError(f"self_attn_ranges: the table lives on {table.ranges_dev.device}, q on {q.device}")
+    return _attn_call("ranges", q, k, vt, S, S, B, H, out, softmax_scale, 11, False, logit_bound=logit_bound, ranges=table)
+
+
+def ranges_attn_mask(table_or_array, S: int, pattern: int = 0) -> torch.Tensor:
+    """CPU bool [S, S]: mask[i, j] = query row i attends key j under self_attn_ranges with `pattern` - the written-down definition of the function
+    (gen3c_hip.h): row i lies in query block i // window_q_rows(), whose list of (first_key, n_keys) ranges ends at the first n_keys == 0."""
+    import numpy as np
+    tab = table_or_array.ranges if isinstance(table_or_array, AttnRangeTable) else table_or_array
+    tab = tab if isinstance(tab, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tab))
+    q_rows = window_q_rows()
+    mask = torch.zeros(S, S, dtype=torch.bool)
+    for b, rl in enumerate(tab[pattern].tolist()):
+        for first, n in rl:
+            if n == 0:
+                break
+            mask[b * q_rows:(b + 1) * q_rows, first:first + n] = True
+    return mask
+
+
 def window_q_rows() -> int:
     """Query rows per block of the window form's key sets (the kernel's workgroup)."""
     return _lib.load().g3_self_attn_window_q_rows()
@@ -615,13 +693,16 @@ _ATTN_ENTRIES = {
     # (likewise: g3_attn_window_cp_plan_bf16)
     "window_cp": (None, "g3_self_attn_fwd_window_cp_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head") + _ASHAPE +
                   ("logit_bound", "frame_len", "total_frames", "q_frame0", "buf_head_frames", "buf_tail_frame0", "window_frames", "sink_frames")),
+    # (likewise: g3_attn_ranges_plan_bf16)
+    "ranges": (None, "g3_self_attn_fwd_ranges_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] +
+               ("logit_bound", "ranges", "n_patterns", "max_ranges", "head_pattern")),
 }
 _ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] + ("logit_bound", "variant"))
 
 
 def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
-               logit_bound=0.0, window=None, window_cp=None):
-    """The one marshaller of flash_attn, self_attn_bounded, self_attn_window and self_attn_window_cp, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
+               logit_bound=0.0, window=None, window_cp=None, ranges=None):
+    """The one marshaller of flash_attn, self_attn_bounded, self_attn_window, self_attn_window_cp and self_attn_ranges, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
     launch and the kernel timer."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
     skv_all = Skv + skip_len  # keys the operands hold
@@ -663,6 +744,10 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
         a.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2])
     if window_cp is not None:
         a.update(total_frames=window_cp[0], q_frame0=window_cp[1], buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3])
+    if ranges is not None:
+        assert vt.dim() == 4 and Sq == Skv, "the range-table form takes plain V^T and Sq == Skv"
+        a.update(ranges=_dev(ranges.ranges_dev, "ranges", torch.int32), n_patterns=ranges.n_patterns, max_ranges=ranges.max_ranges,
+                 head_pattern=_dev(ranges.head_pattern_dev, "head_pattern", torch.int32) if ranges.head_pattern_dev is not None else 0)
     entry_id, symbol, names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
     timer = None
@@ -687,6 +772,10 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
             meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], total_frames=window_cp[0], q_frame0=window_cp[1],
                         buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3], tile_density=attended / dense)
             meta["kernel"] = lib.g3_attn_window_cp_plan_bf16(*[a[n] for n in names]).decode()
+        elif entry == "ranges":
+            # (the table counts its own H heads; with no head_pattern every head runs pattern 0 and the density is the same for any H)
+            meta.update(n_patterns=ranges.n_patterns, max_ranges=ranges.max_ranges, tile_density=ranges.attended / ranges.dense)
+            meta["kernel"] = lib.g3_attn_ranges_plan_bf16(*[a[n] for n in names]).decode()
         else:
             plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
             meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()

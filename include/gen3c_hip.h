@@ -329,6 +329,40 @@ const char* g3_attn_window_cp_plan_bf16(const void* q, int64_t q_row, int64_t q_
 int g3_self_attn_window_cp_tiles(int Sq, int Skv_buf, int frame_len, int total_frames, int q_frame0, int buf_head_frames, int buf_tail_frame0,
                                  int window_frames, int sink_frames, int64_t* attended, int64_t* dense);
 
+/* Self-attention (Sq == Skv == S, S % 64 == 0) over a RANGE TABLE, for tokens ordered (t, h, w): opt-in, training-free sparse attention whose key set
+ * is, per block of query rows, a short list of contiguous key ranges - the shape of the published sparse patterns for video DiTs in this token order
+ * (a spatial band that narrows with frame distance, per-head spatial / temporal patterns, sliding tiles). Definitions:
+ *   query block b   rows [256 b, min(256 b + 256, S)); 256 = g3_self_attn_window_q_rows(); n_qblk = ceil(S / 256)
+ *   range table     int32 ranges[n_patterns][n_qblk][max_ranges][2] of (first_key, n_keys) pairs, 1 <= max_ranges <= 64 = g3_self_attn_ranges_max();
+ *                   n_keys == 0 ends a block's list
+ *   a valid list    has at least one range; first_key and n_keys are positive multiples of 64, except that first_key may be 0; it is ascending
+ *                   and disjoint, first_key[r + 1] >= first_key[r] + n_keys[r] (touching ranges are allowed and stay two ranges);
+ *                   first_key + n_keys <= S; the entries behind the terminator are zero
+ *   head_pattern    optional int32 [H], values in [0, n_patterns): the pattern of a head. NULL: pattern 0 for every head
+ * Every row of query block b of head h attends the keys of the list (head_pattern[h], b), and the output is the exact softmax over those keys, visited
+ * in list order. The function is block-granular and tile-granular by construction: nothing is masked in the kernel's tile loop.
+ * ranges and head_pattern are DEVICE pointers. flash_attn_fwd_w4b_nm_rng_kernel<true> (0 < logit_bound * log2(e) <= 60) or
+ * flash_attn_fwd_w4b_rng_kernel<true> (any other bound: the running-maximum form); always variant 11's family, never another kernel. The launch does not
+ * read the table on the host: validate it once with g3_attn_ranges_check before the upload. The kernel clamps every range (and the pattern index) to
+ * the operand, so a table that breaks the rules gives unspecified values in o and never an access outside K / V^T.
+ * G3_ERR_ARG, with nothing launched and one message each: S no positive multiple of 64; n_patterns < 1; max_ranges outside [1, 64]; a NULL or
+ * misaligned table (8 bytes; head_pattern 4); a V^T leading dimension below ceil64(S); operands beyond the kernel's 32-bit byte offsets over all S keys
+ * (g3_self_attn_fwd_window_bf16's arithmetic); misaligned pointers or strides; head_dim != 128.
+ * g3_attn_ranges_plan_bf16: the dry run - the kernel's name, or NULL with g3_last_error() set exactly as the call sets it; no HIP call, no pointer
+ * dereferenced. g3_attn_ranges_check: pure host code over HOST copies - every rule above, refused with a message that names the pattern, the block
+ * and the range; attended = the (head, query block, 64-key tile) triples a launch with H heads visits, dense = H * n_qblk * S / 64. */
+int g3_self_attn_fwd_ranges_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                 int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                 int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, float softmax_scale, float logit_bound,
+                                 const int32_t* ranges, int n_patterns, int max_ranges, const int32_t* head_pattern, void* stream);
+const char* g3_attn_ranges_plan_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                     int64_t k_head, const void* vt, int64_t vt_row, int64_t vt_batch, int64_t vt_head, void* o, int64_t o_row,
+                                     int64_t o_batch, int64_t o_head, int S, int B, int H, int head_dim, float softmax_scale, float logit_bound,
+                                     const int32_t* ranges, int n_patterns, int max_ranges, const int32_t* head_pattern);
+int g3_attn_ranges_check(const int32_t* ranges_host, int n_patterns, int S, int max_ranges, const int32_t* head_pattern_host, int H, int64_t* attended,
+                         int64_t* dense);
+int g3_self_attn_ranges_max(void);
+
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);

@@ -38,7 +38,7 @@ def _back_branch(v, hdr):
 
 # the one-wave-per-SIMD instantiations attention.hip launches: each must be in the assembly (and is then audited like every flash_attn_fwd kernel found there)
 W4B_KERNELS = ("w4b_kernel<Lb0E>", "w4b_kernel<Lb1E>", "w4b_carry_kernel<Lb1E>", "w4b_nm_kernel<Lb1E>", "w4b_nm_carry_kernel<Lb1E>",
-               "w4b_win_kernel<Lb1E>", "w4b_nm_win_kernel<Lb1E>", "w4c_nm_kernel<>")  # (names as audit() forms them; w4c: attention_w4c.hpp, not a template)
+               "w4b_win_kernel<Lb1E>", "w4b_nm_win_kernel<Lb1E>", "w4b_rng_kernel<Lb1E>", "w4b_nm_rng_kernel<Lb1E>", "w4c_nm_kernel<>")  # (names as audit() forms them; w4c: attention_w4c.hpp, not a template)
 
 
 def audit(asm_text: str):

@@ -4,7 +4,8 @@ boundaries) and demands BITWISE equal outputs.
   build (here, before gpurun):  python tools/race_screen.py --build [n]
   run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]
                                                             [--bounded-cp-only: the no-max key-sharded attention section alone]
-                                                            [--mfma16-only: the 16x16x32 no-max attention section alone]"""
+                                                            [--mfma16-only: the 16x16x32 no-max attention section alone]
+                                                            [--ranges-only: the range-table attention section alone]"""
 import ctypes as C
 import math
 import os
@@ -39,7 +40,8 @@ g = torch.Generator(device=dev).manual_seed(3)
 bad = 0
 ONLY_BCP = "--bounded-cp-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded_cp_bf16
 ONLY_W4C = "--mfma16-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded16_bf16
-ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP or ONLY_W4C  # run only the last section (the launches that emit MXFP8)
+ONLY_RNG = "--ranges-only" in sys.argv  # run only the section of g3_self_attn_fwd_ranges_bf16
+ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP or ONLY_W4C or ONLY_RNG  # run only the last section (the launches that emit MXFP8)
 
 
 def both(fn):
@@ -279,10 +281,34 @@ if "--no-tokenizer" not in sys.argv and not ONLY_MX:
         report(f"tokenizer {what} 121x704x1280 channels=128, product vs jitter build", outs[0][i], outs[1][i])
         report(f"tokenizer {what} 121x704x1280 channels=128, product run twice", outs[0][i], outs[2][i])
     del outs, clip, tnet
+# ---- range-table self-attention (g3_self_attn_fwd_ranges_bf16): both kernel forms on the three shapes of tests/test_attn_ranges_gpu.py (its hand-made tables:
+# one to three tiles per block; random lists under a head-to-pattern lookup on the 3-D grid; 64 one-tile ranges on the 1-D grid) - the cursor's range changes
+# sit between the statements whose LDS hand-offs the jitter stretches
+if not (ONLY_BCP or ONLY_W4C or "--mxfp8-producers-only" in sys.argv):
+    from tests.test_attn_ranges_gpu import _shape as rng_shape
+    for i in (1, 2, 3):
+        S_, B_, H_, tab, hp = rng_shape(i)
+        table = ops.attn_range_table(tab, S_, head_pattern=hp, H=H_)
+        q = torch.randn(S_ * B_, H_ * 128, device=dev, generator=g).to(torch.bfloat16)
+        k = torch.randn(S_ * B_, H_ * 128, device=dev, generator=g).to(torch.bfloat16)
+        vt = ops.transpose_v(torch.randn(S_ * B_, H_ * 128, device=dev, generator=g).to(torch.bfloat16), S_, B_, H_)
+        ld = vt.shape[-1]
+        for bound in (20.0, 0.0):  # (q, k are not normalised here: |q . k| / sqrt(128) is N(0, 1), far below 20; 0: the running-maximum form)
+            def run(lib):
+                o = torch.zeros(S_ * B_, H_ * 128, device=dev, dtype=torch.bfloat16)
+                rc = lib.g3_self_attn_fwd_ranges_bf16(q.data_ptr(), B_ * H_ * 128, H_ * 128, 128, k.data_ptr(), B_ * H_ * 128, H_ * 128, 128, vt.data_ptr(), ld,
+                                                      H_ * 128 * ld, 128 * ld, o.data_ptr(), B_ * H_ * 128, H_ * 128, 128, S_, B_, H_, 128, 1.0 / math.sqrt(128),
+                                                      bound, table.ranges_dev.data_ptr(), table.n_patterns, table.max_ranges,
+                                                      table.head_pattern_dev.data_ptr() if table.head_pattern_dev is not None else None, st)
+                assert rc == 0, lib.g3_last_error()
+                return o
+            a, b = both(run)
+            report(f"self_attn_ranges shape {i}: S={S_} B={B_} H={H_} max_ranges={table.max_ranges} {'no-max' if bound else 'running-max'} form", a, b)
+        del q, k, vt
 # ---- the producers that emit MXFP8 from their registers (mxfp8_producers = "fused"): the GEMM with MXFP8 output (its K loop carries the jitter; the epilogue
 # transposes through each wave's own LDS slice and quantises across lane quads) and the two LayerNorm forms, plain and with the position embedding
 LN_WAVE_START = int(os.environ.get("G3_LN_WAVE_ROWS", "0"))  # what both libraries start with (csrc/api.hip); restored after each case
-for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C) else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
+for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG) else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
     aq, as_ = ops.quant_mxfp8(torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16))
     wq, ws = ops.quant_mxfp8((torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16))
 
@@ -296,7 +322,7 @@ for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C) else [(14080, 16384, 4096, 1)
     a, b = both(run)
     report(f"gemm_mxfp8 with MXFP8 output {M}x{N}x{K} epi{epi}", a, b)
     del aq, as_, wq, ws
-for (T_, Hp, Wp, B_, D_, wave) in [] if (ONLY_BCP or ONLY_W4C) else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
+for (T_, Hp, Wp, B_, D_, wave) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG) else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
     rows = T_ * Hp * Wp * B_
     x_ = torch.randn(rows, D_, device=dev, generator=g).to(torch.bfloat16)
     pe = (0.3 * torch.randn(T_ * Hp * Wp, D_, device=dev, generator=g)).to(torch.bfloat16)
