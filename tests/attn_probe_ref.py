@@ -23,9 +23,17 @@ sits on the keys of its class) and the staircase's s_j = step t / 32 is bf16-exa
  * staircase        one class: q = 2 Hd[0], k_j = s_j Hd[0] with the log2-domain logit step * t, t = j // 64 ascending or descending over the tiles, and
                     V[j, d] = (d == j // 64): output column d is the softmax mass of tile d. s_j is rounded to bf16 and the reference uses the rounded value.
 
+Range tables (g3_self_attn_fwd_ranges_bf16). With the default 128 classes a 64-key tile holds half of them, and a block that attends one tile leaves
+rows without a key of their class; the range family therefore takes classes = 64 (RANGE_CLASSES): every tile holds every class, census-block's V
+column of key j is j // 64, its tile, and output element (i, d) is 1 / n iff tile d is in the list of row i's block (n attended tiles) - every (head,
+query block, tile) triple of a launch owns an output element. ranges_mask / head_masks write the function down from gen3c_hip.h, range_walks the
+kernel's walk (and nine defects of it), range_shape the shapes and tables that the CPU and the GPU test share.
+
 Tensors are [S, B, H, 128] fp64 on the CPU; `flat` gives the kernels' [S*B, H*128] layout (rows (s, b), b fastest)."""
+import functools
 import math
 
+import numpy as np
 import torch
 
 HD = 128
@@ -119,8 +127,8 @@ def census_block(Sq, Skv, B, H, q_scale=2.0, classes=None):
     return Probe("census-block", q, k, _onehot_v(Skv, B, H, torch.arange(Skv) // C), qc, C)
 
 
-def uniform(Sq, Skv, B, H):
-    _q, k, _qc, C = _census_qk(Sq, Skv, B, H)
+def uniform(Sq, Skv, B, H, classes=None):
+    _q, k, _qc, C = _census_qk(Sq, Skv, B, H, classes=classes)
     return Probe("uniform", torch.zeros(Sq, B, H, HD, dtype=torch.float64), k, _onehot_v(Skv, B, H, torch.arange(Skv) // C))
 
 
@@ -148,7 +156,8 @@ def fp32_scale_log2(softmax_scale):
 
 
 def reference(p, mask=None, check_leak=True, softmax_scale=SOFTMAX_SCALE, fold_q=False):
-    """fp64 softmax attention of probe p under the bool mask [Sq, Skv] (None: every key) -> (out [Sq, B, H, 128], lse [B, H, Sq] in the log2 domain).
+    """fp64 softmax attention of probe p under the bool mask [Sq, Skv] or, one per head, [H, Sq, Skv] (None: every key) -> (out [Sq, B, H, 128],
+    lse [B, H, Sq] in the log2 domain).
     Asserts that all but 1e-6 of every row's weight lies on the keys of the query's class.
     fold_q: of the inputs the folding kernels' MFMAs see - q * fp32 scale_log2 rounded to bf16 (identical at SOFTMAX_SCALE, where that is exact)."""
     if fold_q:
@@ -157,8 +166,8 @@ def reference(p, mask=None, check_leak=True, softmax_scale=SOFTMAX_SCALE, fold_q
     else:
         sc = torch.einsum("sbhd,kbhd->bhsk", p.q, p.k) * softmax_scale
     if mask is not None:
-        assert mask.shape == (p.Sq, p.Skv) and bool(mask.any(dim=1).all()), "every query row needs an attended key"
-        sc = sc.masked_fill(~mask[None, None], -math.inf)
+        assert mask.shape in ((p.Sq, p.Skv), (p.H, p.Sq, p.Skv)) and bool(mask.any(dim=-1).all()), "every query row needs an attended key"
+        sc = sc.masked_fill(~(mask[None, None] if mask.dim() == 2 else mask[None]), -math.inf)
     lse = torch.logsumexp(sc, dim=-1)
     w = torch.exp(sc - lse[..., None])
     if check_leak and p.q_class is not None:
@@ -171,9 +180,20 @@ def reference(p, mask=None, check_leak=True, softmax_scale=SOFTMAX_SCALE, fold_q
 
 
 def keys_all_owned(p, mask=None):
-    """census-block: every (attended) key owns a nonzero reference element in some query row of some (batch, head)"""
+    """census-block: every (attended) key owns a nonzero reference element in some query row of some (batch, head); under a per-head mask
+    [H, Sq, Skv]: every key a head attends owns one in some query row of some batch OF THAT HEAD"""
     out, _ = reference(p, mask)
     C = p.C
+    if mask is not None and mask.dim() == 3:
+        j = torch.arange(p.Skv)
+        for h in range(p.H):
+            owned = torch.zeros(p.Skv, dtype=torch.bool)
+            for b in range(p.B):
+                hit = mask[h] & (p.q_class[:, b, h][:, None] == (j % C)[None, :])
+                owned |= (hit & (out[:, b, h, :][:, j // C] > SMALL_REF)).any(dim=0)
+            if not bool(owned[mask[h].any(dim=0)].all()):
+                return False
+        return True
     owned = torch.zeros(p.Skv, dtype=torch.bool)
     att = torch.ones(p.Sq, p.Skv, dtype=torch.bool) if mask is None else mask
     j = torch.arange(p.Skv)
@@ -262,16 +282,170 @@ def window_mask(S, frame_len, W, s, q_row0=0, T_total=None, hi_shift=0):
     return m
 
 
+# ---- range tables (g3_self_attn_fwd_ranges_bf16) ---------------------------------------------------------------------------------------------------------
+# Lists are in TILES: lists[pattern][block] = [(first_tile, n_tiles), ...], ascending and disjoint, without the terminator.
+
+def random_list(rng, n_tiles, max_n):
+    """1..max_n ascending disjoint (first_tile, n_tiles) ranges of random lengths; about a third of the neighbours touch"""
+    n = int(rng.randint(1, max_n + 1))
+    pos, out = int(rng.randint(0, max(1, n_tiles // 3))), []
+    for _ in range(n):
+        ln = int(rng.randint(1, 5))
+        if pos + ln > n_tiles:
+            break
+        out.append((pos, ln))
+        pos += ln + int(rng.choice([0, 1, 2, int(rng.randint(1, max(2, n_tiles // 4)))]))
+    return out or [(n_tiles - 1, 1)]
+
+
+def pack(lists, max_ranges):
+    """lists[pattern][block] = [(first_tile, n_tiles), ...] -> int32 [n_patterns, n_qblk, max_ranges, 2] in keys"""
+    t = np.zeros((len(lists), len(lists[0]), max_ranges, 2), dtype=np.int32)
+    for p, blocks in enumerate(lists):
+        for b, rl in enumerate(blocks):
+            assert 1 <= len(rl) <= max_ranges
+            t[p, b, :len(rl)] = np.asarray(rl, dtype=np.int32) * KVB
+    return t
+
+
+def ranges_mask(lists, S, q_rows=Q_ROWS):
+    """bool [S, S] of ONE pattern's lists - gen3c_hip.h's definition: every row of query block b, rows [q_rows b, min(q_rows b + q_rows, S)), attends
+    the keys [64 first_tile, 64 (first_tile + n_tiles)) of every range of the block's list, and no other key"""
+    assert S % KVB == 0 and len(lists) == (S + q_rows - 1) // q_rows
+    m = torch.zeros(S, S, dtype=torch.bool)
+    for b, rl in enumerate(lists):
+        assert len(rl) >= 1
+        for first, n in rl:
+            assert first >= 0 and n >= 1 and (first + n) * KVB <= S
+            m[b * q_rows:min((b + 1) * q_rows, S), first * KVB:(first + n) * KVB] = True
+    return m
+
+
+def head_masks(lists, head_pattern, S):
+    """[H, S, S]: the mask of every head's pattern"""
+    by_pattern = [ranges_mask(blocks, S) for blocks in lists]
+    return torch.stack([by_pattern[p] for p in head_pattern])
+
+
+def ranges_counts(lists, head_pattern, S):
+    """(attended, dense): the (head, query block, tile) triples of a launch, counted from the lists, and H * n_qblk * S / 64"""
+    return sum(n for p in head_pattern for rl in lists[p] for _f, n in rl), len(head_pattern) * len(lists[0]) * (S // KVB)
+
+
+def _list_walk(rl, n_tiles, defect):
+    """the (k_tile, vt_tile) steps of one block's list as the kernel walks it: lane r holds range r, nt is the sum of the lengths, a cursor runs through
+    the ranges for K, and V^T(t) is read where the K cursor stood one tile earlier. Every tile index is clamped to the operand, as the kernel's are."""
+    rl = list(rl)
+    if defect == "range_list_short" and len(rl) > 1:
+        rl = rl[:-1]
+    if defect == "range_lane_wrap":
+        rl = [rl[r - 32] if r >= 32 else rl[r] for r in range(len(rl))]
+    nt = sum(n for _f, n in (rl[:32] if defect == "range_sum_half" else rl))
+    kt, opens = [], []
+    for r, (first, n) in enumerate(rl):
+        late = 1 if (defect == "range_starts_late" and r > 0) else 0
+        for i in range(n):
+            kt.append(min(first + i + late, n_tiles - 1))
+            opens.append(r if i == 0 else 0)  # (the index of the range this step opens, 0: none or the first)
+    vt = list(kt)
+    if defect == "vt_follows_old_range":
+        vt = [rl[r - 1][0] + rl[r - 1][1] if r else t for t, r in zip(kt, opens)]
+    if defect == "vt_same_step":  # V^T(0) is the prologue's; behind the last tile the cursor stays
+        vt = [kt[0]] + [kt[min(t + 1, len(kt) - 1)] for t in range(1, len(kt))]
+    return list(zip(kt, vt))[:nt]
+
+
+def range_walks(lists, head_pattern, B, S, defect=None):
+    """walks[batch][head][block] for emulate_walks: the clean kernel (defect None: every listed tile once, in list order, K and V^T alike) or one of
+    RANGE_DEFECTS. pattern_by_grid_index: head_pattern read at the (batch, head) pair index, clamped to the array."""
+    H, walks = len(head_pattern), []
+    for b in range(B):
+        per_head = []
+        for h in range(H):
+            pat = head_pattern[h]
+            if defect == "pattern_zero":
+                pat = 0
+            if defect == "pattern_by_grid_index":
+                pat = head_pattern[min(b * H + h, H - 1)]
+            blocks = list(lists[pat])
+            if defect == "last_block_uses_first":
+                blocks[-1] = blocks[0]
+            per_head.append([_list_walk(rl, S // KVB, defect) for rl in blocks])
+        walks.append(per_head)
+    return walks
+
+
+def emulate_walks(q, k, v, walks, **kw):
+    """emulate(walk=...) with walks[batch][head][block]: one call where every batch walks alike, else one per batch"""
+    if all(w == walks[0] for w in walks):
+        return emulate(q, k, v, walk=walks[0], **kw)
+    parts = [emulate(q[:, b:b + 1], k[:, b:b + 1], v[:, b:b + 1], walk=w, **kw) for b, w in enumerate(walks)]
+    return torch.cat([o for o, _l in parts], dim=1), torch.cat([l for _o, l in parts], dim=0)
+
+
+# Family 7 of tests/test_attn_probes_gpu.py, and what tests/test_attn_probe_ref_cpu.py proves about it: the shapes, tables and probes, in one place.
+RANGE_CLASSES = KVB  # every 64-key tile holds every class, and the census-block V column of key j is its tile: element (i, d) is 1 / n iff tile d is in row i's list
+RANGE_HEAD_PATTERNS = {(1, 8): (0, 1, 2, 1, 1, 0, 2, 0), (2, 3): (2, 0, 1), (1, 2): (1, 0)}  # not monotone, the last pattern used, one pattern on two heads
+RANGE_STAIRS_AT = (2, 3)
+RANGE_SHAPES = ("a", "b", "c")
+
+
+@functools.lru_cache(maxsize=None)
+def range_shape(name):
+    """-> dict(S, max_ranges, lists, bhs, probes, stairs): the smallest shapes at which each mechanism of the range kernels exists"""
+    if name == "a":  # three full blocks and a 64-row block, 13 tiles: nt = 1, 2, 3; the prologue's K(1) out of a second range; the operand's last tile
+        rng = np.random.RandomState(832)
+        lists = [[[(0, 1)], [(0, 1), (2, 1)], [(1, 1), (5, 1), (12, 1)], [(0, 2), (3, 1), (6, 7)]],
+                 [[(12, 1)], [(0, 13)], [(3, 2), (5, 2)], [(11, 2)]],
+                 [random_list(rng, 13, 8) for _b in range(4)]]
+        return dict(S=832, max_ranges=8, lists=lists, bhs=((1, 8), (2, 3)), probes=("census-position", "census-block", "uniform"), stairs=True)
+    if name == "b":  # random lists of 1 to 6 ranges over 30 tiles, 7 full blocks and one of 128 rows
+        rng = np.random.RandomState(1920)
+        lists = [[random_list(rng, 30, 6) for _b in range(8)] for _p in range(3)]
+        flat_ = [rl for p in lists for rl in p]
+        assert any(a[0] + a[1] == b[0] for rl in flat_ for a, b in zip(rl, rl[1:])), "some ranges touch"
+        assert any(a[0] + a[1] < b[0] for rl in flat_ for a, b in zip(rl, rl[1:])), "some ranges jump"
+        assert {len(rl) for rl in flat_} >= {1, 2} and max(len(rl) for rl in flat_) >= 5
+        return dict(S=1920, max_ranges=6, lists=lists, bhs=((1, 8), (2, 3)), probes=("census-position", "census-block"), stairs=False)
+    assert name == "c"  # 65 tiles, 16 full blocks and a 64-row one, 64 ranges: table lanes >= 32 in the load, the butterfly and the lane read
+    rng = np.random.RandomState(4160)
+    p0 = [[(t, 1) for t in range(65) if t != (7 * b + 3) % 65] for b in range(17)]  # a cursor step on every tile and one jump
+    p0[5] = [(t, 1) for t in range(63)]
+    p0[9] = [(0, 65)]
+    p0[13] = [(2 * t, 1) for t in range(33)]
+    assert all(len(rl) == 64 for b, rl in enumerate(p0) if b not in (5, 9, 13)) and len(p0[16]) == 64
+    lists = [p0, [random_list(rng, 65, 10) for _b in range(17)]]
+    return dict(S=4160, max_ranges=64, lists=lists, bhs=((1, 2),), probes=("census-block", "census-position"), stairs=False)
+
+
+def range_cases():
+    """(shape name, B, H) of every launch group of family 7"""
+    return [(name, B, H) for name in RANGE_SHAPES for B, H in range_shape(name)["bhs"]]
+
+
+def range_probe(kind, S, B, H):
+    """a probe of family 7: a name of the census / uniform probes at RANGE_CLASSES classes, or a (step, descending) staircase"""
+    if isinstance(kind, tuple):
+        return staircase(S, S, B, H, *kind)
+    return {"census-position": census_position, "census-block": census_block, "uniform": uniform}[kind](S, S, B, H, classes=RANGE_CLASSES)
+
+
 # ---- emulation of the kernels' arithmetic -------------------------------------------------------------------------------------------------------------
 
+RANGE_DEFECTS = ("range_starts_late", "range_list_short", "range_lane_wrap", "range_sum_half", "vt_follows_old_range", "vt_same_step", "pattern_zero",
+                 "pattern_by_grid_index", "last_block_uses_first")  # made by the caller through another walk: range_walks(defect=...)
 DEFECTS = ("drop_last_key", "dup_seam_key", "pad_scored_zero", "swap_vt_cols", "skip_o_rescale", "skip_l_rescale", "window_short", "window_long",
-           "skip_shifted", "lse_without_log2_l", "bh_strides_swapped")
+           "skip_shifted", "lse_without_log2_l", "bh_strides_swapped") + RANGE_DEFECTS
 
 
-def emulate(q, k, v, mask=None, bound_log2=None, defect=None, partial=False, carry=None, softmax_scale=SOFTMAX_SCALE, fold_q=False):
+def emulate(q, k, v, mask=None, bound_log2=None, defect=None, partial=False, carry=None, softmax_scale=SOFTMAX_SCALE, fold_q=False, walk=None,
+            q_rows=Q_ROWS):
     """A tile loop with the kernels' number formats: 64-key tiles, fp32 scores in the log2 domain, a running row maximum (bound_log2 None) or the
     constant bound as the reference point, P rounded to bf16 into P V, l summed in fp32 from the unrounded P, then out = O / l as bf16 (or fp32 with
-    partial=True) and lse = m + log2 l. q [Sq, B, H, 128], k / v [Skv, B, H, 128] hold bf16-exact values; mask [Sq, Skv] bool or None.
+    partial=True) and lse = m + log2 l. q [Sq, B, H, 128], k / v [Skv, B, H, 128] hold bf16-exact values; mask [Sq, Skv] or [H, Sq, Skv] bool or None.
+    walk (in place of a mask): walk[h][block] = the ordered (k_tile, vt_tile) pairs that the block of q_rows query rows of head h visits - K and V^T
+    of one step may come from different tiles and a tile may be visited twice, neither of which a mask can say. Each (head, block) is the same
+    tile loop over its tiles gathered in that order.
     carry = (o fp32 [Sq, B, H, 128], lse [B, H, Sq]): the carry-in fold of g3_flash_attn_fwd_carry_bf16.
     fold_q: the scale rides on Q - q * scale_log2 rounded to bf16 before the products, as the w4 / w4b / w4c and folded v3 kernels do.
     defect: one of DEFECTS that this function implements itself (the mask defects are made by the caller through another mask).
@@ -279,6 +453,19 @@ def emulate(q, k, v, mask=None, bound_log2=None, defect=None, partial=False, car
     Sq, B, H, _ = q.shape
     Skv = k.shape[0]
     f32 = torch.float32
+    if walk is not None:
+        assert mask is None and carry is None and defect is None and len(walk) == H
+        out, lse = torch.empty(Sq, B, H, HD, dtype=f32), torch.empty(B, H, Sq, dtype=f32)
+        tile = torch.arange(KVB)
+        for h in range(H):
+            assert len(walk[h]) == (Sq + q_rows - 1) // q_rows
+            for blk, steps in enumerate(walk[h]):
+                rows = slice(blk * q_rows, min((blk + 1) * q_rows, Sq))
+                kt, vt = (torch.cat([t[i] * KVB + tile for t in steps]) for i in (0, 1))
+                o, l = emulate(q[rows, :, h:h + 1], k[kt][:, :, h:h + 1], v[vt][:, :, h:h + 1], bound_log2=bound_log2, partial=partial,
+                               softmax_scale=softmax_scale, fold_q=fold_q)
+                out[rows, :, h:h + 1], lse[:, h:h + 1, rows] = o, l
+        return out, lse
     if defect == "bh_strides_swapped":  # element (b, h) read at batch stride H' = 1, head stride B: pair index h * B + b in place of b * H + h
         perm = torch.tensor([(idx % H) * B + idx // H for idx in range(B * H)])
         swap = lambda x: x.reshape(x.shape[0], B * H, HD)[:, perm].reshape(x.shape[0], B, H, HD)
@@ -307,11 +494,11 @@ def emulate(q, k, v, mask=None, bound_log2=None, defect=None, partial=False, car
         s = (qf @ kf[:, :, idx].transpose(-1, -2)) * c  # [B, H, Sq, 64] fp32
         att = valid[None, :].expand(Sq, KVB)
         if mask is not None:
-            att = att & mask[:, idx]
+            att = att & mask[..., idx]  # ([H, Sq, 64] under a per-head mask)
         if defect == "pad_scored_zero":
             s = torch.where(valid[None, None, None, :], s, torch.zeros((), dtype=f32))
             att = att | ~valid[None, :]
-        s = s.masked_fill(~att[None, None], -math.inf)
+        s = s.masked_fill(~(att[None, None] if att.dim() == 2 else att[None]), -math.inf)
         vt = vf[:, :, vidx] * valid[None, None, :, None].to(f32)  # V^T's zero tail
         if bound_log2 is None:
             m_new = torch.maximum(m, s.max(dim=-1).values)

@@ -4,9 +4,14 @@
    the query's class, and in the census-block probe every (attended) key of every GPU case owns a nonzero reference element;
  * a clean emulation of the kernels' arithmetic (64-key tiles, fp32 log2-domain scores, running maximum or constant bound, bf16 P, fp32 l from the
    unrounded P, bf16 output, LSE) meets every bar of tests/test_attn_probes_gpu.py at every shape that file runs;
- * each of eleven defects planted into the emulation fails at least one probe;
+ * each of twenty defects planted into the emulation fails at least one probe;
  * the same defects on Gaussian inputs at 2 209 and 4 160 keys against the rel-L2 < 1e-2 bar of the older attention tests: printed, not gated
-   (the list of defects that bar lets through is why the probes exist)."""
+   (the list of defects that bar lets through is why the probes exist);
+ * the range-table family (family 7 of tests/test_attn_probes_gpu.py) at exactly its shapes, tables and probes (R.range_shape, R.range_probe): the
+   probes at 64 classes are exact, leak-free under every head's mask, own every attended key, and census-block's element (i, d) is 1 / n iff tile d
+   is in row i's list; the clean emulation meets every bar in both forms and its explicit walk gives the bits of its mask; each of the nine range
+   defects (R.RANGE_DEFECTS: another walk) fails a named probe BY ITS OUTPUT, and is reported against the Gaussian rel-L2 bar of 4e-3 that
+   tests/test_attn_ranges_gpu.py holds the range kernels to."""
 import functools
 import math
 
@@ -168,10 +173,92 @@ def test_why_the_probes_do_not_run_at_the_default_scale():
             assert abs(d - 0.1055) < 2e-4
 
 
+# ---- range tables: family 7's probes, at its shapes ----------------------------------------------------------------------------------------------------
+
+def _range_kinds(name, B, H):
+    sh = R.range_shape(name)
+    return tuple(sh["probes"]) + (STAIRS if sh["stairs"] and (B, H) == R.RANGE_STAIRS_AT else ())
+
+
+def _range_forms(kind, S):
+    """(log2-domain bound or None, bar) of the two kernel forms: the rule of tests/test_attn_probes_gpu.py (_rel_for, _stair_bound)"""
+    stair = isinstance(kind, tuple)
+    forms = [(None, R.REL_BF16 if stair else R.REL_EXACT_P)]
+    bound = R.staircase_bound_nats(kind[0], S) * R.LOG2E if stair else BOUND_LOG2
+    return forms + ([(bound, R.REL_BF16)] if bound <= 60.0 else [])
+
+
+@functools.lru_cache(maxsize=None)
+def _range_ref(name, B, H, kind):
+    """(probe, per-head masks, fp64 reference, LSE): built once, shared, never written"""
+    sh = R.range_shape(name)
+    p = R.range_probe(kind, sh["S"], B, H)
+    masks = R.head_masks(sh["lists"], R.RANGE_HEAD_PATTERNS[B, H], sh["S"])
+    return (p, masks) + R.reference(p, masks)  # (asserts the leakage)
+
+
+@pytest.mark.parametrize("name,B,H", R.range_cases())
+def test_range_probes_are_exact_leak_free_and_every_tile_is_owned(name, B, H):
+    from gen3c_amd import ops
+    sh = R.range_shape(name)
+    S, lists, hp = sh["S"], sh["lists"], R.RANGE_HEAD_PATTERNS[B, H]
+    assert len(hp) == H and set(hp) == set(range(len(lists))) and list(hp) != sorted(hp)  # every pattern, the last one too, and not in order
+    assert len(set(hp)) < H or H <= len(lists)  # two heads on one pattern wherever there are more heads than patterns
+    for pat, blocks in enumerate(lists):  # the helper's mask, written from the header's definition, is the library's
+        assert torch.equal(R.ranges_mask(blocks, S), ops.ranges_attn_mask(R.pack(lists, sh["max_ranges"]), S, pattern=pat))
+    for kind in _range_kinds(name, B, H):
+        p, masks, ref, lse = _range_ref(name, B, H, kind)
+        for t in (p.q, p.k, p.v):
+            assert torch.equal(t.to(torch.bfloat16).double(), t)
+        assert bool(torch.isfinite(ref).all()) and bool(torch.isfinite(lse).all())
+        assert float((ref.sum(-1) - 1).abs().max()) < 1e-12
+        if p.name != "census-block":
+            continue
+        assert p.C == R.RANGE_CLASSES and R.keys_all_owned(p, masks), (name, B, H)
+        # the closed form: every (head, query block, tile) triple of the launch owns the element (row, tile) of every row of the block
+        want = masks[:, :, ::R.KVB].double()  # [H, S, tiles]: tile d in row i's list
+        want = (want / want.sum(-1, keepdim=True)).permute(1, 0, 2)[:, None].expand(S, B, H, S // R.KVB)
+        assert float((ref[..., :S // R.KVB] - want).abs().max()) < 1e-6 and float(ref[..., S // R.KVB:].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("name,B,H", R.range_cases())
+def test_clean_range_emulation_meets_every_bar_and_its_walk_gives_the_bits_of_its_mask(name, B, H):
+    sh = R.range_shape(name)
+    walks = R.range_walks(sh["lists"], R.RANGE_HEAD_PATTERNS[B, H], B, sh["S"])
+    worst = 0.0
+    for kind in _range_kinds(name, B, H):
+        p, masks, ref, ref_lse = _range_ref(name, B, H, kind)
+        for bound, rel in _range_forms(kind, sh["S"]):
+            out, lse = R.emulate(p.q, p.k, p.v, mask=masks, bound_log2=bound)
+            assert _passes(p, out, lse, ref, ref_lse, rel), (name, p.name, B, H, bound, R.first_bad(out, ref, rel))
+            out_w, lse_w = R.emulate_walks(p.q, p.k, p.v, walks, bound_log2=bound)
+            assert torch.equal(out_w, out) and torch.equal(lse_w, lse), (name, p.name, B, H, bound)
+            worst = max(worst, R.out_errors(out, ref, rel)[1])
+    print(f"[range emulation {name} B={B} H={H}] worst relative element error {worst:.3e}")
+
+
+def _range_defect_runs(defect):
+    """shape (a) in both forms, (b) and (c) with a running maximum; a case whose defective walk IS the clean one (lanes >= 32 on a short table, the
+    pair index at B = 1) is left out"""
+    for name, B, H in R.range_cases():
+        sh = R.range_shape(name)
+        hp = R.RANGE_HEAD_PATTERNS[B, H]
+        walks = R.range_walks(sh["lists"], hp, B, sh["S"], defect)
+        if walks == R.range_walks(sh["lists"], hp, B, sh["S"]):
+            continue
+        for kind in _range_kinds(name, B, H):
+            p, masks, ref, ref_lse = _range_ref(name, B, H, kind)
+            for bound, _rel in _range_forms(kind, sh["S"])[:2 if name == "a" else 1]:
+                yield p, masks, dict(walks=walks, bound_log2=bound, ref=(ref, ref_lse)), f"shape {name} "
+
+
 # ---- teeth -------------------------------------------------------------------------------------------------------------------------------------------
 
 def _defect_runs(defect):
     """(probe, mask the reference uses, emulation keyword arguments) of the cases on which a defect is tried"""
+    if defect in R.RANGE_DEFECTS:
+        yield from _range_defect_runs(defect)
+        return
     if defect in ("window_short", "window_long"):
         fl, S, W, s = 64, 768, 1, 0
         bad = R.window_mask(S, fl, W, s, hi_shift=-R.KVB if defect == "window_short" else R.KVB)
@@ -191,12 +278,19 @@ def _defect_runs(defect):
 @pytest.mark.parametrize("defect", R.DEFECTS)
 def test_every_defect_fails_at_least_one_probe(defect):
     failed = []
-    for p, mask, kw in _defect_runs(defect):
-        ref, ref_lse = R.reference(p, mask)
-        out, lse = R.emulate(p.q, p.k, p.v, **kw)
+    for p, mask, kw, *where in _defect_runs(defect):
         rel = R.REL_EXACT_P if (kw.get("bound_log2") is None and not p.name.startswith("staircase")) else R.REL_BF16
-        if not _passes(p, out, lse, ref, ref_lse, rel):
-            failed.append(f"{p.name} Sq={p.Sq} Skv={p.Skv} B={p.B} H={p.H}")
+        if "walks" in kw:  # a range defect: the shared reference, and the OUTPUT alone (family 7's launches write no LSE)
+            ref, ref_lse = kw["ref"]
+            out, lse = R.emulate_walks(p.q, p.k, p.v, kw["walks"], bound_log2=kw["bound_log2"])
+            caught = not _passes(p, out, lse, ref, ref_lse, rel, check_lse=False)
+        else:
+            ref, ref_lse = R.reference(p, mask)
+            out, lse = R.emulate(p.q, p.k, p.v, **kw)
+            caught = not _passes(p, out, lse, ref, ref_lse, rel)
+        if caught:
+            form = "" if "walks" not in kw else " no-max" if kw["bound_log2"] is not None else " running max"
+            failed.append(f"{''.join(where)}{p.name}{form} Sq={p.Sq} Skv={p.Skv} B={p.B} H={p.H}")
     print(f"[defect {defect}] caught by: {failed}")
     assert failed, f"no probe notices the defect {defect}"
 
@@ -218,6 +312,8 @@ def test_report_defects_against_the_gaussian_rel_l2_bar():
         p = R.Probe("gaussian", q, k, v, exact=False)
         for defect in R.DEFECTS:
             kw, mask = dict(defect=defect), None
+            if defect in R.RANGE_DEFECTS:
+                continue  # (self-attention under a table: reported below, at family 7's shapes and against the range kernels' own bar)
             if defect in ("window_short", "window_long", "skip_shifted") and Skv % 64:
                 continue  # (whole tiles only, as the kernels with these forms)
             if defect in ("window_short", "window_long"):  # the query rows are the first rows of the sequence
@@ -232,3 +328,23 @@ def test_report_defects_against_the_gaussian_rel_l2_bar():
         print(f"[gaussian rel-L2] {d}: " + ", ".join(f"Skv={s}: {e:.3e}" for s, e in runs))
     through = [d for d, runs in errors.items() if d != "lse_without_log2_l" and all(e < 1e-2 for _s, e in runs)]
     print(f"[gaussian rel-L2 < 1e-2 lets through] {through}; never looks at: ['lse_without_log2_l']")
+    # the range defects, against the bar tests/test_attn_ranges_gpu.py holds the range kernels to: the worst (batch, head) rel-L2 < 4e-3 on Gaussian
+    # inputs, at family 7's shapes (a) and (c) and tables, no-max form
+    bar, rng_errors = 4e-3, {}
+    for name, B, H in (("a", 2, 3), ("c", 1, 2)):
+        sh = R.range_shape(name)
+        S, hp = sh["S"], R.RANGE_HEAD_PATTERNS[B, H]
+        q, k, v = _gaussian(S, S, B, H)
+        ref, _ = R.reference(R.Probe("gaussian", q, k, v, exact=False), R.head_masks(sh["lists"], hp, S))
+        clean = R.range_walks(sh["lists"], hp, B, S)
+        for defect in (None,) + R.RANGE_DEFECTS:
+            walks = R.range_walks(sh["lists"], hp, B, S, defect)
+            if defect is not None and walks == clean:
+                continue
+            out, _lse = R.emulate_walks(q, k, v, walks, bound_log2=BOUND_LOG2)
+            pair = lambda b, h: float((out[:, b, h].double() - ref[:, b, h]).norm() / ref[:, b, h].norm())
+            rng_errors.setdefault(defect or "clean", []).append((name, max(pair(b, h) for b in range(B) for h in range(H))))
+    for d, runs in rng_errors.items():
+        print(f"[gaussian worst (batch, head) rel-L2, range table] {d}: " + ", ".join(f"shape {n}: {e:.3e}" for n, e in runs))
+    assert all(e < bar for _n, e in rng_errors["clean"]), rng_errors["clean"]  # (the clean emulation is inside that bar: the report is about the defects)
+    print(f"[gaussian rel-L2 < {bar} lets through] {[d for d, runs in rng_errors.items() if d != 'clean' and all(e < bar for _n, e in runs)]}")

@@ -7,8 +7,10 @@ family 1b runs the default scale and holds every kernel to the exact function or
 
 Families: (1) ops.flash_attn with every attn_variant 1..11, bf16 and partial outputs, LSE, ops.attn_merge of two and three key parts; (2) segmented
 V^T; (3) the cross form (kv_dense, in-kernel Q norm); (4) the no-max kernels (ops.self_attn_bounded, 32x32x16 and 16x16x32); (5) carry / kv_skip /
-launch chains on variants 4 and 11 through both entries; (6) the two frame-window entries, no-max and running-max. Every launch's kernel name is
-asserted, so no family can silently re-run another one's kernel.
+launch chains on variants 4 and 11 through both entries; (6) the two frame-window entries, no-max and running-max; (7) the range-table entry
+(ops.self_attn_ranges), no-max and running-max, with the probes at 64 classes so that every (head, query block, tile) triple of a launch owns an
+output element (shapes, tables and probes: R.range_shape; every launch made twice, bit for bit). Every launch's kernel name is asserted, so no
+family can silently re-run another one's kernel.
 
 Buffers: q is a column view of a wider buffer; K is a column view of a NaN-guarded buffer whose guard rows sit directly behind key Skv - 1; every
 bf16 output (and the fp32 outputs of the carry entry) is a NaN-guarded payload, checked with assert_only_payload_written after the launch.
@@ -24,7 +26,8 @@ Bars (every element is checked, no tolerated outliers).
  * the staircase at step 12 needs a bound of 12 (tiles - 1) in the log2 domain: the no-max forms run it where that is within their limit of 60
    (an understated bound is a caller error), the running-max forms at every length.
 
-Measured on an MI355X (the tests print these per case): MEASURED below; the whole file takes about 25 s. At the default scale (family 1b) the
+Measured on an MI355X (the tests print these per case): MEASURED below; the whole file takes about 22 s, family 7 about 3 s of it (its five
+cases 0.3 to 0.9 s each; every case of it passed on the first run, so the (1, 8) run of shape (b) stays). At the default scale (family 1b) the
 partial launches of the folding kernels write an LSE 0.1055 (census) to 1.319 (staircase, step 12, 2 240 keys) above the fp64 value of the inputs
 and agree with the fp64 value behind the fold to 1.5e-5; family 1b's docstring records the kernel defect it found."""
 import functools
@@ -47,6 +50,7 @@ MEASURED = {
     "5 carry / kv_skip / chains": (3.663e-03, 1.311e-06),
     "6 window": (1.953e-03, None),
     "6 window cp": (1.953e-03, None),
+    "7 ranges": (4.883e-03, None),  # (the no-max form, bar 2^-7; in every one of the five cases)
 }
 
 HD = R.HD
@@ -59,6 +63,7 @@ STAIRS = ((0.5, False), (0.5, True), (12.0, False), (12.0, True))
 NM, W4C = "flash_attn_fwd_w4b_nm_kernel<true>", "flash_attn_fwd_w4c_nm_kernel"
 NM_WIN, MAX_WIN = "flash_attn_fwd_w4b_nm_win_kernel<true>", "flash_attn_fwd_w4b_win_kernel<true>"
 MAX_DENSE = "flash_attn_fwd_w4b_kernel<true>"
+NM_RNG, MAX_RNG = "flash_attn_fwd_w4b_nm_rng_kernel<true>", "flash_attn_fwd_w4b_rng_kernel<true>"
 WINDOWS = ((64, 768), (64, 640), (128, 768), (128, 640), (192, 768), (192, 576))
 WS = ((0, 0), (1, 0), (0, 1), (1, 2))
 
@@ -574,3 +579,55 @@ def test_self_attn_window_cp(fl, T, world, B, H):
                     o.assert_only_payload_written(tag)
                     st.check_out(tag, c, o.payload, _rel_for(c, running_max))
     st.report(f"fl={fl} T={T} world={world} B={B} H={H}")
+
+
+# ---- 7. the range-table entry ----------------------------------------------------------------------------------------------------------------------------
+
+_ranges = _scaled("self_attn_ranges")
+
+
+@functools.lru_cache(maxsize=None)
+def _rng_table(name, B, H):
+    from gen3c_amd import ops
+    sh = R.range_shape(name)
+    return ops.attn_range_table(R.pack(sh["lists"], sh["max_ranges"]), sh["S"], head_pattern=list(R.RANGE_HEAD_PATTERNS[B, H]), H=H)
+
+
+@functools.lru_cache(maxsize=None)
+def _rng_case(name, kind, B, H):
+    sh = R.range_shape(name)
+    return Case(R.range_probe(kind, sh["S"], B, H), mask=R.head_masks(sh["lists"], R.RANGE_HEAD_PATTERNS[B, H], sh["S"]))
+
+
+@pytest.mark.parametrize("name,B,H", R.range_cases())
+def test_self_attn_ranges(name, B, H):
+    """Family 7: g3_self_attn_fwd_ranges_bf16 at R.range_shape's shapes (what each is the smallest shape for is a comment there). All probes have 64
+    classes, so every 64-key tile holds every class, the census-block V column of a key is its tile, and output element (i, d) is 1 / n iff tile d
+    is in the list of row i's block under its head's pattern: every (head, query block, tile) triple of a launch owns an output element of its own.
+    (a) also runs the four staircases at (B, H) = (2, 3) - the running-max form all four, the no-max form those within its limit of 60 (the 0.5-step
+    pair) - so the reference point moves across range jumps. Every launch is made twice into two guarded outputs which must be equal bit for bit
+    (no atomics, no order-dependent sums; the table load is retired before the first LDS-DMA). Measured on an MI355X: every case inside every bar
+    on the first run, no kernel defect found; worst relative element error 4.883e-3 (no-max form), the CPU emulation's figure to the digit."""
+    from gen3c_amd import ops
+    st = Stats("7 ranges")
+    sh = R.range_shape(name)
+    S, lists, hp = sh["S"], sh["lists"], R.RANGE_HEAD_PATTERNS[B, H]
+    table = _rng_table(name, B, H)
+    for pat, blocks in enumerate(lists):
+        assert torch.equal(R.ranges_mask(blocks, S), ops.ranges_attn_mask(table, S, pattern=pat)), (name, pat)
+    assert (table.attended, table.dense) == R.ranges_counts(lists, hp, S)
+    kinds = tuple(sh["probes"]) + (STAIRS if sh["stairs"] and (B, H) == R.RANGE_STAIRS_AT else ())
+    for kind in kinds:
+        c = _rng_case(name, kind, B, H)
+        for bound, kernel, running_max in ((_stair_bound(kind, S), NM_RNG, False), (0.0, MAX_RNG, True)):
+            if bound is None:  # a staircase beyond the no-max form's range
+                continue
+            tag = f"self_attn_ranges shape {name} {c.p.name} S={S} bound={bound} B={B} H={H}"
+            o, o_again = c.out(), c.out()
+            _, names = _launch(lambda: [_ranges(c.q, c.k, c.vt, S, B, H, bound, table, out=g.payload) for g in (o, o_again)])
+            assert names == [kernel] * 2, (tag, names)
+            o.assert_only_payload_written(tag)
+            o_again.assert_only_payload_written(tag + " (second launch)")
+            assert torch.equal(o.payload, o_again.payload), f"{tag}: two launches on the same inputs differ"
+            st.check_out(tag, c, o.payload, _rel_for(c, running_max))
+    st.report(f"shape {name} S={S} B={B} H={H}")

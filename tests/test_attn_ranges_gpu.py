@@ -4,8 +4,12 @@ ops.ranges_attn_mask is the function.
 
 Inputs as in tests/test_attn_window_gpu.py: q, k behind a per-head RMSNorm with unit weights (column views of fused buffers, as the DiT passes them),
 random v; head dim 128; BOUND = sqrt(128) * 1.03. Both kernel forms run on every case and the kernel's name is asserted per launch. The hand-made
-tables are for the kernel alone and do not depend on the builders; no test hands the kernel an invalid table (the clamp is a property of the code,
-g3_attn_ranges_check is what tests/test_attn_ranges_cpu.py tests).
+tables are for the kernel alone and do not depend on the builders; g3_attn_ranges_check is what tests/test_attn_ranges_cpu.py tests.
+
+The element-level check of these kernels - exact fp64 probes in which every (head, query block, tile) triple owns an output element, guarded K and
+O, every launch twice, the 64-range table, the staircases across range jumps - is family 7 of tests/test_attn_probes_gpu.py; operands spanning
+2^31 / 2^32 bytes are the rng_* kinds of tests/test_far_operands_gpu.py. Here: the Gaussian bar, the bitwise oracles, and the one promise the
+header makes about a table that breaks the rules (test_the_kernel_clamps_a_rule_breaking_table_to_the_operand).
 
  1. S 832, B = H = 1, max_ranges 8: block 0 = tile {0}; block 1 = tiles {0}, {2}; block 2 = tiles {1}, {5}, {12}; block 3 (64 rows) = [0, 2), {3}, [6, 13):
     nt = 1, 2, 3; the prologue's K(1) / V^T(1) out of a second range; the t + 2 clamp; the last tile of the operand.
@@ -26,6 +30,8 @@ import math
 import numpy as np
 import pytest
 import torch
+
+from tests import attn_probe_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -89,27 +95,7 @@ def _timed(f):
     return out, metas
 
 
-def _pack(lists, max_ranges):
-    """lists[pattern][block] = [(first_tile, n_tiles), ...] -> int32 [n_patterns, n_qblk, max_ranges, 2] in keys"""
-    t = np.zeros((len(lists), len(lists[0]), max_ranges, 2), dtype=np.int32)
-    for p, blocks in enumerate(lists):
-        for b, rl in enumerate(blocks):
-            assert 1 <= len(rl) <= max_ranges
-            t[p, b, :len(rl)] = np.asarray(rl, dtype=np.int32) * 64
-    return t
-
-
-def _random_list(rng, n_tiles, max_n):
-    """1..max_n ascending disjoint (first_tile, n_tiles) ranges of random lengths; about a third of the neighbours touch"""
-    n = int(rng.randint(1, max_n + 1))
-    pos, out = int(rng.randint(0, max(1, n_tiles // 3))), []
-    for _ in range(n):
-        ln = int(rng.randint(1, 5))
-        if pos + ln > n_tiles:
-            break
-        out.append((pos, ln))
-        pos += ln + int(rng.choice([0, 1, 2, int(rng.randint(1, max(2, n_tiles // 4)))]))
-    return out or [(n_tiles - 1, 1)]
+_pack, _random_list = R.pack, R.random_list  # (shared with family 7 of tests/test_attn_probes_gpu.py, so the seeded lists are the same lists)
 
 
 @functools.lru_cache(maxsize=None)
@@ -199,6 +185,65 @@ def test_frame_ranges_launch_equals_the_window_launch(frame_len, S, W, s, B, H):
         assert metas[0]["kernel"] == kernel and wmetas[0]["kernel"] == win_kernel
         assert metas[0]["tile_density"] == wmetas[0]["tile_density"]
         assert torch.equal(out, win), f"{kernel} differs from {win_kernel} on the same tiles in the same order"
+
+
+def test_the_kernel_clamps_a_rule_breaking_table_to_the_operand():
+    """gen3c_hip.h: "the kernel clamps every range (and the pattern index) to the operand". ops.attn_range_table refuses such a table, so the
+    library entry is called directly, once with a table that breaks the rules and once with the valid table the clamp must make of it -
+    min(first_key, S), min(n_keys, S - first_key), a range of no keys ends the list, pattern n_patterns - 1 - and the two outputs must be EQUAL,
+    in both forms, and finite. Ranges that overrun S by one and by two tiles, first_key == S and first_key == S + 64 (each behind a valid first
+    range, with a valid-looking range behind it that must not be visited), and a head_pattern entry equal to n_patterns.
+    No value here could fault even if the clamp were missing: the largest unclamped key is S + 127 - K has 128 B NaN guard rows behind key S - 1,
+    V^T 128 NaN columns - and the table buffer holds a whole third pattern (the list {0}) behind the two the launch is told of. Negative or huge
+    table values are deliberately not run: their unclamped addresses would leave the allocations; that part of the promise is read from the
+    code (attention_w4b.hpp: the unsigned min in the table load)."""
+    from gen3c_amd import _lib as L, ops
+    from tests.guarded import Guarded
+    lib = L.load()
+    S, B, H, MR = 832, 2, 2, 4
+    D = H * HD
+    bad = np.zeros((3, 4, MR, 2), dtype=np.int32)
+    bad[0, 0, :2] = [(0, 64), (704, 192)]              # over S by one tile
+    bad[0, 1, :2] = [(128, 128), (768, 192)]           # by two
+    bad[0, 2, :3] = [(64, 64), (S, 64), (320, 64)]     # first_key == S: no keys left, the list ends there
+    bad[0, 3, :3] = [(0, 128), (S + 64, 64), (448, 64)]
+    bad[1, 0, :1] = [(256, 640)]                       # by one, the only range
+    bad[1, 1, :3] = [(0, 64), (192, 64), (704, 256)]   # by two
+    bad[1, 2, :3] = [(512, 64), (S, 128), (704, 64)]
+    bad[1, 3, :2] = [(768, 64), (S + 64, 64)]
+    bad[2, :, 0] = (0, 64)                             # behind the launch's two patterns: what an unclamped pattern index would read
+    assert int((bad[:2, :, :, 0] + bad[:2, :, :, 1]).max()) == S + 128
+    good = bad.copy()
+    first = np.minimum(good[..., 0], S)
+    good[..., 1] = np.minimum(good[..., 1], S - first)
+    good[..., 0] = first
+    for p in range(2):
+        for b in range(4):
+            n = int(np.argmax(good[p, b, :, 1] == 0)) if (good[p, b, :, 1] == 0).any() else MR
+            good[p, b, n:] = 0
+    ops.attn_range_table(good[:2], S, head_pattern=[1, 0], H=H)  # (the clamped table keeps every rule)
+    with pytest.raises(Exception):
+        ops.attn_range_table(bad[:2], S, head_pattern=[1, 0], H=H)
+    q, k, v, _ = _problem(S, B, H)
+    dev = q.device
+    kg = Guarded(S * B, 2 * D, guard=2 * 64 * B, data=torch.cat([torch.full((S * B, D), -2.5, dtype=torch.bfloat16, device=dev), k], dim=1))
+    kk = kg.payload[:, D:]
+    ldvt = S + 128
+    vt = torch.full((B, H, HD, ldvt), float("nan"), dtype=torch.bfloat16, device=dev)
+    vt[..., :S] = v.view(S, B, H, HD).permute(1, 2, 3, 0)
+    tables = {name: (torch.from_numpy(t).to(dev), torch.tensor(hp, dtype=torch.int32, device=dev)) for name, t, hp in (("bad", bad, [2, 0]), ("good", good, [1, 0]))}
+    for bound, kernel in ((BOUND, NM_RNG), (0.0, MAX_RNG)):
+        outs = {}
+        for name, (tab, hp) in tables.items():
+            o = Guarded(S * B, D, ld=D + 64)
+            args = (q.data_ptr(), q.stride(0) * B, q.stride(0), HD, kk.data_ptr(), kk.stride(0) * B, kk.stride(0), HD, vt.data_ptr(), ldvt, H * HD * ldvt, HD * ldvt,
+                    o.payload.data_ptr(), o.ld * B, o.ld, HD, S, B, H, HD, 1.0 / math.sqrt(HD), bound, tab.data_ptr(), 2, MR, hp.data_ptr())
+            assert lib.g3_attn_ranges_plan_bf16(*args).decode() == kernel
+            L.check(lib.g3_self_attn_fwd_ranges_bf16(*args, torch.cuda.current_stream().cuda_stream), "g3_self_attn_fwd_ranges_bf16")
+            torch.cuda.synchronize()
+            o.assert_only_payload_written(f"{kernel} {name} table")  # (and the payload finite)
+            outs[name] = o.payload.clone()
+        assert torch.equal(outs["bad"], outs["good"]), f"{kernel}: the rule-breaking table does not give the launch of its clamped table"
 
 
 def test_radial_ranges_vs_masked_fp64():

@@ -37,7 +37,9 @@ Attention (ATTN_KINDS): the census probe at Skv = 320, (B, H) = (2, 3) through e
 tests/test_attn_probes_gpu.py - (1) g3_flash_attn_fwd_ex_bf16 on every variant 1..11 with a bf16 output, and on 4 and 11 with o_partial + lse;
 (3) g3_cross_attn_fwd_bf16 with the in-kernel Q norm; (4) the no-max kernels, 32x32x16 and 16x16x32, and the no-max partial output; (5) the
 key-skip form of the carry entries on variants 4 and 11 and without running max; (6) both frame-window kernels and the window entry under key
-sharding. Each gets Q and O (or o_partial: fp32 at the same element strides) by row, batch and head at P31 and P32, K by row at P31 (inside
+sharding; (7) both range-table kernels (g3_self_attn_fwd_ranges_bf16) at S = 320 - a 256-row and a 64-row query block over 5 tiles, two patterns,
+head_pattern [1, 0, 1], no block attending every tile - with the table and head_pattern placed in the arena like every other operand, so a stray
+access of the table walk lands on sentinel too. Each gets Q and O (or o_partial: fp32 at the same element strides) by row, batch and head at P31 and P32, K by row at P31 (inside
 k_max: same kernel), V^T by head and by batch at P31, and K by row at P32: the 64-bit-addressing kernels keep it, the bf16-output plain and
 bounded entries are planned onto variant 2, every other form must refuse with G3_ERR_ARG, name an entry and leave the whole arena untouched.
 lse is contiguous [B][H][Sq] by the ABI (no stride): it is written beside a far o_partial, never far itself. The carry entries run without a
@@ -50,14 +52,15 @@ operands span 4 GiB (Q, K, O) or 256 GiB (V^T); its refusals are held by tests/t
 (ld_in 2 < 2^31, ...) are still far away: tests/test_gemm_plan_cpu.py holds them; what switches at P32 is the one-wave kernel's tap change
 (test_conv3d_one_operand_far). The convolution's weights (ldw) stay compact.
 
-MEASURED on an MI355X (profiles/far_operand_parity_measured.txt): 762 cases, 21.3 s for the whole file (module wall time, arena included; the
-slowest case 0.6 s) - tests/test_gemm_epilogue_kernels_gpu.py takes 7.8 s for its 46 cases on the parent commit. Kernels named by a plan: 18 GEMM
-instantiations, 8 convolution instantiations, 16 attention kernels. EVERY case is bitwise equal to its compact oracle; no case needed a bar
+MEASURED on an MI355X (profiles/far_operand_parity_measured.txt, made before the range kinds; the figures here are of the run with them): 794 cases,
+21.4 s for the whole file (module wall time, arena included; the slowest case 0.6 s; the 32 range cases and their two compact launches 1.4 s) -
+tests/test_gemm_epilogue_kernels_gpu.py takes 7.8 s for its 46 cases on the parent commit. Kernels named by a plan: 18 GEMM
+instantiations, 8 convolution instantiations, 18 attention kernels. EVERY case is bitwise equal to its compact oracle; no case needed a bar
 instead. The GroupNorm statistics (fp64 atomics, up to 5 workgroups per frame) and the convolution's fused statistics were bitwise repeatable
 between two compact launches in every run - sums of a handful of fp32 partials are exact in fp64 - so the fallback to the bar of
 tests/test_tokenizer_kernels_gpu.py (2e-6 of |sum| + 1 against fp64 sums) never ran. The far K at P32 of the 11 kinds planned onto variant 2
 is ADDITIONALLY held to the fp64 census probe at REL_EXACT_P = 2^-8 (tests/attn_probe_ref.py): worst relative error 3.7e-8, largest element
-that should be zero 3.5e-10; 10 kinds refuse it with the arena untouched, the two 64-bit-addressing variants keep their kernel."""
+that should be zero 3.5e-10; 12 kinds refuse it with the arena untouched, the two 64-bit-addressing variants keep their kernel."""
 import ctypes as C
 import functools
 import time
@@ -547,7 +550,7 @@ def test_rowwise_entry_one_operand_far(arena, entry, operand, pitch):
 
 
 # =================================================================================================================================
-# attention: every launching entry, every kernel family of tests/test_attn_probes_gpu.py (1, 3, 4, 5, 6)
+# attention: every launching entry, every kernel family of tests/test_attn_probes_gpu.py (1, 3, 4, 5, 6, 7)
 # =================================================================================================================================
 from tests import attn_probe_ref as R  # noqa: E402
 
@@ -561,7 +564,13 @@ ATTN_KINDS.update({
     "nm": ("bounded", 11, SQ, "v2"), "nm16": ("bounded16", 11, SQ, "v2"), "nm_partial": ("bounded_partial", 11, SQ, "refused"),  # family 4
     "skip_v4": ("carry", 4, SQ, "refused"), "skip_v11": ("carry", 11, SQ, "refused"), "nm_skip": ("bounded_cp", 11, SQ, "refused"),  # family 5
     "win_nm": ("window", 11, SKV, "refused"), "win_max": ("window_max", 11, SKV, "refused"), "win_cp": ("window_cp", 11, 128, "refused"),  # family 6
+    "rng_nm": ("ranges", 11, SKV, "refused"), "rng_max": ("ranges_max", 11, SKV, "refused"),                                              # family 7
 })
+# family 7: S = 320 is a 256-row and a 64-row query block over 5 tiles; two patterns in tiles, head_pattern [1, 0, 1], max_ranges 4, and no block
+# attends every tile. The table and head_pattern are operands in the arena (8- and 4-byte aligned: the arena aligns to 16).
+RNG_LISTS = [[[(0, 1), (2, 2)], [(1, 1), (4, 1)]], [[(1, 3)], [(0, 2), (3, 1), (4, 1)]]]
+RNG_HEAD_PATTERN, RNG_MAX_RANGES = [1, 0, 1], 4
+assert all(sum(n for _f, n in rl) < SKV // 64 for blocks in RNG_LISTS for rl in blocks)
 SKIP = (64, 64)  # family 5: the keys [64, 128) of the 320 in K / V^T are skipped, S_kv = 256 attended
 ATTN_DIMS = {"q": ("head", "batch", "row"), "o": ("head", "batch", "row"), "k": ("head", "batch", "row"), "vt": ("row", "head", "batch")}  # innermost first
 # (operand, the dimension whose stride is far, pitch). K by row: P31 stays inside the kernels' 32-bit budget (k_max of attn_plan) - the same kernel
@@ -569,7 +578,7 @@ ATTN_DIMS = {"q": ("head", "batch", "row"), "o": ("head", "batch", "row"), "k": 
 ATTN_FAR = [("q", d, p) for d in ("row", "batch", "head") for p in ("P31", "P32")] + [("o", d, p) for d in ("row", "batch", "head") for p in ("P31", "P32")] + \
            [("k", "row", "P31"), ("k", "row", "P32"), ("vt", "head", "P31"), ("vt", "batch", "P31")]
 REFUSAL_NAMES = ("g3_flash_attn_fwd_ex_bf16:", "g3_cross_attn_fwd_bf16:", "g3_flash_attn_fwd_carry_bf16:", "g3_self_attn_fwd_window_bf16:",
-                 "g3_self_attn_fwd_window_cp_bf16:")
+                 "g3_self_attn_fwd_window_cp_bf16:", "g3_self_attn_fwd_ranges_bf16:")
 
 
 @functools.lru_cache(maxsize=4)
@@ -596,11 +605,14 @@ def _attn_strides(operand, Sq, inner_bytes, far_dim=None, pitch=None):
 def _attn_launch(lib, entry, variant, a):
     """-> (the dry run's answer, the launching entry's status); a: the placed operands as ABI arguments"""
     q, k, vt, o, o32, lse, os_, wq, Sq = a["q"], a["k"], a["vt"], a["o"], a["o32"], a["lse"], a["os"], a["wq"], a["Sq"]
-    bound = R.BOUND_NATS if entry in ("bounded", "bounded16", "bounded_partial", "bounded_cp", "window", "window_cp") else 0.0
+    bound = R.BOUND_NATS if entry in ("bounded", "bounded16", "bounded_partial", "bounded_cp", "window", "window_cp", "ranges") else 0.0
     shape, sc, st = (AB, AH, R.HD), R.SOFTMAX_SCALE, _stream()
     if entry in ("window", "window_max"):
         args = (*q, *k, *vt, o, *os_, Sq, *shape, sc, bound, WIN["frame_len"], WIN["W"], WIN["s"])
         return lib.g3_attn_window_plan_bf16(*args), lib.g3_self_attn_fwd_window_bf16(*args, st)
+    if entry in ("ranges", "ranges_max"):
+        args = (*q, *k, *vt, o, *os_, Sq, *shape, sc, bound, a["ranges"], len(RNG_LISTS), RNG_MAX_RANGES, a["head_pattern"])
+        return lib.g3_attn_ranges_plan_bf16(*args), lib.g3_self_attn_fwd_ranges_bf16(*args, st)
     if entry == "window_cp":  # this rank's queries: frames 3 and 4 of 5; the buffer holds all five (a = b = 0), W = 1: frames 2..4 attended
         args = (*q, *k, *vt, o, *os_, Sq, SKV, *shape, sc, bound, WIN["frame_len"], 5, 3, 0, 0, 1, 0)
         return lib.g3_attn_window_cp_plan_bf16(*args), lib.g3_self_attn_fwd_window_cp_bf16(*args, st)
@@ -645,6 +657,11 @@ def _attn_in_arena(arena, entry, variant, Sq, far=None, refused=False):
     lse = arena.place_rows("lse", (1, AB * AH * Sq), dtype=f32, role="out") if partial else None
     a = {n: (_p(v[n]), *es[n]) for n in ("q", "k", "vt")}
     a.update(o=None if partial else _p(v["o"]), o32=_p(v["o"]) if partial else None, lse=_p(lse) if partial else None, os=es["o"], wq=_p(wq), Sq=Sq)
+    if entry in ("ranges", "ranges_max"):
+        tab = arena.place_rows("ranges", torch.from_numpy(R.pack(RNG_LISTS, RNG_MAX_RANGES)).reshape(1, -1))
+        hp = arena.place_rows("head_pattern", torch.tensor([RNG_HEAD_PATTERN], dtype=torch.int32))
+        assert _p(tab) % 8 == 0 and _p(hp) % 4 == 0
+        a.update(ranges=_p(tab), head_pattern=_p(hp))
     planned, rc = _attn_launch(lib, entry, variant, a)
     torch.cuda.synchronize()
     what = f"attention {entry} variant {variant} {far or 'compact'}"
@@ -678,6 +695,7 @@ def test_attention_kinds_reach_the_kernels_they_are_meant_for(arena):
     assert names["nm_skip"] == "flash_attn_fwd_w4b_nm_carry_kernel<true>", names
     assert names["nm"] == names["nm_partial"] == "flash_attn_fwd_w4b_nm_kernel<true>" and names["nm16"] == "flash_attn_fwd_w4c_nm_kernel", names
     assert names["win_nm"] == names["win_cp"] == "flash_attn_fwd_w4b_nm_win_kernel<true>" and names["win_max"] == "flash_attn_fwd_w4b_win_kernel<true>", names
+    assert names["rng_nm"] == "flash_attn_fwd_w4b_nm_rng_kernel<true>" and names["rng_max"] == "flash_attn_fwd_w4b_rng_kernel<true>", names
     assert names["partial_v11"] == names["ex_v11"] and names["partial_v4"] == names["ex_v4"] == names["cross"], names
 
 
@@ -687,7 +705,7 @@ def test_attention_one_operand_far(arena, kind, operand, dim, pitch):
     """K by row at P32: the plain and bounded entries with a bf16 output are planned onto the 64-bit-addressing kernel (variant 2), compared bitwise
     with a compact launch forced there (variant = 2) AND - the one case of this file that is also held to an fp64 reference - with the census
     probe's fp64 result at the bar tests/test_attn_probes_gpu.py gives the running-max kernels on that probe (REL_EXACT_P = 2^-8). Every form that
-    has no 64-bit kernel (partial outputs, cross, carry / key skip, both window entries) must refuse it, name an entry and write nothing; the
+    has no 64-bit kernel (partial outputs, cross, carry / key skip, both window entries, the range-table entry) must refuse it, name an entry and write nothing; the
     refusals' texts are held by tests/test_attn_carry_gpu.py, test_attn_bounded_cp_gpu.py and test_attn_plan_cpu.py."""
     L, lib = _lib()
     entry, variant, Sq, k_p32 = ATTN_KINDS[kind]
