@@ -90,6 +90,12 @@ SIGNATURES = {
     "g3_attn_ranges_plan_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp],
     "g3_attn_ranges_check": [vp, i32, i32, i32, vp, i32, C.POINTER(i64), C.POINTER(i64)],
     "g3_self_attn_ranges_max": [],
+    "g3_attn_pattern_profile_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, f32, vp, i32, vp, i32, i32, vp, C.c_size_t, vp, vp],
+    "g3_attn_pattern_profile_plan_bf16": [vp, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, f32, vp, i32, vp, i32, i32, vp, C.c_size_t, vp],
+    "g3_attn_pattern_select": [vp, i32, i32, i32, i32, vp, vp, vp],
+    "g3_attn_profile_workspace_bytes": [i32, i32, i32],
+    "g3_attn_profile_chunks": [i32, i32, i32],
+    "g3_attn_profile_members": [vp, i32, i32, i32, vp, i32, vp],
     "g3_attn_merge_partials_bf16": [vp, vp, i32, i64, i64, i64, vp, i64, i64, i64, i32, i32, i32, i32, vp],
     "g3_transpose_v_bf16": [vp, i64, vp, i64, i32, i32, i32, i32, vp],
     "g3_cp_scatter_heads_bf16": [vp, vp, vp, i64, vp, vp, vp, i64, i32, i32, i32, i32, vp],
@@ -136,7 +142,7 @@ SIGNATURES = {
     "g3_edm_cond_euler_step_bf16": [vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp],
     "g3_edm_cond_2ab_step_bf16": [vp, vp, vp, vp, vp, i64, i32, i32, f32, f32, f32, f32, f32, f32, f32, vp, vp, i32, f32, f32, f32, vp],
 }
-_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_self_attn16_kernel_name": C.c_char_p, "g3_attn_plan16_bf16": C.c_char_p, "g3_attn_window_plan_bf16": C.c_char_p, "g3_attn_window_cp_plan_bf16": C.c_char_p, "g3_attn_ranges_plan_bf16": C.c_char_p,"g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
+_RESTYPES = {"g3_last_error": C.c_char_p, "g3_flash_attn_kernel_name": C.c_char_p, "g3_gemm_kernel_name": C.c_char_p, "g3_gemm_mxfp8_kernel_name": C.c_char_p, "g3_gemm_mxfp8_mxout_kernel_name": C.c_char_p, "g3_gemm_mxfp6_kernel_name": C.c_char_p, "g3_flash_attn_kernel_name_ex": C.c_char_p, "g3_self_attn_kernel_name": C.c_char_p, "g3_self_attn_cp_kernel_name": C.c_char_p, "g3_attn_plan_bf16": C.c_char_p, "g3_self_attn16_kernel_name": C.c_char_p, "g3_attn_plan16_bf16": C.c_char_p, "g3_attn_window_plan_bf16": C.c_char_p, "g3_attn_window_cp_plan_bf16": C.c_char_p, "g3_attn_ranges_plan_bf16": C.c_char_p, "g3_attn_pattern_profile_plan_bf16": C.c_char_p, "g3_attn_profile_workspace_bytes": C.c_size_t, "g3_gemm_plan_bf16": C.c_char_p, "g3_align_depth_workspace_bytes": C.c_size_t,
              "g3_warp_windows_workspace_bytes": C.c_size_t, "g3_render_workspace_bytes": C.c_size_t}
 
 

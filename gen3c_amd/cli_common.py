@@ -84,11 +84,14 @@ def add_common_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
                    help="with --self_attn_window_frames and --num_gpus > 1: run the window under context parallelism - every rank receives only the latent frames "
                         "within W of its own and the sink frames (the \"window_halo\" schedule) instead of refusing (opt-in, default off; same as a third field "
                         "in G3_SELF_ATTN_WINDOW=\"W,S,cp\")")
-    p.add_argument("--self_attn_pattern", type=str, default=None, metavar="radial:WIDTH1:SINK|frame:W:S",
+    p.add_argument("--self_attn_pattern", type=str, default=None, metavar="radial:WIDTH1:SINK|frame:W:S|band:WIDTH:SINK|auto=SPEC,SPEC",
                    help="single GPU: sparse self-attention over a range table - radial:WIDTH1:SINK is a spatial band of half-width WIDTH1 x the frame length at "
                         "frame distance 1 that halves every time the distance doubles, plus the first SINK latent frames; frame:W:S is the frame window of "
                         "--self_attn_window_frames at any frame length (720p included). Opt-in, default off; outside the parity statement, picture quality with "
-                        "trained weights unmeasured: DESIGN.md section 14; same as G3_SELF_ATTN_PATTERN. Not together with --self_attn_window_frames")
+                        "trained weights unmeasured: DESIGN.md section 14; same as G3_SELF_ATTN_PATTERN. band:WIDTH:SINK is a band of constant half-width WIDTH x the "
+                        "frame length across all frames (the temporal head of the per-head schemes); auto=SPEC,SPEC[,...] (2 to 8 of the former, e.g. "
+                        "auto=frame:2:1,band:0.125:1) lets every head of every block pick its candidate in every forward from 64 sampled query rows, on the GPU "
+                        "(DESIGN.md section 14.1). Not together with --self_attn_window_frames")
     for flag, why in _NO_COUNTERPART.items():
         p.add_argument(f"--{flag}", action="store_true", help=f"accepted for command-line compatibility; {why}")
     p.add_argument("--disable_prompt_encoder", action="store_true", help="all-zero text embeddings (DummyT5TextEncoder, t5_text_encoder.py:111-132)")
@@ -348,8 +351,14 @@ class Session:
         pattern = self_attn_pattern_requested(args)
         if pattern is not None:
             net.set_self_attn_pattern(pattern)  # (with a window, or under context parallelism, the first forward refuses it)
-            print(f"[gen3c_amd] self-attention pattern: {pattern[0]}:{pattern[1]}:{pattern[2]} over a range table (opt-in; outside the parity statement, "
-                  "picture quality unmeasured)")
+            if pattern[0] == "auto":
+                from .sparse_attn import spec_text
+                net.self_attn_pattern_log = print  # (the candidates' tile densities, once the first forward knows the shape)
+                print(f"[gen3c_amd] self-attention pattern: {spec_text(pattern)}: every head of every block picks its candidate in every forward, from "
+                      "64 sampled query rows on the GPU (opt-in; outside the parity statement, picture quality unmeasured)")
+            else:
+                print(f"[gen3c_amd] self-attention pattern: {pattern[0]}:{pattern[1]}:{pattern[2]} over a range table (opt-in; outside the parity statement, "
+                      "picture quality unmeasured)")
         if self.cfg_size > 1:
             self.cfg_group = parallel_state.get_cfg_parallel_group()
             print(f"[gen3c_amd] --cfg_parallel: 2 guidance branches x {self.cp_size} context-parallel rank(s); this rank runs the "

@@ -264,6 +264,7 @@ class VideoExtendGeneralDIT(nn.Module):
             self.set_self_attn_window(*self_attn_window, context_parallel=self_attn_window_cp)
         self.self_attn_pattern = None
         self._self_attn_tables = {}
+        self.self_attn_pattern_log = None  # a print-like callable: the ("auto", ...) pattern's candidate densities, once per table built
         self.set_self_attn_pattern(self_attn_pattern)
         self._tune_blocks: Optional[int] = None  # bench.py's context-parallel autotune: run only the first n blocks (not a model option)
 
@@ -425,9 +426,13 @@ class VideoExtendGeneralDIT(nn.Module):
     def set_self_attn_pattern(self, spec) -> None:
         """None (default, the parity path): dense self-attention. ("radial", width1, sink_frames) | ("frame", W, s) (or the command lines' string,
         "radial:0.25:1" / "frame:2:1"): training-free sparse attention - the single-GPU self-attention of every block runs ops.self_attn_ranges
-        over the range table gen3c_amd.sparse_attn builds for the forward's own (T, Hp * Wp), one pattern for all heads (per-head patterns stay an
-        ops-level capability: choosing heads needs trained weights, which do not exist here). The table is built, validated and uploaded once per
-        (shape, spec, device). A spec whose table covers every tile is the plain forward, bit for bit. Any frame length whose S is a multiple of 64
+        over the range table gen3c_amd.sparse_attn builds for the forward's own (T, Hp * Wp), one pattern for all heads; ("band", width, sink_frames) /
+        "band:0.125:1" likewise. ("auto", spec, spec, ...) / "auto=frame:2:1,band:0.125:1" (2 to 8 candidates): per-head patterns, chosen ONLINE as
+        the published training-free schemes do - in every forward of every block, after q | k are normalised and rotated,
+        ops.attn_pattern_profile measures on the GPU which candidate keeps most of the softmax mass of 64 sampled query rows of each head (both
+        entries of a fused CFG batch vote) and the attention launch reads that choice from device memory; all on the attention's stream, no
+        synchronise. self_attn_head_patterns() reads the last forward's choices back (a diagnostic). The table is built, validated and uploaded
+        once per (shape, spec, device). A spec whose table covers every tile is the plain forward, bit for bit. Any frame length whose S is a multiple of 64
         is accepted (720p's 45 x 80 = 3 600 tokens per frame included, which self_attn_window refuses). Picture quality: unmeasured (no trained
         checkpoint). Not together with self_attn_window; not under context parallelism."""
         from . import sparse_attn
@@ -448,9 +453,25 @@ class VideoExtendGeneralDIT(nn.Module):
         key = (Tp, Hp * Wp, spec, str(device))
         if key not in self._self_attn_tables:
             from . import sparse_attn
-            table = ops.attn_range_table(sparse_attn.build_spec(spec, Tp, Hp * Wp), S, device=device)
-            self._self_attn_tables[key] = None if table.attended == table.dense else table  # every tile: the plain launch
+            host = sparse_attn.build_spec(spec, Tp, Hp * Wp)
+            table = ops.attn_range_table(host, S, device=device)
+            if sparse_attn.is_auto(spec):  # one stacked table, one profile plan and one head_pattern row per block
+                dense = all(d == 1.0 for d in sparse_attn.tile_density(host, S))
+                if self.self_attn_pattern_log is not None:  # (the command lines: every candidate's density, once per shape)
+                    for line in sparse_attn.auto_report(spec, host, S):
+                        self.self_attn_pattern_log(line)
+                table.profile = None if dense else (ops.attn_profile_plan(table),
+                                                    torch.zeros((self.num_blocks, self.num_heads), dtype=torch.int32, device=device))
+            else:
+                dense = table.attended == table.dense
+            self._self_attn_tables[key] = None if dense else table  # every tile (of every candidate): the plain launch
         return self._self_attn_tables[key]
+
+    def self_attn_head_patterns(self):
+        """Diagnostic (it synchronises): the per-block, per-head candidate indices the last forward under an ("auto", ...) pattern chose, as a host
+        list [num_blocks][num_heads]; None where no such forward ran."""
+        hp = getattr(self, "_self_attn_last_choice", None)
+        return None if hp is None else hp.cpu().tolist()
 
     def set_mxfp8_producers(self, producers: str) -> None:
         """How the activations of the mxfp8 linears get quantised; no effect under linear_precision "bf16". Under "mxfp6" the setting is
@@ -763,6 +784,11 @@ class VideoExtendGeneralDIT(nn.Module):
                     vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
                 if fa_window is not None:  # opt-in local attention (a bound out of the no-max form's range, or none: the same kernel with its running maximum)
                     o = ops.self_attn_window(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, *fa_window)
+                elif fa_table is not None and getattr(fa_table, "profile", None) is not None:  # opt-in per-head patterns: profile, select, then the launch reads the choice
+                    fa_plan, fa_choice = fa_table.profile
+                    hp = ops.attn_pattern_profile(q, k, S, B, nH, fa_plan, head_pattern_out=fa_choice[bi])
+                    o = ops.self_attn_ranges(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, fa_table, head_pattern_dev=hp)
+                    self._self_attn_last_choice = fa_choice
                 elif fa_table is not None:  # opt-in sparse attention over a range table (likewise)
                     o = ops.self_attn_ranges(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, fa_table)
                 elif _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)

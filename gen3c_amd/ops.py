@@ -543,7 +543,7 @@ class AttnRangeTable:
     """A validated range table of self_attn_ranges (attn_range_table makes it): `ranges` int32 [n_patterns, n_qblk, max_ranges, 2] and `head_pattern`
     (int32 [H] or None) on the host, `ranges_dev` / `head_pattern_dev` their copies on the device, and (`attended`, `dense`): the (head, query
     block, 64-key tile) triples a launch with H heads visits and the dense launch's count."""
-    __slots__ = ("ranges", "head_pattern", "ranges_dev", "head_pattern_dev", "S", "H", "n_patterns", "max_ranges", "attended", "dense")
+    __slots__ = ("ranges", "head_pattern", "ranges_dev", "head_pattern_dev", "S", "H", "n_patterns", "max_ranges", "attended", "dense", "profile")
 
     @property
     def tile_density(self) -> float:
@@ -579,6 +579,7 @@ def attn_range_table(ranges, S: int, head_pattern=None, H: Optional[int] = None,
     t = AttnRangeTable()
     t.ranges, t.head_pattern, t.S, t.H, t.n_patterns, t.max_ranges = host, hp, int(S), H, host.shape[0], host.shape[2]
     t.attended, t.dense = att.value, dense.value
+    t.profile = None  # (the DiT's auto mode hangs its AttnProfilePlan and per-block choices here)
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     t.ranges_dev = host.to(dev)
     t.head_pattern_dev = hp.to(dev) if hp is not None else None
@@ -586,19 +587,99 @@ def attn_range_table(ranges, S: int, head_pattern=None, H: Optional[int] = None,
 
 
 def self_attn_ranges(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, S: int, B: int, H: int, logit_bound: float, table: AttnRangeTable,
-                     out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None):
+                     out: Optional[torch.Tensor] = None, softmax_scale: Optional[float] = None, head_pattern_dev: Optional[torch.Tensor] = None):
     """Self-attention over a range table (opt-in sparse attention; g3_self_attn_fwd_ranges_bf16): q, k [S*B, H*128] with tokens ordered (t, h, w), vt
     plain [B, H, 128, ldvt], table from attn_range_table for this S (and, with a head_pattern, this H). Every block of window_q_rows() query rows
     attends the keys of its list in the pattern of its head - ranges_attn_mask is the function - and the output is the exact softmax over those
     keys. logit_bound as for self_attn_bounded (out of range: the running-maximum form of the same kernel). The one-wave-per-SIMD kernel's
-    operand rules; no fallback."""
+    operand rules; no fallback. head_pattern_dev: a DEVICE int32 [H] that takes the place of the table's own head_pattern_dev for this launch (what
+    attn_pattern_profile wrote, in stream order; the kernel clamps its values to the table's patterns)."""
     if not isinstance(table, AttnRangeTable):
         raise ValueError("self_attn_ranges: table must come from ops.attn_range_table (which validates it)")
     if table.S != S or (table.head_pattern is not None and table.H != H):
         raise ValueError(f"self_attn_ranges: the table was made for S = {table.S}, H = {table.H}; the call has S = {S}, H = {H}")
     if table.ranges_dev.device != q.device:
         raise ValueError(f"self_attn_ranges: the table lives on {table.ranges_dev.device}, q on {q.device}")
-    return _attn_call("ranges", q, k, vt, S, S, B, H, out, softmax_scale, 11, False, logit_bound=logit_bound, ranges=table)
+    if head_pattern_dev is not None:
+        if (head_pattern_dev.dtype != torch.int32 or head_pattern_dev.numel() != H or not head_pattern_dev.is_contiguous()
+                or head_pattern_dev.device != q.device):
+            raise ValueError(f"self_attn_ranges: head_pattern_dev must be a contiguous int32 [{H}] on {q.device}")
+    return _attn_call("ranges", q, k, vt, S, S, B, H, out, softmax_scale, 11, False, logit_bound=logit_bound, ranges=table,
+                      head_pattern_dev=head_pattern_dev)
+
+
+class AttnProfilePlan:
+    """What attn_pattern_profile needs besides q and k (attn_profile_plan makes it): the table, the n sample rows and the per-tile membership bytes
+    [n, S / 64] on host and device, and - allocated at the first call for its (B, H, n_chunks) - the workspace and the results `recall` float32
+    [B, H, n, n_patterns], `score` float32 [H, n_patterns] and `head_pattern` int32 [H], all on the device."""
+    __slots__ = ("table", "n", "sample_rows", "sample_rows_dev", "member", "member_dev", "workspace", "recall", "score", "head_pattern", "n_chunks")
+
+
+def attn_profile_plan(table: AttnRangeTable, n_samples: int = 64, sample_rows=None) -> AttnProfilePlan:
+    """The sample rows (default: n_samples rows spread evenly, ((2i + 1) * S) // (2n)) and the bitmask g3_attn_profile_members makes of the table
+    for them, built and uploaded ONCE to the table's device."""
+    if not isinstance(table, AttnRangeTable):
+        raise ValueError("attn_profile_plan: table must come from ops.attn_range_table (which validates it)")
+    S = table.S
+    if sample_rows is None:
+        n = int(n_samples)
+        if not 1 <= n <= min(64, S):
+            raise ValueError(f"attn_profile_plan: n_samples {n} outside [1, min(64, S = {S})]")
+        sample_rows = [((2 * i + 1) * S) // (2 * n) for i in range(n)]
+    rows = torch.as_tensor(sample_rows, dtype=torch.int32).cpu().contiguous().flatten()
+    n = rows.numel()
+    member = torch.zeros((max(n, 1), S // 64), dtype=torch.uint8)
+    _lib.check(_lib.load().g3_attn_profile_members(table.ranges.data_ptr(), table.n_patterns, S, table.max_ranges, rows.data_ptr(), n, member.data_ptr()),
+               "g3_attn_profile_members")
+    p = AttnProfilePlan()
+    p.table, p.n, p.sample_rows, p.member = table, n, rows, member
+    dev = table.ranges_dev.device
+    p.sample_rows_dev, p.member_dev = rows.to(dev), member.to(dev)
+    p.workspace = p.recall = p.score = p.head_pattern = None
+    p.n_chunks = 0
+    return p
+
+
+def attn_profile_chunks(S: int, B: int, H: int) -> int:
+    return _lib.load().g3_attn_profile_chunks(S, B, H)
+
+
+def attn_pattern_profile(q: torch.Tensor, k: torch.Tensor, S: int, B: int, H: int, plan: AttnProfilePlan, softmax_scale: Optional[float] = None,
+                         n_chunks: Optional[int] = None, head_pattern_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per head, the pattern of plan.table that keeps most of the softmax mass of the plan's sample rows (g3_attn_pattern_profile_bf16 +
+    g3_attn_pattern_select; the function: include/gen3c_hip.h): q, k [S*B, H*128] as for self_attn_ranges (column views of a fused buffer are
+    fine). Returns the DEVICE int32 [H] head_pattern (plan.head_pattern, or head_pattern_out where given) with plan.recall and plan.score filled -
+    everything on the current stream, nothing read back."""
+    if not isinstance(plan, AttnProfilePlan):
+        raise ValueError("attn_pattern_profile: plan must come from ops.attn_profile_plan")
+    t = plan.table
+    if t.S != S:
+        raise ValueError(f"attn_pattern_profile: the plan was made for S = {t.S}; the call has S = {S}")
+    if t.ranges_dev.device != q.device:
+        raise ValueError(f"attn_pattern_profile: the plan lives on {t.ranges_dev.device}, q on {q.device}")
+    qr, qw, ldq = _rowmajor2d(q, "q")
+    kr, kw, ldk = _rowmajor2d(k, "k")
+    assert qr == S * B and kr == S * B and qw == H * 128 and kw == H * 128
+    lib = _lib.load()
+    nc = int(n_chunks) if n_chunks is not None else lib.g3_attn_profile_chunks(S, B, H)
+    if plan.recall is None or tuple(plan.recall.shape[:2]) != (B, H) or plan.n_chunks < nc:
+        plan.workspace = torch.empty(max(lib.g3_attn_profile_workspace_bytes(B, H, max(nc, 1)) // 4, 1), dtype=torch.float32, device=q.device)
+        plan.recall = torch.empty((B, H, plan.n, t.n_patterns), dtype=torch.float32, device=q.device)
+        plan.score = torch.empty((H, t.n_patterns), dtype=torch.float32, device=q.device)
+        plan.head_pattern = torch.empty(H, dtype=torch.int32, device=q.device)
+        plan.n_chunks = max(nc, 1)
+    hp = plan.head_pattern if head_pattern_out is None else head_pattern_out
+    if hp.dtype != torch.int32 or hp.numel() != H or not hp.is_contiguous() or hp.device != q.device:
+        raise ValueError(f"attn_pattern_profile: head_pattern_out must be a contiguous int32 [{H}] on {q.device}")
+    scale = float(1.0 / math.sqrt(128) if softmax_scale is None else softmax_scale)
+    _lib.check(lib.g3_attn_pattern_profile_bf16(_dev(q, "q"), ldq * B, ldq, 128, _dev(k, "k"), ldk * B, ldk, 128, S, B, H, 128, scale,
+                                                _dev(plan.sample_rows_dev, "sample_rows", torch.int32), plan.n,
+                                                _dev(plan.member_dev, "tile_member", torch.uint8), t.n_patterns, nc,
+                                                _dev(plan.workspace, "workspace", torch.float32), plan.workspace.numel() * 4,
+                                                _dev(plan.recall, "recall", torch.float32), _stream()), "g3_attn_pattern_profile_bf16")
+    _lib.check(lib.g3_attn_pattern_select(_dev(plan.recall, "recall", torch.float32), B, H, plan.n, t.n_patterns, _dev(plan.score, "score", torch.float32),
+                                          _dev(hp, "head_pattern", torch.int32), _stream()), "g3_attn_pattern_select")
+    return hp
 
 
 def ranges_attn_mask(table_or_array, S: int, pattern: int = 0) -> torch.Tensor:
@@ -701,7 +782,7 @@ _ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _
 
 
 def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
-               logit_bound=0.0, window=None, window_cp=None, ranges=None):
+               logit_bound=0.0, window=None, window_cp=None, ranges=None, head_pattern_dev=None):
     """The one marshaller of flash_attn, self_attn_bounded, self_attn_window, self_attn_window_cp and self_attn_ranges, which only choose the C entry point: shape checks, outputs, the entry's arguments, the
     launch and the kernel timer."""
     skip_begin, skip_len = (int(kv_skip[0]), int(kv_skip[1])) if kv_skip is not None else (0, 0)
@@ -746,8 +827,9 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
         a.update(total_frames=window_cp[0], q_frame0=window_cp[1], buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3])
     if ranges is not None:
         assert vt.dim() == 4 and Sq == Skv, "the range-table form takes plain V^T and Sq == Skv"
+        hp_dev = head_pattern_dev if head_pattern_dev is not None else ranges.head_pattern_dev  # (a per-launch choice in place of the table's own)
         a.update(ranges=_dev(ranges.ranges_dev, "ranges", torch.int32), n_patterns=ranges.n_patterns, max_ranges=ranges.max_ranges,
-                 head_pattern=_dev(ranges.head_pattern_dev, "head_pattern", torch.int32) if ranges.head_pattern_dev is not None else 0)
+                 head_pattern=_dev(hp_dev, "head_pattern", torch.int32) if hp_dev is not None else 0)
     entry_id, symbol, names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
     timer = None

@@ -97,34 +97,132 @@ def radial_ranges(T: int, frame_len: int, width1: float = 0.25, sink_frames: int
     return _table("radial_ranges", lists)
 
 
-def parse_pattern(text):
-    """'radial:WIDTH1:SINK' | 'frame:W:S' (the command lines' --self_attn_pattern and G3_SELF_ATTN_PATTERN) -> the DiT's spec tuple; None / '' -> None."""
-    if text is None or text == "":
-        return None
-    parts = str(text).split(":")
+def band_ranges(T: int, frame_len: int, width: float = 0.125, sink_frames: int = 1, min_width: int = 64) -> np.ndarray:
+    """The temporal-head pattern of the per-head schemes (Sparse VideoGen's "temporal head", arXiv 2502.01776, in this token order): a spatial band
+    of CONSTANT width across ALL frames, the query's own included - radial_ranges' band with a half-width that does not shrink,
+        hw = max(min_width, ceil(frame_len * width)),
+    and without its whole-own-frame clause (that is the spatial head's part). Row-level definition: the query at in-frame position pq of frame fq
+    attends the key at position pk of frame fk iff  fk < sink_frames  or  |pq - pk| < hw.
+    The table holds, per query block, the union over its rows, rounded outward to 64-key tiles, touching ranges merged."""
+    S = _check_shape("band_ranges", T, frame_len)
+    if not width > 0 or sink_frames < 0 or min_width < 1:
+        raise ValueError(f"band_ranges: width {width} must be > 0, sink_frames {sink_frames} >= 0, min_width {min_width} >= 1")
+    hw = max(int(min_width), math.ceil(frame_len * width))
+    lists = []
+    for b in range(-(-S // Q_ROWS)):
+        iv = [(0, min(int(sink_frames), T) * frame_len)]
+        for fq, p0, p1 in _block_frames(b, S, frame_len):
+            iv += [(fk * frame_len + max(0, p0 - hw + 1), fk * frame_len + min(frame_len, p1 + hw)) for fk in range(T)]
+        lists.append(_merge_tiles(iv, S))
+    return _table("band_ranges", lists)
+
+
+def stack_tables(tables) -> np.ndarray:
+    """One-or-more-pattern tables for the same S -> one table [sum of n_patterns, n_qblk, max of max_ranges, 2], zero-padded behind every terminator."""
+    tables = [np.asarray(t) for t in tables]
+    if not tables or any(t.ndim != 4 or t.shape[3] != 2 or t.dtype != np.int32 or t.shape[1] != tables[0].shape[1] for t in tables):
+        raise ValueError("stack_tables: expected int32 tables [n_patterns, n_qblk, max_ranges, 2] with one n_qblk")
+    out = np.zeros((sum(t.shape[0] for t in tables), tables[0].shape[1], max(t.shape[2] for t in tables), 2), dtype=np.int32)
+    p = 0
+    for t in tables:
+        out[p:p + t.shape[0], :, :t.shape[2]] = t
+        p += t.shape[0]
+    return out
+
+
+AUTO_MAX = 8  # candidates of an "auto" spec: the bits of the profiler's membership byte
+_EXPECTED = ("expected radial:WIDTH1:SINK or frame:W:S, or band:WIDTH:SINK, or auto=SPEC,SPEC[,...] with 2 to 8 of those (each head picks, per block and "
+             "per forward, the candidate that keeps most of its sampled rows' softmax mass)")
+
+
+def _parse_one(text: str):
+    parts = text.split(":")
     try:
-        if len(parts) == 3 and parts[0] == "radial":
-            return ("radial", float(parts[1]), int(parts[2]))
+        if len(parts) == 3 and parts[0] in ("radial", "band"):
+            return (parts[0], float(parts[1]), int(parts[2]))
         if len(parts) == 3 and parts[0] == "frame":
             return ("frame", int(parts[1]), int(parts[2]))
     except ValueError:
         pass
-    raise ValueError(f"self_attn_pattern {text!r}: expected radial:WIDTH1:SINK or frame:W:S")
+    return None
+
+
+def parse_pattern(text):
+    """'radial:WIDTH1:SINK' | 'frame:W:S' | 'band:WIDTH:SINK' | 'auto=SPEC,SPEC[,...]' (the command lines' --self_attn_pattern and
+    G3_SELF_ATTN_PATTERN) -> the DiT's spec tuple; None / '' -> None."""
+    if text is None or text == "":
+        return None
+    text = str(text)
+    if text.startswith("auto="):
+        cands = [_parse_one(t) for t in text[len("auto="):].split(",")]
+        if all(c is not None for c in cands) and 2 <= len(cands) <= AUTO_MAX:
+            return ("auto", *cands)
+    elif _parse_one(text) is not None:
+        return _parse_one(text)
+    raise ValueError(f"self_attn_pattern {text!r}: {_EXPECTED}")
+
+
+def _check_one(spec):
+    try:
+        if len(spec) == 3 and spec[0] in ("radial", "band") and float(spec[1]) > 0 and int(spec[2]) >= 0:
+            return (spec[0], float(spec[1]), int(spec[2]))
+        if len(spec) == 3 and spec[0] == "frame" and int(spec[1]) >= 0 and int(spec[2]) >= 0:
+            return ("frame", int(spec[1]), int(spec[2]))
+    except (TypeError, ValueError):
+        pass
+    return None
 
 
 def check_spec(spec):
-    """The DiT's spec tuple, normalised: ('radial', width1 > 0, sink_frames >= 0) | ('frame', W >= 0, s >= 0) | None."""
+    """The DiT's spec tuple, normalised: ('radial', width1 > 0, sink_frames >= 0) | ('frame', W >= 0, s >= 0) | ('band', width > 0, sink_frames >= 0) |
+    ('auto', spec, spec, ...) with 2 to 8 of the former | None."""
     if spec is None:
         return None
     if isinstance(spec, str):
         return check_spec(parse_pattern(spec))
-    if len(spec) == 3 and spec[0] == "radial" and float(spec[1]) > 0 and int(spec[2]) >= 0:
-        return ("radial", float(spec[1]), int(spec[2]))
-    if len(spec) == 3 and spec[0] == "frame" and int(spec[1]) >= 0 and int(spec[2]) >= 0:
-        return ("frame", int(spec[1]), int(spec[2]))
-    raise ValueError(f"self_attn_pattern {spec!r}: expected ('radial', width1 > 0, sink_frames >= 0), ('frame', W >= 0, s >= 0) or None")
+    if len(spec) >= 1 and spec[0] == "auto":
+        cands = [None if isinstance(c, str) else _check_one(c) for c in spec[1:]]
+        if 2 <= len(cands) <= AUTO_MAX and all(c is not None for c in cands):
+            return ("auto", *cands)
+    elif _check_one(spec) is not None:
+        return _check_one(spec)
+    raise ValueError(f"self_attn_pattern {spec!r}: expected ('radial', width1 > 0, sink_frames >= 0), ('frame', W >= 0, s >= 0) or None - or "
+                     f"('band', width > 0, sink_frames >= 0), or ('auto', spec, spec, ...) with 2 to 8 of those; as a string: {_EXPECTED}")
+
+
+def is_auto(spec) -> bool:
+    return spec is not None and spec[0] == "auto"
 
 
 def build_spec(spec, T: int, frame_len: int) -> np.ndarray:
-    kind, a, b = check_spec(spec)
-    return radial_ranges(T, frame_len, a, b) if kind == "radial" else frame_ranges(T, frame_len, a, b)
+    """The table of a (checked) spec: one pattern, or for ('auto', ...) its candidates stacked in their order."""
+    spec = check_spec(spec)
+    if is_auto(spec):
+        return stack_tables([build_spec(c, T, frame_len) for c in spec[1:]])
+    kind, a, b = spec
+    return {"radial": radial_ranges, "band": band_ranges, "frame": frame_ranges}[kind](T, frame_len, a, b)
+
+
+def tile_density(table: np.ndarray, S: int) -> list:
+    """Per pattern of a valid table: attended (query block, tile) pairs / all pairs."""
+    table = np.asarray(table)
+    return [float(table[p, :, :, 1].sum()) / KEY_TILE / (table.shape[1] * (S // KEY_TILE)) for p in range(table.shape[0])]
+
+
+def spec_text(spec) -> str:
+    """The command lines' string of a checked spec."""
+    if is_auto(spec):
+        return "auto=" + ",".join(spec_text(c) for c in spec[1:])
+    return f"{spec[0]}:{spec[1]}:{spec[2]}"
+
+
+def auto_report(spec, table: np.ndarray, S: int) -> list:
+    """The lines the command lines print once per shape under an ('auto', ...) spec: every candidate's tile density, and a warning where the densities
+    differ by more than a factor 1.25 - recall, the selection criterion, favours the denser candidate."""
+    dens = tile_density(table, S)
+    lines = [f"[gen3c_amd] self-attention pattern auto, S = {S}: " + ", ".join(f"{i} = {spec_text(c)} tile density {d:.3f}" for i, (c, d) in
+                                                                             enumerate(zip(spec[1:], dens)))]
+    if max(dens) > 1.25 * min(dens):
+        lines.append(f"[gen3c_amd] warning: the candidates' tile densities differ by a factor {max(dens) / min(dens):.2f} (> 1.25): heads are chosen by the "
+                     "softmax mass a candidate keeps, which favours the denser one")
+    return lines

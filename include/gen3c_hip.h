@@ -363,6 +363,41 @@ int g3_attn_ranges_check(const int32_t* ranges_host, int n_patterns, int S, int 
                          int64_t* dense);
 int g3_self_attn_ranges_max(void);
 
+/* Per-head choice among the patterns of a range table, made on the device, in stream order, from the q and k of the forward that is running (opt-in; the
+ * online head classification of the published training-free sparse schemes for video DiTs). A few query rows per head are profiled against every
+ * candidate pattern and each head gets the pattern that loses least of its softmax mass. Definitions, for sample row r = sample_rows[i] (int32,
+ * strictly ascending, in [0, S), 1 <= n <= 64), batch b, head h:
+ *   l_j            = softmax_scale * (q_r . k_j) over ALL S keys, m = max_j l_j (always a running maximum: no logit bound, no dependence on QK-norm)
+ *   recall[b][h][i][p] = sum over the keys j of the list (pattern p, block r / 256) of exp(l_j - m)  /  sum over all j of exp(l_j - m):
+ *                    the share of the row's softmax mass pattern p keeps. 2 (1 - recall) is the L1 distance between the row's dense and masked
+ *                    softmax weights; no V is needed. Membership is tile-granular, as in the attention kernel.
+ *   score[h][p]    = mean of recall over b and i, summed in that order;  head_pattern[h] = argmax_p score[h][p], the lowest index on ties.
+ * A pattern whose list holds every tile has recall == 1.0f exactly: every tile's row sum enters the dense accumulator and each member pattern's
+ * accumulator as the same value by the same operations. Deterministic: no atomics, fixed merge orders.
+ * g3_attn_pattern_profile_bf16: q, k [S*B, H*128] bf16 strided as for g3_self_attn_fwd_ranges_bf16 (element strides; row s*B + b); sample_rows and
+ *   tile_member are DEVICE pointers; tile_member is uint8 [n][S / 64], bit p = "tile in pattern p's list for that sample row's block"
+ *   (g3_attn_profile_members builds it on the host from HOST copies of a table g3_attn_ranges_check accepted); n_chunks in [1, S / 64] key chunks
+ *   (g3_attn_profile_chunks: the default, two workgroups per CU); workspace of g3_attn_profile_workspace_bytes(B, H, n_chunks) bytes; recall is
+ *   float [B][H][n][n_patterns]. The kernel clamps the sample rows to [0, S - 1].
+ * G3_ERR_ARG, with nothing launched and one message each: a NULL operand; head_dim != 128; S no positive multiple of 64; n_patterns outside [1, 8];
+ *   n outside [1, 64]; n_chunks outside [1, S / 64]; misaligned pointers (q, k 16 bytes) or strides (8 elements); a workspace too small; operands
+ *   beyond the kernel's 32-bit byte offsets over all S rows.
+ * g3_attn_pattern_profile_plan_bf16: the dry run - the kernel's name, or NULL with g3_last_error() set exactly as the call sets it; no HIP call.
+ * g3_attn_pattern_select: recall -> score [H][n_patterns] (optional, may be NULL) and int32 head_pattern [H], all on the device. */
+int g3_attn_pattern_profile_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row, int64_t k_batch,
+                                 int64_t k_head, int S, int B, int H, int head_dim, float softmax_scale, const int32_t* sample_rows, int n,
+                                 const uint8_t* tile_member, int n_patterns, int n_chunks, void* workspace, size_t workspace_bytes, float* recall,
+                                 void* stream);
+const char* g3_attn_pattern_profile_plan_bf16(const void* q, int64_t q_row, int64_t q_batch, int64_t q_head, const void* k, int64_t k_row,
+                                              int64_t k_batch, int64_t k_head, int S, int B, int H, int head_dim, float softmax_scale,
+                                              const int32_t* sample_rows, int n, const uint8_t* tile_member, int n_patterns, int n_chunks,
+                                              void* workspace, size_t workspace_bytes, float* recall);
+int g3_attn_pattern_select(const float* recall, int B, int H, int n, int n_patterns, float* score, int32_t* head_pattern, void* stream);
+size_t g3_attn_profile_workspace_bytes(int B, int H, int n_chunks);
+int g3_attn_profile_chunks(int S, int B, int H);
+int g3_attn_profile_members(const int32_t* ranges_host, int n_patterns, int S, int max_ranges, const int32_t* sample_rows_host, int n,
+                            uint8_t* member_out);
+
 int g3_attn_merge_partials_bf16(const float* const* o_parts /*host*/, const float* const* lse_parts /*host*/, int n_parts, int64_t p_row,
                                 int64_t p_batch, int64_t p_head, void* out, int64_t o_row, int64_t o_batch, int64_t o_head, int Sq, int B,
                                 int H, int head_dim, void* stream);
