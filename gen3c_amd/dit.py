@@ -15,7 +15,9 @@ absolute position embedding) once per (shape, fps).
 from __future__ import annotations
 
 import math
+import os
 from enum import Enum
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Tuple
 
 import torch
@@ -24,11 +26,17 @@ from torch import nn
 from . import ops
 from .parallel import ContextParallelAttention, split_inputs_cp
 
+
+def _env_flag(name: str, default: str) -> bool:
+    """An A/B switch of the environment, read once at import: on unless it is "0"."""
+    return os.environ.get(name, default) != "0"
+
+
 # 1: run the per-head RMSNorm + RoPE and the V transpose in the QKV projection's epilogue (g3_gemm_qk_norm_rope_bf16) instead of as separate
 # HBM-bound passes behind a plain GEMM. Measured in one process at the benchmark shape (tools/qkv_probe.py, profiles/r3_qkv_probe.txt):
 # B = 2: plain GEMM 8.23 ms; GEMM + 2 norm passes + transpose 9.21 ms; fused 11.85 ms - at one wave per SIMD nothing overlaps the
 # epilogue's VALU work and table reads, so the separate passes (0.98 ms at the HBM rate) are the default since round 3 (+2 % on the step).
-_FUSE_QKV_EPILOGUE = __import__("os").environ.get("G3_FUSE_QKV_EPILOGUE", "0") != "0"
+_FUSE_QKV_EPILOGUE = _env_flag("G3_FUSE_QKV_EPILOGUE", "0")
 
 
 # 1 (default, round 6): the V third of the self-attention QKV projection is computed with the operands SWAPPED - V^T[b] = W_v . h[:, b]^T, one GEMM per batch item whose
@@ -37,7 +45,7 @@ _FUSE_QKV_EPILOGUE = __import__("os").environ.get("G3_FUSE_QKV_EPILOGUE", "0") !
 # transpose of the fused projection's v columns (tests/test_kernels_gpu.py). 0: fused [S*B, 3D] projection + transpose (A/B).
 # The swapped GEMM's output width is the token count S, and g3_gemm_bf16_nt stores 4 columns at a time (it refuses N % 4 != 0): a token count that is
 # no multiple of 4 (a 45 x 45 patch grid = 2025 tokens, ...) takes the fused projection + transpose whatever this switch says (_v_by_operand_swap).
-_V_OPERAND_SWAP = __import__("os").environ.get("G3_V_OPERAND_SWAP", "1") != "0"
+_V_OPERAND_SWAP = _env_flag("G3_V_OPERAND_SWAP", "1")
 
 
 # True (default): the single-GPU self-attention hands the kernel a bound on its logits (ops.self_attn_bounded), computed per block from the weights
@@ -82,7 +90,7 @@ def _v_by_operand_swap(S: int) -> bool:
 # 1 (default, round 6): the cross-attention's Q goes from the projection GEMM straight into the attention kernel, which applies to_q[1]'s per-head RMSNorm while
 # it loads the rows (g3_cross_attn_fwd_bf16) - the separate norm pass (one read + one write of the [S*B, 4096] Q per block, ~10 ms of a 3.3 s step) is gone.
 # Same rounding points as the separate pass; the 128 squares are summed in another order (tests/test_kernels_gpu.py). 0: separate pass (A/B).
-_CROSS_Q_NORM_IN_ATTENTION = __import__("os").environ.get("G3_CROSS_Q_NORM_IN_ATTENTION", "1") != "0"
+_CROSS_Q_NORM_IN_ATTENTION = _env_flag("G3_CROSS_Q_NORM_IN_ATTENTION", "1")
 
 
 def _project_norm_rope(h, w, n_q, n_k, norm_q, norm_k, cos, sin, S, B, nH_total, hq=None, wq=None):
@@ -254,6 +262,9 @@ class VideoExtendGeneralDIT(nn.Module):
         self.cross_attention_skip_zero_context = True
         self._tables: Dict[tuple, tuple] = {}
         self._packed = None
+        self._vt_cache = None  # (key, V^T buffer): _vt_buffer
+        self._ca_kv_cache: Dict[tuple, tuple] = {}  # key -> (context tensor, per-block (K, V^T), dense keys): _cross_attention_kv
+        self._self_attn_last_choice = None  # the per-block head patterns of the last forward under an ("auto", ...) pattern
         self.linear_precision = "bf16"
         self.set_linear_precision(linear_precision)
         self.mxfp8_producers = "separate"
@@ -342,6 +353,10 @@ class VideoExtendGeneralDIT(nn.Module):
                 fan_out, fan_in = p.shape
                 a = math.sqrt(6.0 / (fan_in + fan_out))
                 p.uniform_(-a, a, generator=gen)
+        self._invalidate()
+
+    def _invalidate(self) -> None:
+        """The parameters were replaced, moved or rewritten: drop the fused weight copies and the cached position tables, which derive from them."""
         self._packed = None
         self._tables.clear()
 
@@ -350,16 +365,14 @@ class VideoExtendGeneralDIT(nn.Module):
         # (cosmos_predict1/diffusion/inference/inference_utils.py:240-242).
         sd = {k: v for k, v in state_dict.items() if not k.endswith("_extra_state")}
         out = super().load_state_dict(sd, strict=strict, assign=assign)
-        self._packed = None
-        self._tables.clear()
+        self._invalidate()
         return out
 
     def _apply(self, fn, *args, **kwargs):
         # .to() / .cuda() / .bfloat16() move or re-create the parameters: the fused weight copies and the cached tables would be
         # stale (or on the old device)
         out = super()._apply(fn, *args, **kwargs)
-        self._packed = None
-        self._tables.clear()
+        self._invalidate()
         return out
 
     def set_linear_precision(self, precision: str) -> None:
@@ -405,20 +418,17 @@ class VideoExtendGeneralDIT(nn.Module):
         if self.self_attn_window is None:
             return None
         W, s = self.self_attn_window
-        if self._cp_attn is not None and self.self_attn_window_cp:
-            if (Hp * Wp) % 64 != 0:
-                raise ValueError(f"self_attn_window=({W}, {s}): {Hp} x {Wp} = {Hp * Wp} tokens per latent frame is not a multiple of 64, the kernel's key tile "
-                                 "(the product size is 44 x 80 = 3520 = 55 x 64)")
-            T_all = Tp * self.cp_size
-            covers = W >= T_all - 1 or s >= T_all  # every frame of the whole sequence: the rank's ordinary schedule
-            self._cp_attn.configure(window=None if covers else (Hp * Wp, W, s))
-            return None
-        if self._cp_attn is not None:
+        if self._cp_attn is not None and not self.self_attn_window_cp:
             raise ValueError(f"self_attn_window=({W}, {s}) with context parallelism over {self.cp_size} ranks: the window form is single-GPU only. Windows under "
                              "key sharding would also cut the K / V exchange; that is later work")
         if (Hp * Wp) % 64 != 0:
             raise ValueError(f"self_attn_window=({W}, {s}): {Hp} x {Wp} = {Hp * Wp} tokens per latent frame is not a multiple of 64, the kernel's key tile "
                              "(the product size is 44 x 80 = 3520 = 55 x 64)")
+        if self._cp_attn is not None:
+            T_all = Tp * self.cp_size
+            covers = W >= T_all - 1 or s >= T_all  # every frame of the whole sequence: the rank's ordinary schedule
+            self._cp_attn.configure(window=None if covers else (Hp * Wp, W, s))
+            return None
         if W >= Tp - 1 or s >= Tp:
             return None  # the window covers every frame: the dense launch
         return (Hp * Wp, W, s)
@@ -470,7 +480,7 @@ class VideoExtendGeneralDIT(nn.Module):
     def self_attn_head_patterns(self):
         """Diagnostic (it synchronises): the per-block, per-head candidate indices the last forward under an ("auto", ...) pattern chose, as a host
         list [num_blocks][num_heads]; None where no such forward ran."""
-        hp = getattr(self, "_self_attn_last_choice", None)
+        hp = self._self_attn_last_choice
         return None if hp is None else hp.cpu().tolist()
 
     def set_mxfp8_producers(self, producers: str) -> None:
@@ -555,17 +565,17 @@ class VideoExtendGeneralDIT(nn.Module):
         self.cp_size = dist.get_world_size(cp_group)
         # default schedule of the DiT: local_first, 4 head groups - on one GPU playing one rank (tools/cp_rank_emulate.py, profiles/r6_cp_rank_shapes.txt) it is the
         # fastest or within 2 % of the fastest at cp = 2 / 4 / 8, it never waits for the first exchange, and with it the QKV projection stays ONE launch
-        # (forward()). The class default stays gather_first (bitwise equal to the single-rank attention).
+        # (_self_attn_qkv). The class default stays gather_first (bitwise equal to the single-rank attention).
         self._cp_attn = ContextParallelAttention(cp_group, head_groups=4, schedule="local_first")
         # G3_CP_CONFIG="<head groups>,<auto|w4b|wave8>,<gather_first|local_first|local_carry|head_parallel>": the configuration `python bench.py --gpus N` measured fastest on
         # this node (its `cp.chosen`), for the entry points that do not tune themselves (gen3c_single_image.py --num_gpus N, ...)
-        cfg = __import__("os").environ.get("G3_CP_CONFIG")
+        cfg = os.environ.get("G3_CP_CONFIG")
         if cfg:
             g_, kern_, sched_ = (c.strip() for c in cfg.split(","))
             self._cp_attn.configure(head_groups=int(g_), kernel=kern_, schedule=sched_)
         # G3_CP_LOGIT_BOUND=1 (opt-in, default off; --cp_logit_bound on the command lines): the key-sharding schedules hand the blocks' QK-norm logit bound to
         # their attention launches too - the no-running-max kernels of g3_self_attn_fwd_bounded_cp_bf16 (ContextParallelAttention's `bounded`)
-        if __import__("os").environ.get("G3_CP_LOGIT_BOUND", "0").strip() not in ("", "0"):
+        if os.environ.get("G3_CP_LOGIT_BOUND", "0").strip() not in ("", "0"):
             self._cp_attn.configure(bounded=True)
         self._tables.clear()
 
@@ -716,8 +726,7 @@ class VideoExtendGeneralDIT(nn.Module):
         M = crossattn_emb.shape[1]
         nH = self.num_heads
         ca_kv, ca_dense = self._cross_attention_kv(pk, crossattn_emb)
-        fa_window = self._self_attn_window_for(Tp, Hp, Wp)
-        fa_table = self._self_attn_table_for(Tp, Hp, Wp, dev)
+        fa = self._self_attn_mode(Tp, Hp, Wp, dev)
         if not self.cross_attention_skip_zero_context:
             ca_dense = 0
         for bi, blk in enumerate(pk["blocks"][: self._tune_blocks] if self._tune_blocks else pk["blocks"]):
@@ -734,67 +743,8 @@ class VideoExtendGeneralDIT(nn.Module):
             else:
                 h = ops.posemb_layernorm_modulate(xs, pos["full"], None, None, None, Tp, Hp, Wp, B, shift, scale)
                 hq = _mx_quant(blk["mx_fmt"])(h) if "mx" in blk else None
-            if self._cp_fused_qkv():
-                # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
-                # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
-                # (M = 14 080) a separate N = 4096 Q projection is 3.44 rounds of 256 x 256 tiles on 256 workgroups and ran at 77 % of its cp = 1
-                # rate (profiles/r6_cp_rank_shapes.txt); inside the N = 12 288 projection the same tiles are part of 10.3 rounds.
-                qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
-                                         wq=_mx_rows(blk, "fa_qkv", slice(None)))
-                pending = self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
-                self._cp_attn.mfma16 = _self_attn_mfma16()  # (head_parallel only)
-                # (the bound is read by head_parallel, whose launches see all keys of their heads at once as the single-GPU call below, and by the other
-                # schedules when ContextParallelAttention's `bounded` switch is on)
-                o = self._cp_attn.finish(qkv[:, :D], pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)
-            elif self._cp_attn is not None:
-                # K / V first, so their exchange is in flight while Q is still being projected (same fused weight, sliced;
-                # every output element sees the same K order, so this is bit-identical to the single fused GEMM)
-                # the per-head RMSNorm + RoPE of q and k (attention.py:262-280) run in the projections' epilogues
-                kv = _project_norm_rope(h, blk["fa_qkv"][D:], 0, D, None, blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
-                                        wq=_mx_rows(blk, "fa_qkv", slice(D, None)))  # [S*B, 2D]: k normalised + rotated, v plain
-                pending = self._cp_attn.start(kv[:, :D], kv[:, D:], S, B, nH)
-                self._cp_attn.mfma16 = _self_attn_mfma16()  # (head_parallel only)
-                q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH, hq=hq,
-                                       wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
-                o = self._cp_attn.finish(q, pending, logit_bound=blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0)  # (read with `bounded` only)
-            else:
-                if hq is not None:  # mxfp8 / mxfp6: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
-                    qkv = _mx_gemm(blk["mx_fmt"])(hq[0], hq[1], *blk["mx"]["fa_qkv"])
-                    ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
-                    q, k = qkv[:, :D], qkv[:, D:2 * D]
-                    vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
-                elif _FUSE_QKV_EPILOGUE:
-                    # [S*B, 3D]: q and k normalised + rotated; the v heads go straight into V^T (their columns of qkv stay unwritten)
-                    vt = self._vt_buffer(S, B, nH, dev)
-                    qkv = ops.gemm_qk_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, vt=vt)
-                    q, k = qkv[:, :D], qkv[:, D:2 * D]
-                elif _v_by_operand_swap(S):
-                    # q | k: plain GEMM, then normalised + rotated IN PLACE by one pass; v: projected straight into V^T (operands swapped, see _V_OPERAND_SWAP)
-                    qk = ops.gemm_nt(h, blk["fa_qkv"][:2 * D])
-                    ops.qk_rmsnorm_rope_pair(qk, blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
-                    q, k = qk[:, :D], qk[:, D:]
-                    vt = self._vt_buffer(S, B, nH, dev)
-                    hv = h.view(S, B, D)
-                    for b_ in range(B):
-                        ops.gemm_nt(blk["fa_qkv"][2 * D:], hv[:, b_], out=vt[b_].view(D, -1)[:, :S])
-                else:  # (also every S % 4 != 0) plain GEMM, then q / k normalised + rotated IN PLACE in the fused buffer and v transposed
-                    qkv = ops.gemm_nt(h, blk["fa_qkv"])
-                    ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)  # one pass over q | k
-                    q, k = qkv[:, :D], qkv[:, D:2 * D]
-                    vt = ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev))
-                if fa_window is not None:  # opt-in local attention (a bound out of the no-max form's range, or none: the same kernel with its running maximum)
-                    o = ops.self_attn_window(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, *fa_window)
-                elif fa_table is not None and getattr(fa_table, "profile", None) is not None:  # opt-in per-head patterns: profile, select, then the launch reads the choice
-                    fa_plan, fa_choice = fa_table.profile
-                    hp = ops.attn_pattern_profile(q, k, S, B, nH, fa_plan, head_pattern_out=fa_choice[bi])
-                    o = ops.self_attn_ranges(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, fa_table, head_pattern_dev=hp)
-                    self._self_attn_last_choice = fa_choice
-                elif fa_table is not None:  # opt-in sparse attention over a range table (likewise)
-                    o = ops.self_attn_ranges(q, k, vt, S, B, nH, blk["fa_bound"] if _SELF_ATTN_LOGIT_BOUND else 0.0, fa_table)
-                elif _SELF_ATTN_LOGIT_BOUND:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
-                    o = ops.self_attn_bounded(q, k, vt, S, S, B, nH, blk["fa_bound"], mfma16=_self_attn_mfma16())
-                else:
-                    o = ops.flash_attn(q, k, vt, S, S, B, nH)
+            q, kv = self._self_attn_qkv(blk, h, hq, cos, sin, S, B, dev)
+            o = self._self_attn(fa, bi, blk, q, kv, S, B)
             self._linear(o, blk, "fa_out", out=xs, epilogue=ops.EPI_GATED_RESIDUAL, gate=gate, residual=xs)
             # -- cross attention (unmasked over all M context tokens, general_dit.py:407-410)
             shift, scale, gate = self._modulation(emb, blk["ada"][1], adaln_lora, 3)
@@ -820,11 +770,96 @@ class VideoExtendGeneralDIT(nn.Module):
         y = ops.gemm_nt(h, P["final_layer.linear.weight"])  # [S*B, p1*p2*t*C]
         return ops.dit_unpatchify(y, B, self.out_channels, T, H, W, pt, ps)
 
+    # ------------------------------------------------------------------------------------------------ self-attention stage
+    def _self_attn_mode(self, Tp: int, Hp: int, Wp: int, dev) -> SimpleNamespace:
+        """What the self-attention launch of every block of this forward is, resolved once: mode "cp" (context parallel: the schedule of
+        self._cp_attn), "window" (window = (frame_len, W, s)), "auto" (table, with its profile plan and the per-block choice rows), "ranges"
+        (table), "bounded" or "plain"; bounded: the block's logit bound is handed over (_SELF_ATTN_LOGIT_BOUND); mfma16: _self_attn_mfma16()."""
+        window = self._self_attn_window_for(Tp, Hp, Wp)
+        table = self._self_attn_table_for(Tp, Hp, Wp, dev)
+        plan, choice = getattr(table, "profile", None) or (None, None)
+        if self._cp_attn is not None:
+            mode = "cp"
+        elif window is not None:  # opt-in local attention (a bound out of the no-max form's range, or none: the same kernel with its running maximum)
+            mode = "window"
+        elif table is not None:  # opt-in sparse attention over a range table (likewise); "auto": per-head patterns - profile, select, then the launch reads the choice
+            mode = "auto" if plan is not None else "ranges"
+        else:  # q, k are RMS-normalised per head: the kernel may drop its running maximum (falls back by itself where it cannot)
+            mode = "bounded" if _SELF_ATTN_LOGIT_BOUND else "plain"
+        return SimpleNamespace(mode=mode, window=window, table=table, plan=plan, choice=choice, bounded=_SELF_ATTN_LOGIT_BOUND, mfma16=_self_attn_mfma16())
+
+    def _self_attn_qkv(self, blk: dict, h, hq, cos, sin, S: int, B: int, dev):
+        """The QKV projection of a block with the per-head RMSNorm + RoPE of q and k (attention.py:262-280). h: the modulated bf16 activation (None
+        under fused mxfp8 producers), hq: its MX (q, scales) pair or None. -> (q, (k, V^T)) on a single GPU; under context parallelism
+        (q, pending) with the K / V exchange of self._cp_attn already started."""
+        D, nH = self.model_channels, self.num_heads
+        if self._cp_fused_qkv():
+            # local_first / local_carry start every head group on this rank's OWN K / V shard, so nothing waits for the exchange at first: one fused QKV
+            # projection + one norm / RoPE pass over q | k, then the exchange goes out under the local attention. At the cp = 8 shape
+            # (M = 14 080) a separate N = 4096 Q projection is 3.44 rounds of 256 x 256 tiles on 256 workgroups and ran at 77 % of its cp = 1
+            # rate (profiles/r6_cp_rank_shapes.txt); inside the N = 12 288 projection the same tiles are part of 10.3 rounds.
+            qkv = _project_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
+                                     wq=_mx_rows(blk, "fa_qkv", slice(None)))
+            return qkv[:, :D], self._cp_attn.start(qkv[:, D:2 * D], qkv[:, 2 * D:], S, B, nH)
+        if self._cp_attn is not None:
+            # K / V first, so their exchange is in flight while Q is still being projected (same fused weight, sliced;
+            # every output element sees the same K order, so this is bit-identical to the single fused GEMM)
+            # the per-head RMSNorm + RoPE of q and k run in the projections' epilogues
+            kv = _project_norm_rope(h, blk["fa_qkv"][D:], 0, D, None, blk["fa_kn"], cos, sin, S, B, nH, hq=hq,
+                                    wq=_mx_rows(blk, "fa_qkv", slice(D, None)))  # [S*B, 2D]: k normalised + rotated, v plain
+            pending = self._cp_attn.start(kv[:, :D], kv[:, D:], S, B, nH)
+            q = _project_norm_rope(h, blk["fa_qkv"][:D], D, 0, blk["fa_qn"], None, cos, sin, S, B, nH, hq=hq,
+                                   wq=_mx_rows(blk, "fa_qkv", slice(0, D)))
+            return q, pending
+        if hq is not None:  # mxfp8 / mxfp6: the plain fused projection, then one norm / RoPE pass over q | k and the V transpose
+            qkv = _mx_gemm(blk["mx_fmt"])(hq[0], hq[1], *blk["mx"]["fa_qkv"])
+        elif _FUSE_QKV_EPILOGUE:
+            # [S*B, 3D]: q and k normalised + rotated; the v heads go straight into V^T (their columns of qkv stay unwritten)
+            vt = self._vt_buffer(S, B, nH, dev)
+            qkv = ops.gemm_qk_norm_rope(h, blk["fa_qkv"], D, D, blk["fa_qn"], blk["fa_kn"], cos, sin, S, B, vt=vt)
+            return qkv[:, :D], (qkv[:, D:2 * D], vt)
+        elif _v_by_operand_swap(S):
+            # q | k: plain GEMM, then normalised + rotated IN PLACE by one pass; v: projected straight into V^T (operands swapped, see _V_OPERAND_SWAP)
+            qk = ops.gemm_nt(h, blk["fa_qkv"][:2 * D])
+            ops.qk_rmsnorm_rope_pair(qk, blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)
+            vt = self._vt_buffer(S, B, nH, dev)
+            hv = h.view(S, B, D)
+            for b_ in range(B):
+                ops.gemm_nt(blk["fa_qkv"][2 * D:], hv[:, b_], out=vt[b_].view(D, -1)[:, :S])
+            return qk[:, :D], (qk[:, D:], vt)
+        else:  # (also every S % 4 != 0) plain GEMM, then q / k normalised + rotated IN PLACE in the fused buffer and v transposed
+            qkv = ops.gemm_nt(h, blk["fa_qkv"])
+        ops.qk_rmsnorm_rope_pair(qkv[:, :2 * D], blk["fa_qn"], nH, blk["fa_kn"], nH, cos, sin, S, B)  # one pass over q | k
+        return qkv[:, :D], (qkv[:, D:2 * D], ops.transpose_v(qkv[:, 2 * D:], S, B, nH, out=self._vt_buffer(S, B, nH, dev)))
+
+    def _self_attn(self, fa: SimpleNamespace, bi: int, blk: dict, q, kv, S: int, B: int):
+        """The self-attention launch of block bi in the forward's mode `fa` (_self_attn_mode) on what _self_attn_qkv returned. -> o [S*B, D]"""
+        nH = self.num_heads
+        bound = blk["fa_bound"] if fa.bounded else 0.0  # the block's logit bound (_qk_logit_bounds), or none
+        if fa.mode == "cp":
+            self._cp_attn.mfma16 = fa.mfma16  # (head_parallel only)
+            # (the bound is read by head_parallel, whose launches see all keys of their heads at once as the single-GPU call below, and by the other
+            # schedules when ContextParallelAttention's `bounded` switch is on)
+            return self._cp_attn.finish(q, kv, logit_bound=bound)
+        k, vt = kv
+        if fa.mode == "window":
+            return ops.self_attn_window(q, k, vt, S, B, nH, bound, *fa.window)
+        if fa.mode == "auto":
+            hp = ops.attn_pattern_profile(q, k, S, B, nH, fa.plan, head_pattern_out=fa.choice[bi])
+            o = ops.self_attn_ranges(q, k, vt, S, B, nH, bound, fa.table, head_pattern_dev=hp)
+            self._self_attn_last_choice = fa.choice
+            return o
+        if fa.mode == "ranges":
+            return ops.self_attn_ranges(q, k, vt, S, B, nH, bound, fa.table)
+        if fa.mode == "bounded":
+            return ops.self_attn_bounded(q, k, vt, S, S, B, nH, bound, mfma16=fa.mfma16)
+        return ops.flash_attn(q, k, vt, S, S, B, nH)
+
     def _vt_buffer(self, S: int, B: int, H: int, dev) -> torch.Tensor:
         """V^T [B, H, 128, ceil64(S)] shared by all blocks of all forwards of this shape (each block overwrites positions [0, S); the zero
         tail the attention kernel relies on is written once, here)."""
         key = (S, B, H, str(dev))
-        buf = getattr(self, "_vt_cache", None)
+        buf = self._vt_cache
         if buf is None or buf[0] != key:
             buf = self._vt_cache = (key, torch.zeros((B, H, 128, ops.ceil_to(S, 64)), dtype=torch.bfloat16, device=dev))
         return buf[1]
@@ -839,7 +874,7 @@ class VideoExtendGeneralDIT(nn.Module):
         # (pk["versioned"] False) can have to_k / to_v edited in place behind an unchanged pk["key"]
         use_cache = cacheable(crossattn_emb) and pk["versioned"]
         key = (crossattn_emb.data_ptr(), tensor_version(crossattn_emb), tuple(crossattn_emb.shape), crossattn_emb.dtype, pk["key"])
-        cache = self.__dict__.setdefault("_ca_kv_cache", {})
+        cache = self._ca_kv_cache
         hit = cache.get(key) if use_cache else None
         if hit is not None and hit[0] is crossattn_emb:
             return hit[1], hit[2]

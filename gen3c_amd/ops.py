@@ -5,6 +5,7 @@ shapes and the current HIP stream to libgen3c_hip.so; none of them computes anyt
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional
 
@@ -59,17 +60,36 @@ def _rowmajor2d(t: torch.Tensor, name: str):
     return t.shape[0], t.shape[1], t.stride(0)
 
 
-def gemm_nt(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
-            gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T).  gate: [rows, N] (row = m % rows); residual: [M, N]."""
-    M, K, lda = _rowmajor2d(a, "a")
-    N, Kw, ldw = _rowmajor2d(w, "w")
-    if K != Kw:
-        raise _lib.Gen3cHipError(f"gemm_nt: K mismatch {K} vs {Kw}")
+@contextlib.contextmanager
+def _kernel_timer(kind: str, meta, on: bool = True):
+    """The one kernel timer: with timers enabled (and `on`), a hipEvent pair around the launch inside the block, collected as (kind, meta, timer) -
+    meta a dict, or a callable that makes it once the launch has returned. A launch that raises collects nothing."""
+    if _KERNEL_TIMERS is None or not on:
+        yield
+        return
+    timer = HipTimer()
+    timer.start()
+    yield
+    timer.stop()
+    _KERNEL_TIMERS.append((kind, meta() if callable(meta) else meta, timer))
+
+
+def _gemm_timer(kind: str, M: int, N: int, K: int, epilogue: int):
+    """The timer of the block GEMMs (M >= 4096); tiny ones (context K/V, embeddings of a few rows) are not worth an event pair."""
+    return _kernel_timer(kind, dict(M=M, N=N, K=K, epilogue=epilogue), M >= 4096)
+
+
+def _out_bf16(out: Optional[torch.Tensor], M: int, N: int, device):
+    """The bf16 [M, N] output of an op: allocated, or the caller's (any row stride), checked. -> out, its row stride"""
     if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
+        out = torch.empty((M, N), dtype=torch.bfloat16, device=device)
     Mo, No, ldc = _rowmajor2d(out, "out")
     assert (Mo, No) == (M, N)
+    return out, ldc
+
+
+def _gate_residual(gate: Optional[torch.Tensor], residual: Optional[torch.Tensor], M: int, N: int):
+    """The epilogue operands of the GEMM entries: gate [rows, N], residual [M, N], either may be None. -> gate, gate_rows, ldg, residual, ldr"""
     gp, grows, ldg, rp, ldr = 0, 1, 0, 0, 0
     if gate is not None:
         grows, gn, ldg = _rowmajor2d(gate, "gate")
@@ -79,16 +99,29 @@ def gemm_nt(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None
         rm, rn, ldr = _rowmajor2d(residual, "residual")
         assert (rm, rn) == (M, N)
         rp = _dev(residual, "residual")
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None and M >= 4096:  # the block GEMMs; tiny ones (context K/V, embeddings of a few rows) are not worth an event pair
-        timer = HipTimer()
-        timer.start()
-    _lib.check(lib.g3_gemm_bf16_nt(_dev(a, "a"), lda, _dev(w, "w"), ldw, _dev(out, "out"), ldc, M, N, K, epilogue, gp, grows,
-                                   ldg, rp, ldr, _stream()), "g3_gemm_bf16_nt")
-    if timer is not None:
-        timer.stop()
-        _KERNEL_TIMERS.append(("gemm_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    return gp, grows, ldg, rp, ldr
+
+
+def _rope_tables(cos: Optional[torch.Tensor], sin: Optional[torch.Tensor], S: int):
+    """The RoPE tables cos / sin, contiguous fp32 [S, 128], or None for no rotation. -> their pointers (0, 0 without)"""
+    if cos is None:
+        return 0, 0
+    assert cos.shape == (S, 128) and sin.shape == (S, 128) and cos.is_contiguous() and sin.is_contiguous()
+    return _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32)
+
+
+def gemm_nt(a: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None, epilogue: int = EPI_NONE,
+            gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T).  gate: [rows, N] (row = m % rows); residual: [M, N]."""
+    M, K, lda = _rowmajor2d(a, "a")
+    N, Kw, ldw = _rowmajor2d(w, "w")
+    if K != Kw:
+        raise _lib.Gen3cHipError(f"gemm_nt: K mismatch {K} vs {Kw}")
+    out, ldc = _out_bf16(out, M, N, a.device)
+    epi = _gate_residual(gate, residual, M, N)
+    with _gemm_timer("gemm_nt", M, N, K, epilogue):
+        _lib.check(_lib.load().g3_gemm_bf16_nt(_dev(a, "a"), lda, _dev(w, "w"), ldw, _dev(out, "out"), ldc, M, N, K, epilogue, *epi, _stream()),
+                   "g3_gemm_bf16_nt")
     return out
 
 
@@ -96,29 +129,27 @@ def quant_mxfp8(x: torch.Tensor, out=None):
     """MXFP8 (OCP MX, e4m3fn) of a bf16 [M, K] matrix: (q [M, K] torch.float8_e4m3fn, scales [M, K/32] torch.uint8 E8M0).
     out: an optional (q, scales) pair to write into. See g3_quant_mxfp8_bf16 for the rounding rule."""
     M, K, ldx = _rowmajor2d(x, "x")
-    if out is None:
-        out = (torch.empty((M, K), dtype=torch.float8_e4m3fn, device=x.device), torch.empty((M, K // 32), dtype=torch.uint8, device=x.device))
-    q, s = out
-    Mq, Kq, ldq = _rowmajor2d(q, "q")
-    Ms, Ks, lds = _rowmajor2d(s, "scales")
-    if (Mq, Kq) != (M, K) or (Ms, Ks) != (M, K // 32):
-        raise _lib.Gen3cHipError(f"quant_mxfp8: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match x {tuple(x.shape)}")
-    lib = _lib.load()
-    _lib.check(lib.g3_quant_mxfp8_bf16(_dev(x, "x"), ldx, _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, M, K,
-                                       _stream()), "g3_quant_mxfp8_bf16")
+    q, s, ldq, lds = _mx_out_pair(out, M, K, x.device, "quant_mxfp8", of=f"x {tuple(x.shape)}")
+    _lib.check(_lib.load().g3_quant_mxfp8_bf16(_dev(x, "x"), ldx, _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, M, K,
+                                               _stream()), "g3_quant_mxfp8_bf16")
     return q, s
 
 
-def _mx_operands(aq, as_, wq, ws):
-    """Shapes and strides of the MXFP8 operands of both GEMM forms, checked against each other. -> M, N, K, lda, ldas, ldw, ldws"""
+def _mx_operands(what: str, aq, as_, wq, ws):
+    """Shapes and strides of the MX operands and their scales, checked against each other: MXFP8 (gemm_mxfp8_nt, both forms) or MXFP6
+    (gemm_mxfp6_nt), whose K comes from the packed row bytes - 32 six-bit codes per 24. -> M, N, K, lda, ldas, ldw, ldws"""
     M, K, lda = _rowmajor2d(aq, "aq")
     N, Kw, ldw = _rowmajor2d(wq, "wq")
-    if K != Kw:
-        raise _lib.Gen3cHipError(f"gemm_mxfp8_nt: K mismatch {K} vs {Kw}")
+    if what == "gemm_mxfp6_nt":
+        if K != Kw or K % 24:
+            raise _lib.Gen3cHipError(f"gemm_mxfp6_nt: packed row bytes {K} vs {Kw} (must be equal and a multiple of 24)")
+        K = K // 3 * 4
+    elif K != Kw:
+        raise _lib.Gen3cHipError(f"{what}: K mismatch {K} vs {Kw}")
     Ma, Ka, ldas = _rowmajor2d(as_, "as_")
     Nw, Kws, ldws = _rowmajor2d(ws, "ws")
     if (Ma, Nw) != (M, N) or Ka * 32 != K or Kws * 32 != K:
-        raise _lib.Gen3cHipError(f"gemm_mxfp8_nt: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
+        raise _lib.Gen3cHipError(f"{what}: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
     return M, N, K, lda, ldas, ldw, ldws
 
 
@@ -130,32 +161,14 @@ def gemm_mxfp8_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: tor
     written (g3_gemm_mxfp8_nt_mxout; NONE and GELU only); returns (q, scales)."""
     if out_mx is not None and out_mx is not False:
         return _gemm_mxfp8_nt_mxout(aq, as_, wq, ws, out_mx, epilogue, out, gate, residual)
-    M, N, K, lda, ldas, ldw, ldws = _mx_operands(aq, as_, wq, ws)
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
-    Mo, No, ldc = _rowmajor2d(out, "out")
-    assert (Mo, No) == (M, N)
-    gp, grows, ldg, rp, ldr = 0, 1, 0, 0, 0
-    if gate is not None:
-        grows, gn, ldg = _rowmajor2d(gate, "gate")
-        assert gn == N
-        gp = _dev(gate, "gate")
-    if residual is not None:
-        rm, rn, ldr = _rowmajor2d(residual, "residual")
-        assert (rm, rn) == (M, N)
-        rp = _dev(residual, "residual")
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None and M >= 4096:
-        timer = HipTimer()
-        timer.start()
+    M, N, K, lda, ldas, ldw, ldws = _mx_operands("gemm_mxfp8_nt", aq, as_, wq, ws)
+    out, ldc = _out_bf16(out, M, N, aq.device)
+    epi = _gate_residual(gate, residual, M, N)
     f8 = torch.float8_e4m3fn
-    _lib.check(lib.g3_gemm_mxfp8_nt(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
-                                    _dev(ws, "ws", torch.uint8), ldws, _dev(out, "out"), ldc, M, N, K, epilogue, gp, grows, ldg, rp, ldr,
-                                    _stream()), "g3_gemm_mxfp8_nt")
-    if timer is not None:
-        timer.stop()
-        _KERNEL_TIMERS.append(("gemm_mxfp8_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    with _gemm_timer("gemm_mxfp8_nt", M, N, K, epilogue):
+        _lib.check(_lib.load().g3_gemm_mxfp8_nt(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
+                                                _dev(ws, "ws", torch.uint8), ldws, _dev(out, "out"), ldc, M, N, K, epilogue, *epi, _stream()),
+                   "g3_gemm_mxfp8_nt")
     return out
 
 
@@ -180,71 +193,39 @@ def gemm_mxfp6_nt(aq: torch.Tensor, as_: torch.Tensor, wq: torch.Tensor, ws: tor
                   epilogue: int = EPI_NONE, gate: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None):
     """out[M,N] = epi(dequant(aq, as_) @ dequant(wq, ws)^T) on the block-scaled matrix cores at the MXFP6 rate; operands as quant_mxfp6
     returns them. Same epilogues and rounding points as gemm_nt (NONE, GELU, GATED_RESIDUAL; out may be the residual)."""
-    M, Kb, lda = _rowmajor2d(aq, "aq")
-    N, Kwb, ldw = _rowmajor2d(wq, "wq")
-    if Kb != Kwb or Kb % 24:
-        raise _lib.Gen3cHipError(f"gemm_mxfp6_nt: packed row bytes {Kb} vs {Kwb} (must be equal and a multiple of 24)")
-    K = Kb // 3 * 4
-    Ma, Ka, ldas = _rowmajor2d(as_, "as_")
-    Nw, Kws, ldws = _rowmajor2d(ws, "ws")
-    if (Ma, Nw) != (M, N) or Ka * 32 != K or Kws * 32 != K:
-        raise _lib.Gen3cHipError(f"gemm_mxfp6_nt: scale shapes {tuple(as_.shape)} / {tuple(ws.shape)} do not match operands [{M}, {K}] / [{N}, {K}]")
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=aq.device)
-    Mo, No, ldc = _rowmajor2d(out, "out")
-    assert (Mo, No) == (M, N)
-    gp, grows, ldg, rp, ldr = 0, 1, 0, 0, 0
-    if gate is not None:
-        grows, gn, ldg = _rowmajor2d(gate, "gate")
-        assert gn == N
-        gp = _dev(gate, "gate")
-    if residual is not None:
-        rm, rn, ldr = _rowmajor2d(residual, "residual")
-        assert (rm, rn) == (M, N)
-        rp = _dev(residual, "residual")
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None and M >= 4096:
-        timer = HipTimer()
-        timer.start()
+    M, N, K, lda, ldas, ldw, ldws = _mx_operands("gemm_mxfp6_nt", aq, as_, wq, ws)
+    out, ldc = _out_bf16(out, M, N, aq.device)
+    epi = _gate_residual(gate, residual, M, N)
     u8 = torch.uint8
-    _lib.check(lib.g3_gemm_mxfp6_nt(_dev(aq, "aq", u8), lda, _dev(as_, "as_", u8), ldas, _dev(wq, "wq", u8), ldw, _dev(ws, "ws", u8), ldws,
-                                    _dev(out, "out"), ldc, M, N, K, epilogue, gp, grows, ldg, rp, ldr, _stream()), "g3_gemm_mxfp6_nt")
-    if timer is not None:
-        timer.stop()
-        _KERNEL_TIMERS.append(("gemm_mxfp6_nt", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    with _gemm_timer("gemm_mxfp6_nt", M, N, K, epilogue):
+        _lib.check(_lib.load().g3_gemm_mxfp6_nt(_dev(aq, "aq", u8), lda, _dev(as_, "as_", u8), ldas, _dev(wq, "wq", u8), ldw, _dev(ws, "ws", u8), ldws,
+                                                _dev(out, "out"), ldc, M, N, K, epilogue, *epi, _stream()), "g3_gemm_mxfp6_nt")
     return out
 
 
-def _mx_out_pair(out, M: int, K: int, device, what: str):
-    """The (q, scales) pair an MXFP8-producing op writes: allocated, or the caller's, checked against [M, K]. -> q, s, ldq, lds"""
+def _mx_out_pair(out, M: int, K: int, device, what: str, of: Optional[str] = None):
+    """The (q, scales) pair an MXFP8-producing op writes: allocated, or the caller's, checked against [M, K] (`of`: what the error text calls
+    it). -> q, s, ldq, lds"""
     if out is None or out is True:
         out = (torch.empty((M, K), dtype=torch.float8_e4m3fn, device=device), torch.empty((M, K // 32), dtype=torch.uint8, device=device))
     q, s = out
     Mq, Kq, ldq = _rowmajor2d(q, "q")
     Ms, Ks, lds = _rowmajor2d(s, "scales")
     if (Mq, Kq) != (M, K) or (Ms, Ks) != (M, K // 32):
-        raise _lib.Gen3cHipError(f"{what}: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match [{M}, {K}]")
+        raise _lib.Gen3cHipError(f"{what}: output shapes {tuple(q.shape)} / {tuple(s.shape)} do not match {of or f'[{M}, {K}]'}")
     return q, s, ldq, lds
 
 
 def _gemm_mxfp8_nt_mxout(aq, as_, wq, ws, out_mx, epilogue, out, gate, residual):
     if out is not None or gate is not None or residual is not None:
         raise _lib.Gen3cHipError("gemm_mxfp8_nt: out_mx takes no bf16 out, gate or residual (epilogues NONE and GELU only)")
-    M, N, K, lda, ldas, ldw, ldws = _mx_operands(aq, as_, wq, ws)
+    M, N, K, lda, ldas, ldw, ldws = _mx_operands("gemm_mxfp8_nt", aq, as_, wq, ws)
     q, s, ldq, lds = _mx_out_pair(out_mx, M, N, aq.device, "gemm_mxfp8_nt")
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None and M >= 4096:
-        timer = HipTimer()
-        timer.start()
     f8 = torch.float8_e4m3fn
-    _lib.check(lib.g3_gemm_mxfp8_nt_mxout(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
-                                          _dev(ws, "ws", torch.uint8), ldws, _dev(q, "q", f8), ldq, _dev(s, "scales", torch.uint8), lds, M, N, K,
-                                          epilogue, _stream()), "g3_gemm_mxfp8_nt_mxout")
-    if timer is not None:
-        timer.stop()
-        _KERNEL_TIMERS.append(("gemm_mxfp8_nt_mxout", dict(M=M, N=N, K=K, epilogue=epilogue), timer))
+    with _gemm_timer("gemm_mxfp8_nt_mxout", M, N, K, epilogue):
+        _lib.check(_lib.load().g3_gemm_mxfp8_nt_mxout(_dev(aq, "aq", f8), lda, _dev(as_, "as_", torch.uint8), ldas, _dev(wq, "wq", f8), ldw,
+                                                      _dev(ws, "ws", torch.uint8), ldws, _dev(q, "q", f8), ldq, _dev(s, "scales", torch.uint8), lds,
+                                                      M, N, K, epilogue, _stream()), "g3_gemm_mxfp8_nt_mxout")
     return q, s
 
 
@@ -267,12 +248,32 @@ def gemv(a: torch.Tensor, w: torch.Tensor, add: Optional[torch.Tensor] = None, a
     return out
 
 
-def layernorm_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None,
-                       eps: float = 1e-6) -> torch.Tensor:
-    """x: [rows, D] (rows = (s, b), b fastest); shift/scale: [B, D]."""
+def _modulated(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor):
+    """x [rows, D] and the AdaLN shift / scale [B, D] (one row stride) of a LayerNorm + modulate. -> rows, D, ldx, B, ldmod"""
     rows, D, ldx = _rowmajor2d(x, "x")
     B, Ds, ldmod = _rowmajor2d(shift, "shift")
     assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    return rows, D, ldx, B, ldmod
+
+
+def _posemb_modulated(x, pe_t, pe_h, pe_w, pos_norm, T: int, Hp: int, Wp: int, B: int, shift, scale):
+    """The operands both posemb_layernorm_modulate forms share, checked. -> rows, D, ldx, B of shift / scale, ldmod, the four table pointers"""
+    rows, D, ldx, Bm, ldmod = _modulated(x, shift, scale)
+    assert rows == T * Hp * Wp * B
+    if pe_h is None:
+        assert pe_w is None and pos_norm is None and pe_t.shape == (T * Hp * Wp, D) and pe_t.is_contiguous()
+    else:
+        for t, n in ((pe_t, T), (pe_h, Hp), (pe_w, Wp)):
+            assert t.dim() == 2 and t.shape[0] >= n and t.shape[1] == D and t.is_contiguous()
+        assert pos_norm.numel() == T * Hp * Wp and pos_norm.is_contiguous()
+    tables = tuple(_dev(t, n) if t is not None else 0 for t, n in ((pe_t, "pe_t"), (pe_h, "pe_h"), (pe_w, "pe_w"), (pos_norm, "pos_norm")))
+    return rows, D, ldx, Bm, ldmod, tables
+
+
+def layernorm_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out: Optional[torch.Tensor] = None,
+                       eps: float = 1e-6) -> torch.Tensor:
+    """x: [rows, D] (rows = (s, b), b fastest); shift/scale: [B, D]."""
+    rows, D, ldx, B, ldmod = _modulated(x, shift, scale)
     if out is None:
         out = torch.empty((rows, D), dtype=torch.bfloat16, device=x.device)
     lib = _lib.load()
@@ -285,9 +286,7 @@ def layernorm_modulate(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor
 def layernorm_modulate_mxfp8(x: torch.Tensor, shift: torch.Tensor, scale: torch.Tensor, out=None, eps: float = 1e-6):
     """layernorm_modulate with the result as MXFP8: returns (q [rows, D] float8_e4m3fn, scales [rows, D/32] uint8), bitwise
     quant_mxfp8(layernorm_modulate(x, shift, scale)) without the bf16 tensor in between. out: an optional (q, scales) pair to write into."""
-    rows, D, ldx = _rowmajor2d(x, "x")
-    B, Ds, ldmod = _rowmajor2d(shift, "shift")
-    assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    rows, D, ldx, B, ldmod = _modulated(x, shift, scale)
     q, s, ldq, lds = _mx_out_pair(out, rows, D, x.device, "layernorm_modulate_mxfp8")
     lib = _lib.load()
     _lib.check(lib.g3_layernorm_modulate_mxfp8(_dev(x, "x"), ldx, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, B,
@@ -302,23 +301,11 @@ def posemb_layernorm_modulate(x: torch.Tensor, pe_t: torch.Tensor, pe_h: Optiona
     """x [T*Hp*Wp*B, D] += per-block absolute position embedding (IN PLACE), returns LayerNorm(x)*(1+scale)+shift.
     Either the three axis tables + norm (the kernel rebuilds every row), or pe_h = pe_w = pos_norm = None and pe_t the finished embedding
     [T*Hp*Wp, D] (one table read per row). See g3_posemb_layernorm_modulate_bf16."""
-    rows, D, ldx = _rowmajor2d(x, "x")
-    assert rows == T * Hp * Wp * B
-    if pe_h is None:
-        assert pe_w is None and pos_norm is None and pe_t.shape == (T * Hp * Wp, D) and pe_t.is_contiguous()
-    else:
-        for t, n in ((pe_t, T), (pe_h, Hp), (pe_w, Wp)):
-            assert t.dim() == 2 and t.shape[0] >= n and t.shape[1] == D and t.is_contiguous()
-        assert pos_norm.numel() == T * Hp * Wp and pos_norm.is_contiguous()
-    Bm, Ds, ldmod = _rowmajor2d(shift, "shift")
-    assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    rows, D, ldx, Bm, ldmod, tables = _posemb_modulated(x, pe_t, pe_h, pe_w, pos_norm, T, Hp, Wp, B, shift, scale)
     if out is None:
         out = torch.empty((rows, D), dtype=torch.bfloat16, device=x.device)
-    lib = _lib.load()
-    _lib.check(lib.g3_posemb_layernorm_modulate_bf16(_dev(x, "x"), ldx, _dev(pe_t, "pe_t"), _dev(pe_h, "pe_h") if pe_h is not None else 0,
-                                                     _dev(pe_w, "pe_w") if pe_w is not None else 0, _dev(pos_norm, "pos_norm") if pos_norm is not None else 0,
-                                                     T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
-                                                     _dev(out, "out"), out.stride(0), D, eps, _stream()), "g3_posemb_layernorm_modulate_bf16")
+    _lib.check(_lib.load().g3_posemb_layernorm_modulate_bf16(_dev(x, "x"), ldx, *tables, T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
+                                                             _dev(out, "out"), out.stride(0), D, eps, _stream()), "g3_posemb_layernorm_modulate_bf16")
     return out
 
 
@@ -326,22 +313,10 @@ def posemb_layernorm_modulate_mxfp8(x: torch.Tensor, pe_t: torch.Tensor, pe_h: O
                                     pos_norm: Optional[torch.Tensor], T: int, Hp: int, Wp: int, B: int, shift: torch.Tensor, scale: torch.Tensor,
                                     out=None, eps: float = 1e-6):
     """posemb_layernorm_modulate (x updated IN PLACE the same way) with the result as MXFP8: returns (q, scales) as layernorm_modulate_mxfp8."""
-    rows, D, ldx = _rowmajor2d(x, "x")
-    assert rows == T * Hp * Wp * B
-    if pe_h is None:
-        assert pe_w is None and pos_norm is None and pe_t.shape == (T * Hp * Wp, D) and pe_t.is_contiguous()
-    else:
-        for t, n in ((pe_t, T), (pe_h, Hp), (pe_w, Wp)):
-            assert t.dim() == 2 and t.shape[0] >= n and t.shape[1] == D and t.is_contiguous()
-        assert pos_norm.numel() == T * Hp * Wp and pos_norm.is_contiguous()
-    Bm, Ds, ldmod = _rowmajor2d(shift, "shift")
-    assert Ds == D and scale.shape == shift.shape and scale.stride(0) == ldmod
+    rows, D, ldx, Bm, ldmod, tables = _posemb_modulated(x, pe_t, pe_h, pe_w, pos_norm, T, Hp, Wp, B, shift, scale)
     q, s, ldq, lds = _mx_out_pair(out, rows, D, x.device, "posemb_layernorm_modulate_mxfp8")
-    lib = _lib.load()
-    _lib.check(lib.g3_posemb_layernorm_modulate_mxfp8(_dev(x, "x"), ldx, _dev(pe_t, "pe_t"), _dev(pe_h, "pe_h") if pe_h is not None else 0,
-                                                      _dev(pe_w, "pe_w") if pe_w is not None else 0, _dev(pos_norm, "pos_norm") if pos_norm is not None else 0,
-                                                      T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
-                                                      _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, D, eps, _stream()),
+    _lib.check(_lib.load().g3_posemb_layernorm_modulate_mxfp8(_dev(x, "x"), ldx, *tables, T, Hp, Wp, B, _dev(shift, "shift"), _dev(scale, "scale"), ldmod, Bm,
+                                                              _dev(q, "q", torch.float8_e4m3fn), ldq, _dev(s, "scales", torch.uint8), lds, D, eps, _stream()),
                "g3_posemb_layernorm_modulate_mxfp8")
     return q, s
 
@@ -353,10 +328,7 @@ def qk_rmsnorm_rope(x: torch.Tensor, weight: torch.Tensor, cos: Optional[torch.T
     assert rows == S * B and width == H * 128
     if out is None:
         out = torch.empty((rows, H * 128), dtype=torch.bfloat16, device=x.device)
-    cp = sp = 0
-    if cos is not None:
-        assert cos.shape == (S, 128) and sin.shape == (S, 128) and cos.is_contiguous() and sin.is_contiguous()
-        cp, sp = _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32)
+    cp, sp = _rope_tables(cos, sin, S)
     lib = _lib.load()
     _lib.check(lib.g3_qk_rmsnorm_rope_bf16(_dev(x, "x"), ld_in, _dev(weight, "weight"), cp, sp, _dev(out, "out"),
                                            out.stride(0), S, B, H, 128, eps, _stream()), "g3_qk_rmsnorm_rope_bf16")
@@ -371,10 +343,7 @@ def qk_rmsnorm_rope_pair(x: torch.Tensor, weight_q: torch.Tensor, H_q: int, weig
     assert rows == S * B and width == (H_q + H_k) * 128
     if out is None:
         out = x
-    cp = sp = 0
-    if cos is not None:
-        assert cos.shape == (S, 128) and sin.shape == (S, 128) and cos.is_contiguous() and sin.is_contiguous()
-        cp, sp = _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32)
+    cp, sp = _rope_tables(cos, sin, S)
     lib = _lib.load()
     _lib.check(lib.g3_qk_rmsnorm_rope_pair_bf16(_dev(x, "x"), ld_in, _dev(weight_q, "weight_q"), H_q, _dev(weight_k, "weight_k"), H_k, cp, sp, _dev(out, "out"),
                                                 out.stride(0), S, B, 128, eps, _stream()), "g3_qk_rmsnorm_rope_pair_bf16")
@@ -390,31 +359,17 @@ def gemm_qk_norm_rope(a: torch.Tensor, w: torch.Tensor, n_q: int, n_k: int, norm
     M, K, lda = _rowmajor2d(a, "a")
     N, Kw, ldw = _rowmajor2d(w, "w")
     assert K == Kw and M == S * B
-    if out is None:
-        out = torch.empty((M, N), dtype=torch.bfloat16, device=a.device)
-    Mo, No, ldc = _rowmajor2d(out, "out")
-    assert (Mo, No) == (M, N)
-    cp = sp = 0
-    if cos is not None:
-        assert cos.shape == (S, 128) and sin.shape == (S, 128) and cos.is_contiguous() and sin.is_contiguous()
-        cp, sp = _dev(cos, "cos", torch.float32), _dev(sin, "sin", torch.float32)
-    lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None and M >= 4096:
-        timer = HipTimer()
-        timer.start()
+    out, ldc = _out_bf16(out, M, N, a.device)
+    cp, sp = _rope_tables(cos, sin, S)
     vtp, vt_ld = 0, 0
     if vt is not None:
         n_v = N - n_q - n_k
         assert n_v > 0 and vt.dim() == 4 and vt.shape[:3] == (B, n_v // 128, 128) and vt.shape[3] >= S and vt.is_contiguous()
         vtp, vt_ld = _dev(vt, "vt"), vt.shape[3]
-    _lib.check(lib.g3_gemm_qk_norm_rope_bf16(_dev(a, "a"), lda, _dev(w, "w"), ldw, _dev(out, "out"), ldc, M, N, K, n_q, n_k,
-                                             _dev(norm_q, "norm_q") if n_q else 0, _dev(norm_k, "norm_k") if n_k else 0, cp, sp, B, eps, vtp, vt_ld,
-                                             _stream()),
-               "g3_gemm_qk_norm_rope_bf16")
-    if timer is not None:
-        timer.stop()
-        _KERNEL_TIMERS.append(("gemm_nt", dict(M=M, N=N, K=K, epilogue=5), timer))
+    with _gemm_timer("gemm_nt", M, N, K, 5):  # (collected with the block GEMMs, under an epilogue number of its own)
+        _lib.check(_lib.load().g3_gemm_qk_norm_rope_bf16(_dev(a, "a"), lda, _dev(w, "w"), ldw, _dev(out, "out"), ldc, M, N, K, n_q, n_k,
+                                                         _dev(norm_q, "norm_q") if n_q else 0, _dev(norm_k, "norm_k") if n_k else 0, cp, sp, B, eps,
+                                                         vtp, vt_ld, _stream()), "g3_gemm_qk_norm_rope_bf16")
     return out
 
 
@@ -735,50 +690,44 @@ def window_attn_mask(S: int, frame_len: int, window_frames: int, sink_frames: in
         if S <= 0 or frame_len <= 0 or S % frame_len or q_row0 < 0 or q_row0 % frame_len or q_row0 + S > T_total * frame_len or window_frames < 0 or sink_frames < 0:
             raise ValueError(f"window_attn_mask: S {S} and q_row0 {q_row0} must be multiples of frame_len {frame_len} (S positive) within T_total {T_total} "
                              f"frames, window_frames {window_frames} and sink_frames {sink_frames} >= 0")
-        q_rows = window_q_rows() if q_rows is None else q_rows
-        r0 = torch.arange(S) // q_rows * q_rows
-        f0 = (r0 + q_row0) // frame_len
-        f1 = (torch.clamp(r0 + q_rows, max=S) - 1 + q_row0) // frame_len
-        kf = torch.arange(T_total * frame_len) // frame_len
-        lo, hi = torch.clamp(f0 - window_frames, min=0), torch.clamp(f1 + window_frames + 1, max=T_total)
-        return ((kf[None, :] >= lo[:, None]) & (kf[None, :] < hi[:, None])) | (kf[None, :] < min(sink_frames, T_total))
-    if S <= 0 or frame_len <= 0 or S % frame_len or window_frames < 0 or sink_frames < 0:
+    elif S <= 0 or frame_len <= 0 or S % frame_len or window_frames < 0 or sink_frames < 0:
         raise ValueError(f"window_attn_mask: S {S} must be a positive multiple of frame_len {frame_len}, window_frames {window_frames} and sink_frames {sink_frames} >= 0")
+    else:
+        T_total = S // frame_len  # the single-GPU form: the rows are the whole sequence
     q_rows = window_q_rows() if q_rows is None else q_rows
-    T = S // frame_len
-    rows = torch.arange(S)
-    r0 = rows // q_rows * q_rows
-    f0 = r0 // frame_len
-    f1 = (torch.clamp(r0 + q_rows, max=S) - 1) // frame_len
-    kf = rows // frame_len  # frame of every key
-    lo, hi = torch.clamp(f0 - window_frames, min=0), torch.clamp(f1 + window_frames + 1, max=T)
-    return ((kf[None, :] >= lo[:, None]) & (kf[None, :] < hi[:, None])) | (kf[None, :] < min(sink_frames, T))
+    r0 = torch.arange(S) // q_rows * q_rows  # first row of every row's block
+    f0 = (r0 + q_row0) // frame_len
+    f1 = (torch.clamp(r0 + q_rows, max=S) - 1 + q_row0) // frame_len
+    kf = torch.arange(T_total * frame_len) // frame_len  # frame of every key
+    lo, hi = torch.clamp(f0 - window_frames, min=0), torch.clamp(f1 + window_frames + 1, max=T_total)
+    return ((kf[None, :] >= lo[:, None]) & (kf[None, :] < hi[:, None])) | (kf[None, :] < min(sink_frames, T_total))
 
 
-# The launching entry points ops uses: (enum g3_attn_entry, symbol, its arguments by name in call order - the stream follows). g3_attn_plan_bf16 takes
-# the union (_ATTN_PLAN_ARGS), so the kernel a timer records is the dry run's answer for the very arguments launched ("bounded16": g3_attn_plan16_bf16,
-# the dry run in which entry 4 stands for g3_self_attn_fwd_bounded16_bf16).
+# The launching entry points ops uses: (enum g3_attn_entry, symbol, its arguments by name in call order - the stream follows -, the symbol of its dry run,
+# that one's arguments). g3_attn_plan_bf16 takes the entry and the union of the arguments (_ATTN_PLAN), so the kernel a timer records is the dry run's
+# answer for the very arguments launched ("bounded16": g3_attn_plan16_bf16, the dry run in which entry 4 stands for g3_self_attn_fwd_bounded16_bf16).
+# The window and range-table entries have no value of enum g3_attn_entry: their dry runs take exactly the call's arguments.
 _AQ, _AK, _AVT = ("q", "q_row", "q_batch", "q_head"), ("k", "k_row", "k_batch", "k_head"), ("vt", "vt_row", "vt_batch", "vt_head", "vt_seg_len", "vt_seg_stride")
 _AOUT, _ASHAPE = ("o", "o_partial", "lse", "o_row", "o_batch", "o_head"), ("Sq", "Skv", "B", "H", "head_dim", "softmax_scale")
 _ACP = ("kv_skip_begin", "kv_skip_len", "carry_o", "carry_lse")
+_ATTN_PLAN = ("g3_attn_plan_bf16", ("entry",) + _AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] +
+              ("logit_bound", "variant"))
+_ABOUNDED = _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")
+_AWINDOW = _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] + ("logit_bound", "frame_len", "window_frames", "sink_frames")
+_AWINDOW_CP = _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head") + _ASHAPE + ("logit_bound", "frame_len", "total_frames", "q_frame0", "buf_head_frames",
+                                                                                   "buf_tail_frame0", "window_frames", "sink_frames")
+_ARANGES = _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] + ("logit_bound", "ranges", "n_patterns", "max_ranges", "head_pattern")
 _ATTN_ENTRIES = {
-    "cross": (2, "g3_cross_attn_fwd_bf16", _AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq", "Skv", "kv_dense") + _ASHAPE[2:]),
-    "ex": (3, "g3_flash_attn_fwd_ex_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("variant",)),
-    "bounded": (4, "g3_self_attn_fwd_bounded_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
-    "bounded16": (4, "g3_self_attn_fwd_bounded16_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("logit_bound", "variant")),
-    "carry": (5, "g3_flash_attn_fwd_carry_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("variant",)),
-    "bounded_cp": (6, "g3_self_attn_fwd_bounded_cp_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("logit_bound", "variant")),
-    # (no value of enum g3_attn_entry: its dry run is g3_attn_window_plan_bf16, which takes exactly the call's arguments)
-    "window": (None, "g3_self_attn_fwd_window_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] +
-               ("logit_bound", "frame_len", "window_frames", "sink_frames")),
-    # (likewise: g3_attn_window_cp_plan_bf16)
-    "window_cp": (None, "g3_self_attn_fwd_window_cp_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head") + _ASHAPE +
-                  ("logit_bound", "frame_len", "total_frames", "q_frame0", "buf_head_frames", "buf_tail_frame0", "window_frames", "sink_frames")),
-    # (likewise: g3_attn_ranges_plan_bf16)
-    "ranges": (None, "g3_self_attn_fwd_ranges_bf16", _AQ + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq") + _ASHAPE[2:] +
-               ("logit_bound", "ranges", "n_patterns", "max_ranges", "head_pattern")),
+    "cross": (2, "g3_cross_attn_fwd_bf16", _AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT[:4] + ("o", "o_row", "o_batch", "o_head", "Sq", "Skv", "kv_dense") + _ASHAPE[2:]) + _ATTN_PLAN,
+    "ex": (3, "g3_flash_attn_fwd_ex_bf16", _AQ + _AK + _AVT + _AOUT + _ASHAPE + ("variant",)) + _ATTN_PLAN,
+    "bounded": (4, "g3_self_attn_fwd_bounded_bf16", _ABOUNDED) + _ATTN_PLAN,
+    "bounded16": (4, "g3_self_attn_fwd_bounded16_bf16", _ABOUNDED, "g3_attn_plan16_bf16", _ATTN_PLAN[1]),
+    "carry": (5, "g3_flash_attn_fwd_carry_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("variant",)) + _ATTN_PLAN,
+    "bounded_cp": (6, "g3_self_attn_fwd_bounded_cp_bf16", _AQ + _AK + _AVT + _ACP + _AOUT + _ASHAPE + ("logit_bound", "variant")) + _ATTN_PLAN,
+    "window": (None, "g3_self_attn_fwd_window_bf16", _AWINDOW, "g3_attn_window_plan_bf16", _AWINDOW),
+    "window_cp": (None, "g3_self_attn_fwd_window_cp_bf16", _AWINDOW_CP, "g3_attn_window_cp_plan_bf16", _AWINDOW_CP),
+    "ranges": (None, "g3_self_attn_fwd_ranges_bf16", _ARANGES, "g3_attn_ranges_plan_bf16", _ARANGES),
 }
-_ATTN_PLAN_ARGS = (_AQ + ("q_norm_weight", "q_norm_eps") + _AK + _AVT + _ACP + _AOUT + ("Sq", "Skv", "kv_dense") + _ASHAPE[2:] + ("logit_bound", "variant"))
 
 
 def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, partial, kv_dense=0, q_norm_weight=None, q_norm_eps=0.0, carry=None, kv_skip=None,
@@ -801,10 +750,7 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
             out = torch.empty((Sq * B, H * 128), dtype=torch.float32, device=q.device)
         assert out.dtype == torch.float32, "partial=True writes fp32"
         lse = torch.empty((B, H, Sq), dtype=torch.float32, device=q.device)
-    elif out is None:
-        out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=q.device)
-    orows, ow, ldo = _rowmajor2d(out, "out")
-    assert (orows, ow) == (Sq * B, H * 128)
+    out, ldo = _out_bf16(out, Sq * B, H * 128, q.device)  # (partial: the fp32 part from above, only checked)
     co = cl = 0
     if carry is not None:
         o_c, l_c = carry
@@ -830,16 +776,10 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
         hp_dev = head_pattern_dev if head_pattern_dev is not None else ranges.head_pattern_dev  # (a per-launch choice in place of the table's own)
         a.update(ranges=_dev(ranges.ranges_dev, "ranges", torch.int32), n_patterns=ranges.n_patterns, max_ranges=ranges.max_ranges,
                  head_pattern=_dev(hp_dev, "head_pattern", torch.int32) if hp_dev is not None else 0)
-    entry_id, symbol, names = _ATTN_ENTRIES[entry]
+    a["entry"], symbol, names, plan, plan_names = _ATTN_ENTRIES[entry]
     lib = _lib.load()
-    timer = None
-    if _KERNEL_TIMERS is not None:
-        timer = HipTimer()
-        timer.start()
-    _lib.check(getattr(lib, symbol)(*[a[n] for n in names], _stream()), symbol)
-    if timer is not None:
-        timer.stop()
-        # the kernel the launcher picked for THIS launch: every fallback, the per-call variant, else the library option in force
+
+    def timer_meta():
         meta = dict(Sq=Sq, Skv=Skv, B=B, H=H, partial=partial)
         if entry == "cross":
             meta.update(kv_dense=kv_dense, q_norm=q_norm_weight is not None)
@@ -848,20 +788,19 @@ def _attn_call(entry, q, k, vt, Sq, Skv, B, H, out, softmax_scale, variant, part
         if entry == "window":
             attended, dense = window_attn_tiles(Sq, *window)
             meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], tile_density=attended / dense)
-            meta["kernel"] = lib.g3_attn_window_plan_bf16(*[a[n] for n in names]).decode()
         elif entry == "window_cp":
             attended, dense = window_attn_tiles_cp(Sq, Skv, window[0], *window_cp, window[1], window[2])
             meta.update(frame_len=window[0], window_frames=window[1], sink_frames=window[2], total_frames=window_cp[0], q_frame0=window_cp[1],
                         buf_head_frames=window_cp[2], buf_tail_frame0=window_cp[3], tile_density=attended / dense)
-            meta["kernel"] = lib.g3_attn_window_cp_plan_bf16(*[a[n] for n in names]).decode()
         elif entry == "ranges":
             # (the table counts its own H heads; with no head_pattern every head runs pattern 0 and the density is the same for any H)
             meta.update(n_patterns=ranges.n_patterns, max_ranges=ranges.max_ranges, tile_density=ranges.attended / ranges.dense)
-            meta["kernel"] = lib.g3_attn_ranges_plan_bf16(*[a[n] for n in names]).decode()
-        else:
-            plan = lib.g3_attn_plan16_bf16 if entry == "bounded16" else lib.g3_attn_plan_bf16
-            meta["kernel"] = plan(entry_id, *[a[n] for n in _ATTN_PLAN_ARGS]).decode()
-        _KERNEL_TIMERS.append(("flash_attn_fwd", meta, timer))
+        # the kernel the launcher picked for THIS launch: every fallback, the per-call variant, else the library option in force
+        meta["kernel"] = getattr(lib, plan)(*[a[n] for n in plan_names]).decode()
+        return meta
+
+    with _kernel_timer("flash_attn_fwd", timer_meta):
+        _lib.check(getattr(lib, symbol)(*[a[n] for n in names], _stream()), symbol)
     return (out, lse) if partial else out
 
 
@@ -874,10 +813,7 @@ def attn_merge(parts, Sq: int, B: int, H: int, out: Optional[torch.Tensor] = Non
     ld = parts[0][0].stride(0)
     for o, l in parts:
         assert o.shape == (Sq * B, H * 128) and o.stride(1) == 1 and o.stride(0) == ld and l.shape == (B, H, Sq) and l.is_contiguous()
-    if out is None:
-        out = torch.empty((Sq * B, H * 128), dtype=torch.bfloat16, device=parts[0][0].device)
-    orows, ow, ldo = _rowmajor2d(out, "out")
-    assert (orows, ow) == (Sq * B, H * 128)
+    out, ldo = _out_bf16(out, Sq * B, H * 128, parts[0][0].device)
     op = (C.c_void_p * n)(*[_dev(o, "o_part", torch.float32) for o, _ in parts])
     lp = (C.c_void_p * n)(*[_dev(l, "lse", torch.float32) for _, l in parts])
     _lib.check(_lib.load().g3_attn_merge_partials_bf16(op, lp, n, ld * B, ld, 128, _dev(out, "out"), ldo * B, ldo, 128, Sq, B, H, 128, _stream()),
