@@ -41,6 +41,7 @@ int g3_opt_gemm_pingpong = env_int("G3_GEMM_PINGPONG", 3);  // 3: one wave per S
 int g3_opt_tok_tattn_px = env_int("G3_TOK_TATTN_PX", 1);
 int g3_opt_gemm_persistent = env_int("G3_GEMM_PERSISTENT", 0);  // measured slower or equal (profiles/r3_gemm_persistent_ab.txt): off
 int g3_opt_gemm_deferred = env_int("G3_GEMM_DEFERRED", 1);  // block GEMMs with the epilogue deferred into the next tile's K loop (gemm_w4e.hpp) where it applies
+int g3_opt_gemm_mfma16 = env_int("G3_GEMM_MFMA16", 1);  // gemm_w4e.hpp: the K loop of the deferred kernel on 16x16x32 MFMAs (bitwise the 32x32x16 body's results)
 int g3_opt_gemm_deferred_grid = env_int("G3_GEMM_DEFERRED_GRID", 0);  // tests: workgroup count of the deferred-epilogue GEMM (0 = one per CU)
 int g3_opt_gemm_tokens_first = env_int("G3_GEMM_TOKENS_FIRST", 2);  // gemm_w4e.hpp piece order: 0 weights first, 1 tokens first, 2 (default) tokens first where N <= 4096
 int g3_opt_conv_w4 = env_int("G3_CONV_W4", 1);  // tokenizer convolutions on the one-wave-per-SIMD kernel (gemm_w4_conv.hpp) where it applies
@@ -64,6 +65,7 @@ static int* opt_by_name(const char* name) {
     if (!strcmp(name, "gemm_deferred")) return &g3_opt_gemm_deferred;
     if (!strcmp(name, "gemm_tokens_first")) return &g3_opt_gemm_tokens_first;
     if (!strcmp(name, "gemm_deferred_grid")) return &g3_opt_gemm_deferred_grid;
+    if (!strcmp(name, "gemm_mfma16")) return &g3_opt_gemm_mfma16;
     if (!strcmp(name, "tok_tattn_px")) return &g3_opt_tok_tattn_px;
     if (!strcmp(name, "gemm_rowmajor_tiles")) return &g3_opt_gemm_rowmajor_tiles;
     if (!strcmp(name, "ln_wave_rows")) return &g3_opt_ln_wave_rows;

@@ -626,6 +626,11 @@ constexpr int GEMM_LDS_BYTES = 2 * (BM + BN) * BK * (int)sizeof(bf16_t);  // 128
 #define G3_GEMM_ROW(E, THREADS, LDS, FAMILY, KERNEL, ...) {G3_STR(KERNEL<E, ##__VA_ARGS__>), &KERNEL<E, ##__VA_ARGS__>, THREADS, LDS, FAMILY},
 enum GemmKernelId { G3_GEMM_FAMILIES(G3_GEMM_IDS) GK_COUNT };  // GK_<family>_<epilogue>; a family's first row is GK_<family>_0
 const GemmKernel gemm_kernels[GK_COUNT] = {G3_GEMM_FAMILIES(G3_GEMM_ROWS)};
+// The twins of the GK_W4E / GK_W4E_TF rows with the K loop on v_mfma_f32_16x16x32_bf16 (gemm_w4e.hpp), [tokens first][epilogue]: gemm_launch starts them from
+// those rows where p.mfma16 is set. No rows of their own: the plan, the names and the grid do not depend on the option, and the bits are the same.
+void (*const gemm_w4e16_twins[2][3])(GemmParams) = {
+    {&gemm_bf16_nt_w4e16_kernel<0, false>, &gemm_bf16_nt_w4e16_kernel<1, false>, &gemm_bf16_nt_w4e16_kernel<2, false>},
+    {&gemm_bf16_nt_w4e16_kernel<0, true>, &gemm_bf16_nt_w4e16_kernel<1, true>, &gemm_bf16_nt_w4e16_kernel<2, true>}};
 #undef G3_GEMM_IDS
 #undef G3_GEMM_ID
 #undef G3_GEMM_ROWS
@@ -757,6 +762,7 @@ int gemm_plan(const g3_gemm_call& call, int n_cu, GemmPlan& plan) {
     p.R = (const bf16_t*)c.residual; p.ldr = c.ldr;
     p.tiles_m = (c.M + BM - 1) / BM; p.tiles_n = (c.N + BN - 1) / BN;
     p.tile_order_rowmajor = g3_opt_gemm_rowmajor_tiles;
+    p.mfma16 = g3_opt_gemm_mfma16 != 0;
     p.wide_store = g3_opt_gemm_wide_store && !(c.N & 7) && !(c.ldc & 7) && !(at(c.C) & 15) && (!c.gate || (!(c.ldg & 7) && !(at(c.gate) & 15))) &&
                    (!c.residual || (!(c.ldr & 7) && !(at(c.residual) & 15)));
     if (conv) p.cv = ConvGeom{c.To, c.Ho, c.Wo, c.Ti, c.Hi, c.Wi, c.kt, c.kh, c.kw, c.st, c.sh, c.sw, c.ot, c.oh, c.ow, c.kt * c.kh * c.kw, (int64_t)c.N * c.ldw, g3_opt_conv_w4 != 2};
@@ -795,9 +801,16 @@ int gemm_launch(const g3_gemm_call& c) {
     if (int rc = gemm_plan(c, device_cu_count(), plan)) return rc;
     const GemmKernel& k = gemm_kernels[plan.row];
     const GemmParams& p = plan.p;
-    static bool granted[GK_COUNT][G3_MAX_DEVICES] = {};
-    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(k.fn), k.lds, granted[plan.row], "gemm")) return rc;
-    hipLaunchKernelGGL(k.fn, dim3(plan.grid), dim3(k.threads), k.lds, (hipStream_t)c.stream, p);
+    static bool granted[GK_COUNT][G3_MAX_DEVICES] = {}, granted16[6][G3_MAX_DEVICES] = {};
+    void (*fn)(GemmParams) = k.fn;
+    bool (*grant)[G3_MAX_DEVICES] = &granted[plan.row];
+    if (p.mfma16 && plan.row >= GK_W4E_0 && plan.row <= GK_W4E_TF_2) {  // the deferred kernel's 16x16x32 twin (gemm_w4e16_twins)
+        const int t = plan.row - GK_W4E_0;
+        fn = gemm_w4e16_twins[t / 3][t % 3];
+        grant = &granted16[t];
+    }
+    if (int rc = g3_grant_dynamic_lds(reinterpret_cast<const void*>(fn), k.lds, *grant, "gemm")) return rc;
+    hipLaunchKernelGGL(fn, dim3(plan.grid), dim3(k.threads), k.lds, (hipStream_t)c.stream, p);
     int rc = g3_check_launch(plan.what);
     const int S = c.B > 0 ? p.M / c.B : 0;
     if (rc == G3_OK && (plan.follow_up & G3_GEMM_THEN_NORM_Q))

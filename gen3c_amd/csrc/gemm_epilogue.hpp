@@ -34,6 +34,7 @@ struct GemmParams {
     bf16_t* vt; int64_t vt_ld, vt_batch; int vt_S;  // optional V^T destination of the remaining (v) heads: [B][H_v][128][vt_ld], S valid positions
     // gemm_w4_conv.hpp: optional GroupNorm statistics of the output ([frames][2] doubles: sum, sum of squares; frame = gn_rows consecutive rows)
     double* gn_stats = nullptr; int gn_rows = 0;
+    int mfma16 = 0;  // gemm_w4e.hpp: the K loop on v_mfma_f32_16x16x32_bf16 (option gemm_mfma16; same bits, same kernel names)
 };
 
 // ---- epilogue shared by the kernels below. acc[i][j][r]: feature = nw + 32 i + (r & 3) + 8 (r >> 2) + 4 g ; token = mw + 32 j + l31

@@ -20,6 +20,14 @@
 // equal outputs across all GEMM kernels (tests/test_kernels_gpu.py).
 
 #include "gemm_w4e_gen.hpp"
+#include "gemm_w4e16_gen.hpp"
+
+// a statement of the K loop in the body the kernel runs: gw4e_<fn> (32x32x16) or gw4e16_<fn> (16x16x32, gemm_w4e16_gen.hpp); N16 is the tile loop's constant
+#define GW4E_DO(fn, ...)                                  \
+    do {                                                  \
+        if constexpr (N16) gw4e16_##fn(__VA_ARGS__);      \
+        else gw4e_##fn(__VA_ARGS__);                      \
+    } while (0)
 
 constexpr int GW4E_LDS_BYTES = 2 * GW4_STAGE_BYTES + 32768;  // 160 KiB
 #ifndef G3_GW4E_PFD
@@ -30,8 +38,10 @@ constexpr int GW4E_MIN_NK = 38;                               // K tile 0 preamb
 // TF (token pieces first): the order in which a K tile's 16 LDS-DMA pieces are requested. false (gemm_w4.hpp's order): weight rows 0..5 two K tiles ahead (K step 3),
 // weight rows 6, 7 + token rows one tile ahead (K steps 0, 1); true: the same with the operands' roles swapped - the token panel gets the longer lead. The token
 // operand of MLP-down is a 3.7 GB stream from HBM (K = 16 384), its weights come from the L2 / Infinity Cache: host heuristic in gemm_choose, gemm.hip (N <= 4096).
-template <int EPI, bool TF>
-__global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmParams p) {
+// N16: the K loop on v_mfma_f32_16x16x32_bf16 (gemm_w4e16_gen.hpp, whose generator describes the quadrant order): gemm_bf16_nt_w4e16_kernel below. The tile
+// loop, the piece order, the barriers, the hand-over and the flush are the same code for both bodies; the results are the same bits.
+template <int EPI, bool TF, bool N16>
+G3_DEVICE void gemm_w4e_body(const GemmParams& p) {
     static_assert(EPI == EPI_NONE || EPI == EPI_GELU || EPI == EPI_GATED_RESIDUAL, "gemm_bf16_nt_w4e_kernel: epilogue class without a deferred form");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];  // [stage 2][W tile | T tile][X 4 waves x 4 KiB][Y 4 waves x 4 KiB]
     const int tid = threadIdx.x;
@@ -86,8 +96,20 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
     const uint32_t (&vo_f)[8] = TF ? vo_t : vo_w;
     const uint32_t (&vo_s)[8] = TF ? vo_w : vo_t;
     const uint32_t m0_f = TF ? m0_t : m0_w, m0_s = TF ? m0_w : m0_t;
-    uint32_t adw[2][4], adt[2][4];
-    {
+    // fragment read addresses [stage][K step]; N16: [stage][K half] - lane l reads row l & 15, 16-byte chunk (l >> 4) + 4 half of the image: fragment f of an
+    // operand at offset 2048 f, the K half is ^ 64 (tools/gen_gemm_w4e16.py)
+    uint32_t adw[2][N16 ? 2 : 4], adt[2][N16 ? 2 : 4];
+    if constexpr (N16) {
+        const int l15 = lane & 15;
+        const uint32_t c0 = (uint32_t)(((lane >> 4) ^ ((l15 >> 1) & 7)) << 4);
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) {
+                adw[st][kh] = ((lds0 + (uint32_t)((wn * 128 + l15) * 128) + c0) ^ (uint32_t)(kh << 6)) + (uint32_t)(st * GW4_STAGE_BYTES);
+                adt[st][kh] = ((lds0 + (uint32_t)((wm * 128 + l15) * 128) + c0) ^ (uint32_t)(kh << 6)) + (uint32_t)(st * GW4_STAGE_BYTES);
+            }
+    } else {
         const uint32_t c0 = (uint32_t)((g ^ ((l31 >> 1) & 7)) << 4);
 #pragma unroll
         for (int st = 0; st < 2; ++st)
@@ -102,7 +124,10 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
     const uint32_t lds_y = lds0 + 2u * GW4_STAGE_BYTES + 16384u + (uint32_t)wave * 4096u;
     const int rr = lane >> 3, cc = lane & 7;
     GW4EOps E{};  // the fields every statement of the kernel shares
-    E.xw = lds_x + (uint32_t)(l31 * 128 + 8 * g + ((l31 & 7) << 4));
+    if constexpr (N16)  // the 16 x 16 layout: features 4 (lane >> 4) .. + 3 of row lane & 15 (tools/gen_gemm_w4e16.py: xwrite_texts)
+        E.xw = lds_x + (uint32_t)((lane & 15) * 128 + ((((lane >> 5) ^ (lane & 7)) << 4)) + 8 * ((lane >> 4) & 1));
+    else
+        E.xw = lds_x + (uint32_t)(l31 * 128 + 8 * g + ((l31 & 7) << 4));
     E.xr = lds_x + (uint32_t)(rr * 128 + ((cc ^ rr) << 4));
     E.yb = lds_y + (uint32_t)lane * 16u;
     E.coff = (uint32_t)(((int64_t)rr * p.ldc + 8 * cc) * 2);
@@ -134,10 +159,16 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
                                          (__attribute__((address_space(3))) void*)(uintptr_t)(m0_f + GW4_STAGE_BYTES + 1024u * q), 16, 0, 0);
     asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     __syncthreads();
-    asm volatile("ds_read_b128 v[192:195], %0\n\tds_read_b128 v[196:199], %0 offset:4096\n\tds_read_b128 v[200:203], %0 offset:8192\n\t"
-                 "ds_read_b128 v[204:207], %0 offset:12288\n\tds_read_b128 v[208:211], %1 offset:32768\n\tds_read_b128 v[212:215], %1 offset:36864\n\t"
-                 "ds_read_b128 v[216:219], %1 offset:40960\n\tds_read_b128 v[220:223], %1 offset:45056"
-                 ::"v"(adw[0][0]), "v"(adt[0][0]) : GW4E_OWNED, "memory");
+    if constexpr (N16)  // W0-3 and T0-3 of K tile 0's first half
+        asm volatile("ds_read_b128 v[192:195], %0\n\tds_read_b128 v[196:199], %0 offset:2048\n\tds_read_b128 v[200:203], %0 offset:4096\n\t"
+                     "ds_read_b128 v[204:207], %0 offset:6144\n\tds_read_b128 v[224:227], %1 offset:32768\n\tds_read_b128 v[228:231], %1 offset:34816\n\t"
+                     "ds_read_b128 v[232:235], %1 offset:36864\n\tds_read_b128 v[236:239], %1 offset:38912"
+                     ::"v"(adw[0][0]), "v"(adt[0][0]) : GW4E_OWNED, "memory");
+    else
+        asm volatile("ds_read_b128 v[192:195], %0\n\tds_read_b128 v[196:199], %0 offset:4096\n\tds_read_b128 v[200:203], %0 offset:8192\n\t"
+                     "ds_read_b128 v[204:207], %0 offset:12288\n\tds_read_b128 v[208:211], %1 offset:32768\n\tds_read_b128 v[212:215], %1 offset:36864\n\t"
+                     "ds_read_b128 v[216:219], %1 offset:40960\n\tds_read_b128 v[220:223], %1 offset:45056"
+                     ::"v"(adw[0][0]), "v"(adt[0][0]) : GW4E_OWNED, "memory");
 
     using S0 = std::integral_constant<int, 0>;
     using S1 = std::integral_constant<int, 1>;
@@ -160,7 +191,11 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
             constexpr int S = decltype(sc)::value, KS = decltype(ksc)::value;
             constexpr uint32_t SO = S * GW4_STAGE_BYTES, SN = (S ^ 1) * GW4_STAGE_BYTES;
             GW4EOps o = E;
-            if constexpr (KS < 3) {
+            if constexpr (N16) {  // what the statement's two quadrants read: K half 0 / 1 / 1 of this stage, K half 0 of the other
+                constexpr int RS = KS == 3 ? (S ^ 1) : S, RH = (KS == 1 || KS == 2) ? 1 : 0;
+                o.adw = adw[RS][RH];
+                o.adt = adt[RS][RH];
+            } else if constexpr (KS < 3) {
                 o.adw = adw[S][KS + 1];
                 o.adt = adt[S][KS + 1];
             } else {
@@ -207,21 +242,21 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
         using K3 = std::integral_constant<int, 3>;
         auto plain_tile = [&](auto sc, int t) {
             G3_JITTER(wave + blockIdx.x, t);
-            gw4e_ks0(kops(sc, K0{}, t));
-            gw4e_ks1(kops(sc, K1{}, t));
-            gw4e_ks2_bar(kops(sc, K2{}, t));
-            gw4e_ks3(kops(sc, K3{}, t));
+            GW4E_DO(ks0, kops(sc, K0{}, t));
+            GW4E_DO(ks1, kops(sc, K1{}, t));
+            GW4E_DO(ks2_bar, kops(sc, K2{}, t));
+            GW4E_DO(ks3, kops(sc, K3{}, t));
         };
         auto xwrite = [&](int u) {  // unit u's registers -> X (the only statements that name a unit's registers)
             switch (u) {
-                case 0: gw4e_xwrite_0(E); break;
-                case 1: gw4e_xwrite_1(E); break;
-                case 2: gw4e_xwrite_2(E); break;
-                case 3: gw4e_xwrite_3(E); break;
-                case 4: gw4e_xwrite_4(E); break;
-                case 5: gw4e_xwrite_5(E); break;
-                case 6: gw4e_xwrite_6(E); break;
-                default: gw4e_xwrite_7(E); break;
+                case 0: GW4E_DO(xwrite_0, E); break;
+                case 1: GW4E_DO(xwrite_1, E); break;
+                case 2: GW4E_DO(xwrite_2, E); break;
+                case 3: GW4E_DO(xwrite_3, E); break;
+                case 4: GW4E_DO(xwrite_4, E); break;
+                case 5: GW4E_DO(xwrite_5, E); break;
+                case 6: GW4E_DO(xwrite_6, E); break;
+                default: GW4E_DO(xwrite_7, E); break;
             }
         };
         // the finished tile's unit u: first output / residual byte of its chunk 0 (rows 8 ch further per chunk)
@@ -236,10 +271,10 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
         int t = 0;
         if (carry) {
             // ---- K tile 0: preamble - unit 0 (written to X behind the drain) comes back in row layout
-            gw4e_ks0_init(kops(S0{}, K0{}, 0));
-            gw4e_ks1_pre(kops(S0{}, K1{}, 0));
-            gw4e_ks2_bar(kops(S0{}, K2{}, 0));
-            gw4e_ks3(kops(S0{}, K3{}, 0));
+            GW4E_DO(ks0_init, kops(S0{}, K0{}, 0));
+            GW4E_DO(ks1_pre, kops(S0{}, K1{}, 0));
+            GW4E_DO(ks2_bar, kops(S0{}, K2{}, 0));
+            GW4E_DO(ks3, kops(S0{}, K3{}, 0));
             // ---- 8 periods of 4 K tiles: the arithmetic and stores of unit u, the transposition of unit u + 1
             for (int u = 0; u < 8; ++u) {
                 char* cb = unit_c(u);
@@ -266,26 +301,26 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
                             }
                         }
                         if constexpr (EPI == EPI_NONE) {
-                            if constexpr (KAPPA == 0) gw4e_none_k0(o); else if constexpr (KAPPA == 1) gw4e_none_k1(o); else if constexpr (KAPPA == 2) { if (u == 0) gw4e_none_k2f(o); else gw4e_none_k2(o); }
-                            else if constexpr (KAPPA == 3) gw4e_none_k3(o); else if constexpr (KAPPA == 4) gw4e_none_k4(o); else if constexpr (KAPPA == 5) gw4e_none_k5(o);
-                            else if constexpr (KAPPA == 6) gw4e_none_k6(o); else if constexpr (KAPPA == 7) gw4e_none_k7(o); else if constexpr (KAPPA == 8) gw4e_none_k8(o);
-                            else if constexpr (KAPPA == 9) gw4e_none_k9(o); else if constexpr (KAPPA == 10) gw4e_none_k10(o); else if constexpr (KAPPA == 11) gw4e_none_k11(o);
-                            else if constexpr (KAPPA == 12) gw4e_none_k12(o); else if constexpr (KAPPA == 13) gw4e_none_k13(o); else if constexpr (KAPPA == 14) gw4e_none_k14(o);
-                            else gw4e_none_k15(o);
+                            if constexpr (KAPPA == 0) GW4E_DO(none_k0, o); else if constexpr (KAPPA == 1) GW4E_DO(none_k1, o); else if constexpr (KAPPA == 2) { if (u == 0) GW4E_DO(none_k2f, o); else GW4E_DO(none_k2, o); }
+                            else if constexpr (KAPPA == 3) GW4E_DO(none_k3, o); else if constexpr (KAPPA == 4) GW4E_DO(none_k4, o); else if constexpr (KAPPA == 5) GW4E_DO(none_k5, o);
+                            else if constexpr (KAPPA == 6) GW4E_DO(none_k6, o); else if constexpr (KAPPA == 7) GW4E_DO(none_k7, o); else if constexpr (KAPPA == 8) GW4E_DO(none_k8, o);
+                            else if constexpr (KAPPA == 9) GW4E_DO(none_k9, o); else if constexpr (KAPPA == 10) GW4E_DO(none_k10, o); else if constexpr (KAPPA == 11) GW4E_DO(none_k11, o);
+                            else if constexpr (KAPPA == 12) GW4E_DO(none_k12, o); else if constexpr (KAPPA == 13) GW4E_DO(none_k13, o); else if constexpr (KAPPA == 14) GW4E_DO(none_k14, o);
+                            else GW4E_DO(none_k15, o);
                         } else if constexpr (EPI == EPI_GELU) {
-                            if constexpr (KAPPA == 0) gw4e_gelu_k0(o); else if constexpr (KAPPA == 1) gw4e_gelu_k1(o); else if constexpr (KAPPA == 2) { if (u == 0) gw4e_gelu_k2f(o); else gw4e_gelu_k2(o); }
-                            else if constexpr (KAPPA == 3) gw4e_gelu_k3(o); else if constexpr (KAPPA == 4) gw4e_gelu_k4(o); else if constexpr (KAPPA == 5) gw4e_gelu_k5(o);
-                            else if constexpr (KAPPA == 6) gw4e_gelu_k6(o); else if constexpr (KAPPA == 7) gw4e_gelu_k7(o); else if constexpr (KAPPA == 8) gw4e_gelu_k8(o);
-                            else if constexpr (KAPPA == 9) gw4e_gelu_k9(o); else if constexpr (KAPPA == 10) gw4e_gelu_k10(o); else if constexpr (KAPPA == 11) gw4e_gelu_k11(o);
-                            else if constexpr (KAPPA == 12) gw4e_gelu_k12(o); else if constexpr (KAPPA == 13) gw4e_gelu_k13(o); else if constexpr (KAPPA == 14) gw4e_gelu_k14(o);
-                            else gw4e_gelu_k15(o);
+                            if constexpr (KAPPA == 0) GW4E_DO(gelu_k0, o); else if constexpr (KAPPA == 1) GW4E_DO(gelu_k1, o); else if constexpr (KAPPA == 2) { if (u == 0) GW4E_DO(gelu_k2f, o); else GW4E_DO(gelu_k2, o); }
+                            else if constexpr (KAPPA == 3) GW4E_DO(gelu_k3, o); else if constexpr (KAPPA == 4) GW4E_DO(gelu_k4, o); else if constexpr (KAPPA == 5) GW4E_DO(gelu_k5, o);
+                            else if constexpr (KAPPA == 6) GW4E_DO(gelu_k6, o); else if constexpr (KAPPA == 7) GW4E_DO(gelu_k7, o); else if constexpr (KAPPA == 8) GW4E_DO(gelu_k8, o);
+                            else if constexpr (KAPPA == 9) GW4E_DO(gelu_k9, o); else if constexpr (KAPPA == 10) GW4E_DO(gelu_k10, o); else if constexpr (KAPPA == 11) GW4E_DO(gelu_k11, o);
+                            else if constexpr (KAPPA == 12) GW4E_DO(gelu_k12, o); else if constexpr (KAPPA == 13) GW4E_DO(gelu_k13, o); else if constexpr (KAPPA == 14) GW4E_DO(gelu_k14, o);
+                            else GW4E_DO(gelu_k15, o);
                         } else {
-                            if constexpr (KAPPA == 0) gw4e_gated_k0(o); else if constexpr (KAPPA == 1) gw4e_gated_k1(o); else if constexpr (KAPPA == 2) { if (u == 0) gw4e_gated_k2f(o); else gw4e_gated_k2(o); }
-                            else if constexpr (KAPPA == 3) gw4e_gated_k3(o); else if constexpr (KAPPA == 4) gw4e_gated_k4(o); else if constexpr (KAPPA == 5) gw4e_gated_k5(o);
-                            else if constexpr (KAPPA == 6) gw4e_gated_k6(o); else if constexpr (KAPPA == 7) gw4e_gated_k7(o); else if constexpr (KAPPA == 8) gw4e_gated_k8(o);
-                            else if constexpr (KAPPA == 9) gw4e_gated_k9(o); else if constexpr (KAPPA == 10) gw4e_gated_k10(o); else if constexpr (KAPPA == 11) gw4e_gated_k11(o);
-                            else if constexpr (KAPPA == 12) gw4e_gated_k12(o); else if constexpr (KAPPA == 13) gw4e_gated_k13(o); else if constexpr (KAPPA == 14) gw4e_gated_k14(o);
-                            else gw4e_gated_k15(o);
+                            if constexpr (KAPPA == 0) GW4E_DO(gated_k0, o); else if constexpr (KAPPA == 1) GW4E_DO(gated_k1, o); else if constexpr (KAPPA == 2) { if (u == 0) GW4E_DO(gated_k2f, o); else GW4E_DO(gated_k2, o); }
+                            else if constexpr (KAPPA == 3) GW4E_DO(gated_k3, o); else if constexpr (KAPPA == 4) GW4E_DO(gated_k4, o); else if constexpr (KAPPA == 5) GW4E_DO(gated_k5, o);
+                            else if constexpr (KAPPA == 6) GW4E_DO(gated_k6, o); else if constexpr (KAPPA == 7) GW4E_DO(gated_k7, o); else if constexpr (KAPPA == 8) GW4E_DO(gated_k8, o);
+                            else if constexpr (KAPPA == 9) GW4E_DO(gated_k9, o); else if constexpr (KAPPA == 10) GW4E_DO(gated_k10, o); else if constexpr (KAPPA == 11) GW4E_DO(gated_k11, o);
+                            else if constexpr (KAPPA == 12) GW4E_DO(gated_k12, o); else if constexpr (KAPPA == 13) GW4E_DO(gated_k13, o); else if constexpr (KAPPA == 14) GW4E_DO(gated_k14, o);
+                            else GW4E_DO(gated_k15, o);
                         }
                     };
                     step(K0{});
@@ -299,20 +334,21 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
             }
             // ---- K tile 33: its barrier step stores the last unit's chunk 3; K tile 34 brings the plain loop back to an odd tile index
             {
-                gw4e_ks0(kops(S1{}, K0{}, 33));
-                gw4e_ks1(kops(S1{}, K1{}, 33));
+                GW4E_DO(ks0, kops(S1{}, K0{}, 33));
+                GW4E_DO(ks1, kops(S1{}, K1{}, 33));
                 GW4EOps o = kops(S1{}, K2{}, 33);
                 o.cb = unit_c(7) + 3 * c_chunk;
-                gw4e_ks2_bar_store3(o);
-                gw4e_ks3(kops(S1{}, K3{}, 33));
+                GW4E_DO(ks2_bar_store3, o);
+                GW4E_DO(ks3, kops(S1{}, K3{}, 33));
                 plain_tile(S0{}, 34);
             }
             t = 35;
         } else {
-            gw4e_ks0_init(kops(S0{}, K0{}, 0));
-            gw4e_ks1(kops(S0{}, K1{}, 0));
-            gw4e_ks2_bar(kops(S0{}, K2{}, 0));
-            gw4e_ks3(kops(S0{}, K3{}, 0));
+            GW4E_DO(ks0_init, kops(S0{}, K0{}, 0));
+            if constexpr (N16) gw4e16_ks1_init(kops(S0{}, K1{}, 0));  // (a K = 32 step spans K steps 0 and 1: both start at C = 0; gw4e16_ks1_pre does too)
+            else gw4e_ks1(kops(S0{}, K1{}, 0));
+            GW4E_DO(ks2_bar, kops(S0{}, K2{}, 0));
+            GW4E_DO(ks3, kops(S0{}, K3{}, 0));
             t = 1;
         }
         // ---- the rest of the K loop (t is odd here, nk even): pairs of plain tiles up to K tile nk - 4
@@ -322,43 +358,43 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
         }
         // K tile nk - 3: + the finished-to-be tile's gate vectors into v[56:63] (the previous tile's epilogue is done with them: t >= 33)
         {
-            gw4e_ks0(kops(S1{}, K0{}, t));
-            gw4e_ks1(kops(S1{}, K1{}, t));
-            gw4e_ks2_bar(kops(S1{}, K2{}, t));
+            GW4E_DO(ks0, kops(S1{}, K0{}, t));
+            GW4E_DO(ks1, kops(S1{}, K1{}, t));
+            GW4E_DO(ks2_bar, kops(S1{}, K2{}, t));
             GW4EOps o = kops(S1{}, K3{}, t);
             if constexpr (EPI == EPI_GATED_RESIDUAL) {
                 o.gb0 = reinterpret_cast<const char*>(p.gate) + (int64_t)(n0 + wn * 128) * 2;
                 o.gb1 = o.gb0 + 128;
-                gw4e_ks3_gate(o);
+                GW4E_DO(ks3_gate, o);
             } else {
-                gw4e_ks3(o);
+                GW4E_DO(ks3, o);
             }
             ++t;
         }
         if (has_next) {  // K tiles nk - 2, nk - 1 fetch the next output tile's K tiles 0, 1
             const char* fl = f_tile + (int64_t)(nk - 1) * 128;
             const char* sl = s_tile + (int64_t)(nk - 1) * 128;
-            gw4e_ks0(kops_src(S0{}, K0{}, fl, sl, f_next));
-            gw4e_ks1(kops_src(S0{}, K1{}, fl, sl, f_next));
-            gw4e_ks2_bar(with_prefetch(kops_src(S0{}, K2{}, fl, sl, f_next), nk - 2));
-            gw4e_ks3(kops_src(S0{}, K3{}, fl, sl, f_next));
-            gw4e_ks0(kops_src(S1{}, K0{}, f_next, s_next, f_next + 128));
-            gw4e_ks1(kops_src(S1{}, K1{}, f_next, s_next, f_next + 128));
-            gw4e_ks2_bar(with_prefetch(kops_src(S1{}, K2{}, f_next, s_next, f_next + 128), nk - 1));
-            gw4e_ks3(kops_src(S1{}, K3{}, f_next, s_next, f_next + 128));
+            GW4E_DO(ks0, kops_src(S0{}, K0{}, fl, sl, f_next));
+            GW4E_DO(ks1, kops_src(S0{}, K1{}, fl, sl, f_next));
+            GW4E_DO(ks2_bar, with_prefetch(kops_src(S0{}, K2{}, fl, sl, f_next), nk - 2));
+            GW4E_DO(ks3, kops_src(S0{}, K3{}, fl, sl, f_next));
+            GW4E_DO(ks0, kops_src(S1{}, K0{}, f_next, s_next, f_next + 128));
+            GW4E_DO(ks1, kops_src(S1{}, K1{}, f_next, s_next, f_next + 128));
+            GW4E_DO(ks2_bar, with_prefetch(kops_src(S1{}, K2{}, f_next, s_next, f_next + 128), nk - 1));
+            GW4E_DO(ks3, kops_src(S1{}, K3{}, f_next, s_next, f_next + 128));
         } else {  // the workgroup's last tile: nothing further to fetch
-            gw4e_ks0(kops(S0{}, K0{}, t));
-            gw4e_ks1(kops(S0{}, K1{}, t));
-            gw4e_ks2_bar(kops(S0{}, K2{}, t));
-            gw4e_ks3_nodma(kops(S0{}, K3{}, t));
-            gw4e_ks0_nodma(kops(S1{}, K0{}, t + 1));
-            gw4e_ks1_nodma(kops(S1{}, K1{}, t + 1));
-            gw4e_ks2_nobar(kops(S1{}, K2{}, t + 1));
-            gw4e_ks3_last(kops(S1{}, K3{}, t + 1));
+            GW4E_DO(ks0, kops(S0{}, K0{}, t));
+            GW4E_DO(ks1, kops(S0{}, K1{}, t));
+            GW4E_DO(ks2_bar, kops(S0{}, K2{}, t));
+            GW4E_DO(ks3_nodma, kops(S0{}, K3{}, t));
+            GW4E_DO(ks0_nodma, kops(S1{}, K0{}, t + 1));
+            GW4E_DO(ks1_nodma, kops(S1{}, K1{}, t + 1));
+            GW4E_DO(ks2_nobar, kops(S1{}, K2{}, t + 1));
+            GW4E_DO(ks3_last, kops(S1{}, K3{}, t + 1));
         }
 
         // ---- drain (the only dead time between two K loops): accumulators -> P
-        if (!(G3_AB_GW4E_ABLATE & 8)) gw4e_drain();  // (bit 8: timing ablation)
+        if (!(G3_AB_GW4E_ABLATE & 8)) GW4E_DO(drain);  // (bit 8: timing ablation)
         m0e = m0;
         n0e = n0;
         if (!has_next) {
@@ -416,6 +452,17 @@ __global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmPa
         w_tile = w_next;
         t_tile = t_next;
     }
+}
+
+template <int EPI, bool TF>
+__global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e_kernel(GemmParams p) {
+    gemm_w4e_body<EPI, TF, false>(p);
+}
+// the twin gemm_launch starts from the same table row where p.mfma16 is set (gemm.hip: gemm_w4e16_twins): one function cannot hold both bodies - the
+// compiler then reloads kernel arguments between the K steps, behind the first MFMA, where the hand-counted lgkmcnt waits allow no scalar load
+template <int EPI, bool TF>
+__global__ __launch_bounds__(GW4_THREADS, 1) void gemm_bf16_nt_w4e16_kernel(GemmParams p) {
+    gemm_w4e_body<EPI, TF, true>(p);
 }
 
 // gate_rows in {1, 2, 4}: the gate row of an output row m is m % gate_rows = (8 ch + rr) % gate_rows = rr % gate_rows (tile origins are multiples of 32)

@@ -40,6 +40,7 @@ const char* g3_last_error(void);
 int g3_abi_version(void);
 /* runtime switches for A/B measurements: "gemm_regstage", "gemm_rowmajor_tiles", "gemm_unpinned" (0/1), "gemm_pingpong" (3 = one wave per SIMD, the
  * default), "gemm_deferred" (1 = the persistent block GEMM with the deferred epilogue where it applies, the default; 0 = epilogue behind every K loop),
+ * "gemm_mfma16" (1, the default: that kernel's K loop on v_mfma_f32_16x16x32_bf16; 0: on v_mfma_f32_32x32x16_bf16 - the same bits and the same reported kernel name),
  * "gemm_persistent", "conv_w4" (2 = without the in-gap tap change), "attn_variant" (0 = automatic), "attn_xcd_heads", "splat_tiled", "render_overlap", "render_fused", "render_full_extent"
  * (1, default: the renderer's tiles publish unclamped destination rectangles and the gather pass reads the dense accumulator per texel),
  * "render_exclusive" (1: extent pre-pass + single-writer texels resolved inside the splat - a quarter less memory traffic, 18 % slower; default 0),

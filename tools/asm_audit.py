@@ -189,21 +189,23 @@ def audit_gemm_w4e(asm_text: str):
     drained tile v64..v191 and the gate vectors v56..v63 belong to the generated asm statements (gemm_w4e_gen.hpp) - the finished tile LIVES in
     v64..v191 across compiler-generated code (pointer arithmetic, the unit switch), which therefore may not name any of them anywhere in the kernel;
     no scratch; no scalar memory load behind the first MFMA (the gated-residual statements wait with hand-counted lgkmcnt(N): SMEM returns out of order);
-    every period statement keeps its 16 MFMAs."""
+    every K-step statement keeps its MFMAs: 16 v_mfma_f32_32x32x16_bf16, or 32 v_mfma_f32_16x16x32_bf16 in the twins gemm_bf16_nt_w4e16_kernel
+    (gemm_w4e16_gen.hpp), which are audited like the kernels they stand in for and hold no MFMA of the other shape."""
     findings, cur, funcs = [], None, {}
     for ln in asm_text.split("\n"):
-        m = re.match(r"^(_ZN12_GLOBAL__N_1\d+gemm_bf16_nt_w4e_kernelILi(\d+)ELb([01])EEEvNS_10GemmParamsE):", ln)
+        m = re.match(r"^(_ZN12_GLOBAL__N_1\d+gemm_bf16_nt_w4e(16)?_kernelILi(\d+)ELb([01])EEEvNS_10GemmParamsE):", ln)
         if m:
-            cur = f"gemm_w4e<{m.group(2)}, {'tokens' if m.group(3) == '1' else 'weights'} first>"
+            cur = f"gemm_w4e{m.group(2) or ''}<{m.group(3)}, {'tokens' if m.group(4) == '1' else 'weights'} first>"
             funcs[cur] = []
         elif cur is not None:
             funcs[cur].append(ln)
             if ln.startswith(".Lfunc_end"):
                 cur = None
-    if len(funcs) != 6:
-        findings.append(f"gemm_w4e: expected 6 kernel instances (epilogues 0, 1, 2 x piece order), found {sorted(funcs)}")
+    if len(funcs) != 12:
+        findings.append(f"gemm_w4e: expected 12 kernel instances (epilogues 0, 1, 2 x piece order x MFMA shape), found {sorted(funcs)}")
     for name, v in funcs.items():
         in_asm, seen_mfma, n_mfma_stmt, n_stmt = False, False, 0, 0
+        shape, per_stmt = ("v_mfma_f32_16x16x32_bf16", 32) if name.startswith("gemm_w4e16") else ("v_mfma_f32_32x32x16_bf16", 16)
         for i, l in enumerate(v):
             t = l.strip()
             if "ASMSTART" in t:
@@ -213,8 +215,8 @@ def audit_gemm_w4e(asm_text: str):
                 in_asm = False
                 if n_mfma_stmt:
                     n_stmt += 1
-                    if n_mfma_stmt != 16:
-                        findings.append(f"{name}: line {i}: an asm statement with {n_mfma_stmt} MFMAs (a K step has 16)")
+                    if n_mfma_stmt != per_stmt:
+                        findings.append(f"{name}: line {i}: an asm statement with {n_mfma_stmt} MFMAs (a K step has {per_stmt})")
                 continue
             if not t or t[0] in ";.":
                 continue
@@ -222,6 +224,8 @@ def audit_gemm_w4e(asm_text: str):
                 if t.startswith("v_mfma"):
                     n_mfma_stmt += 1
                     seen_mfma = True
+                    if not t.startswith(shape + " "):
+                        findings.append(f"{name}: line {i}: `{t.split()[0]}` in the body of {shape}")
                 continue
             if t.startswith("scratch_"):
                 findings.append(f"{name}: line {i}: scratch access `{t}`")

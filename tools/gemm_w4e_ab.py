@@ -1,9 +1,10 @@
 """A/B of build-time variants of the deferred-epilogue GEMM (csrc/gemm_w4e.hpp) at the benchmark shapes, interleaved in one process on one box.
 Build HERE before gpurun:  python tools/gemm_w4e_ab.py --build      (copies of the library with -DG3_AB_GW4E_PF=0 / 1, -DG3_GW4E_PFD=8)
 GPU box:                   python tools/gemm_w4e_ab.py
-Shapes: G3_W4E_AB_SHAPES="name:M:N:K:epilogue;..." (default: the four block GEMMs at M = 2 x 56 320).
+Shapes: G3_W4E_AB_SHAPES="name:M:N:K:epilogue;..." (default: the step's five block GEMMs: M = 2 x 56 320 and the operand-swapped V^T launch).
 Variants (G3_W4E_AB_VARIANTS="name=flags;..."): product (no prefetch), pf1 (token slices by every workgroup), pf2 (token + weight slices), pf3 / pf4 (leaders only),
-and the product library with gemm_deferred = 0 (the non-persistent one-wave kernel)."""
+the product library with gemm_deferred = 0 (the non-persistent one-wave kernel), and the product with gemm_mfma16 = 0 / 1 (the deferred kernel's K loop on
+32x32x16 / 16x16x32 MFMAs: "product" is the option's default, the two arms name the value)."""
 import ctypes as C
 import os
 import sys
@@ -21,10 +22,12 @@ if "--build" in sys.argv:
     sys.exit(0)
 
 import torch  # noqa: E402
-from gen3c_amd import _lib  # noqa: E402
+from gen3c_amd import _lib, ops  # noqa: E402
 from tools.microbench import timeit  # noqa: E402
 
-libs = [("plain-w4", _lib.load(), 0, 0), ("product", _lib.load(), 1, 0), ("tokens-first", _lib.load(), 1, 1)]  # (label, library, gemm_deferred, gemm_tokens_first)
+MFMA16_DEFAULT = ops.option("gemm_mfma16")
+libs = [("plain-w4", _lib.load(), 0, 0, None), ("product", _lib.load(), 1, 0, None), ("tokens-first", _lib.load(), 1, 1, None),  # (label, library, gemm_deferred, gemm_tokens_first, gemm_mfma16)
+        ("mfma16=0", _lib.load(), 1, 2, 0), ("mfma16=1", _lib.load(), 1, 2, 1)]  # (piece order by shape, as the step launches them)
 for suffix, _ in VARIANTS:
     f = ROOT / "gen3c_amd" / "lib" / f"libgen3c_hip_{suffix}.so"
     if not f.exists():
@@ -32,11 +35,11 @@ for suffix, _ in VARIANTS:
     lib = C.CDLL(str(f))
     for name, argtypes in _lib.SIGNATURES.items():
         getattr(lib, name).argtypes = argtypes
-    libs.append((suffix, lib, 1, 0))
+    libs.append((suffix, lib, 1, 0, None))
 dev = torch.device("cuda:0")
 st = torch.cuda.current_stream().cuda_stream
 B = 2  # the benchmark's launches carry both CFG branches: M = 2 x 56 320
-SHAPES = [("qkv", 56320 * B, 12288, 4096, 0), ("out", 56320 * B, 4096, 4096, 2), ("w1", 56320 * B, 16384, 4096, 1), ("w2", 56320 * B, 4096, 16384, 2)]
+SHAPES = [("qk", 56320 * B, 8192, 4096, 0), ("vt", 4096, 56320, 4096, 0), ("out", 56320 * B, 4096, 4096, 2), ("w1", 56320 * B, 16384, 4096, 1), ("w2", 56320 * B, 4096, 16384, 2)]
 if os.environ.get("G3_W4E_AB_SHAPES"):  # "name:M:N:K:epilogue;..." (e.g. the per-rank shapes of cp = 8: M = 14 080)
     SHAPES = [(t.split(":")[0], *[int(x) for x in t.split(":")[1:]]) for t in os.environ["G3_W4E_AB_SHAPES"].split(";") if t]
 for (nm, M, N, K, epi) in SHAPES:
@@ -48,10 +51,11 @@ for (nm, M, N, K, epi) in SHAPES:
     fl = 2.0 * M * N * K
     for rnd in range(3):
         line = []
-        for (label, lib, deferred, tf) in libs:
+        for (label, lib, deferred, tf, m16) in libs:
             lib.g3_set_option(b"gemm_pingpong", 3)
             lib.g3_set_option(b"gemm_deferred", deferred)
             lib.g3_set_option(b"gemm_tokens_first", tf)
+            lib.g3_set_option(b"gemm_mfma16", MFMA16_DEFAULT if m16 is None else m16)
             out = outs.setdefault(label, torch.empty(M, N, device=dev, dtype=torch.bfloat16))
             def run():
                 rc = lib.g3_gemm_bf16_nt(a.data_ptr(), K, w.data_ptr(), K, out.data_ptr(), N, M, N, K, epi, gate.data_ptr() if epi == 2 else None, B, N,
@@ -66,3 +70,4 @@ for (nm, M, N, K, epi) in SHAPES:
     del a, w, gate, res, outs
 _lib.load().g3_set_option(b"gemm_deferred", 1)
 _lib.load().g3_set_option(b"gemm_tokens_first", 0)
+_lib.load().g3_set_option(b"gemm_mfma16", MFMA16_DEFAULT)

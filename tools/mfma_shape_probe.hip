@@ -15,8 +15,10 @@
 //            front of V^T group 10, no piece in region B;
 //        (K) K one tile ahead: the four K pieces on four bare V^T groups behind the barrier (10..13 or 12..15), the four V^T pieces beside the pair
 //            units of K groups 8, 10, 12, 14.
-// build: hipcc --offload-arch=gfx950 -O3 tools/mfma_shape_probe.hip -o tools/bin/mfma_shape_probe ; run on the GPU box, record the output
-// in profiles/mfma_shape_probe.txt.
+//   c. WALL at the K tile of the deferred block GEMM under its GELU epilogue (gen3c_amd/csrc/gemm_w4e.hpp), both shapes: see the section's head.
+//      Decided whether that kernel's K loop moved to 16x16x32 (profiles/gemm_mfma16_ab.txt).
+// build: hipcc --offload-arch=gfx950 -O3 tools/mfma_shape_probe.hip -o tools/bin/mfma_shape_probe ; run on the GPU box
+// (mfma_shape_probe [tiles] [all | attn | gemm]), record the output in profiles/mfma_shape_probe.txt.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -377,6 +379,342 @@ __global__ __launch_bounds__(256, 1) void tile_kernel(const char* __restrict__ s
     if (sink == -1.2345f) stamps[0].c0 = 0;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------ c. GEMM wall
+// The K tile of gemm_bf16_nt_w4e_kernel (gen3c_amd/csrc/gemm_w4e.hpp) while it carries the GELU epilogue, in both MFMA shapes. Per wave: a 128 x 128
+// output in a[0:255], fragments in v[192:255], and per K tile of 64: 64 v_mfma_f32_32x32x16_bf16 or 128 v_mfma_f32_16x16x32_bf16, 32 ds_read_b128 from
+// the product's LDS image (128-byte rows, 16-byte chunk ^ (row >> 1 & 7)), 16 LDS-DMA pieces with their s_mov m0 from two 2 MiB panels that stay in
+// the L2, one vmcnt + barrier, and four GELU pair units of 33 VALU (the arithmetic of gw4e_gelu_k*). Values are NOT meaningful, as in b.
+//   arm 32: the product's four K steps: gaps of gw4e_gelu_k0 / k1 (5 pieces), k2 (barrier), k3 (6 pieces); at most 5 ops in a gap.
+//   arm 16: two K = 32 steps of four quadrants (4 x 4 blocks of 16 x 16) each. The 64 fragment registers hold exactly one step: the quadrants run
+//           00 01 11 10 | 01 00 10 11, and each quadrant's four reads land in the four fragments whose last reader was the quadrant before it.
+//           A pair unit spans two quadrants (17 + 16 VALU); pieces 3 2 3 2 | 0 0 (barrier) 3 3; at most 2 ops in a gap.
+constexpr int G_STAGE = 65536, G_T_OFF = 32768, G_LDS = 2 * G_STAGE + 32768;  // the product's 160 KiB (its X / Y slices are not used here)
+constexpr int G_LD = 8192;          // row stride of the source panels in bytes (K = 4096)
+constexpr int G_PANEL = 256 * G_LD;  // 2 MiB: 256 rows x 64 K tiles of 128 bytes; the weight panel, then the token panel
+
+#define G_OWNED_V                                                                                                                                                            \
+    "v192", "v193", "v194", "v195", "v196", "v197", "v198", "v199", "v200", "v201", "v202", "v203", "v204", "v205", "v206", "v207", "v208", "v209", "v210", "v211", "v212", \
+        "v213", "v214", "v215", "v216", "v217", "v218", "v219", "v220", "v221", "v222", "v223", "v224", "v225", "v226", "v227", "v228", "v229", "v230", "v231", "v232",      \
+        "v233", "v234", "v235", "v236", "v237", "v238", "v239", "v240", "v241", "v242", "v243", "v244", "v245", "v246", "v247", "v248", "v249", "v250", "v251", "v252",      \
+        "v253", "v254", "v255"
+#define G_OWNED OWNED_AGPRS, G_OWNED_V
+
+// one GELU pair unit: two bf16 of %[src] -> x (1 - 0.5 erfc-polynomial), packed into %[dst]: the 33 instructions of the product's unit
+#define GE0 "v_lshlrev_b32 %[x0], 16, %[src]\n\t"
+#define GE1 "v_and_b32 %[x1], 0xffff0000, %[src]\n\t"
+#define GE2 "v_fma_f32 %[t0], |%[x0]|, %[c0], 1.0\n\t"
+#define GE3 "v_fma_f32 %[t1], |%[x1]|, %[c0], 1.0\n\t"
+#define GE4 "v_rcp_f32 %[t0], %[t0]\n\t"
+#define GE5 "v_rcp_f32 %[t1], %[t1]\n\t"
+#define GE6 "v_mov_b32 %[p0], 0x3f07dc22\n\t"
+#define GE7 "v_mov_b32 %[p1], 0x3f07dc22\n\t"
+#define GE8 "v_fmaak_f32 %[p0], %[p0], %[t0], 0xbf3a00e3\n\t"
+#define GE9 "v_fmaak_f32 %[p1], %[p1], %[t1], 0xbf3a00e3\n\t"
+#define GE10 "v_fmaak_f32 %[p0], %[p0], %[t0], 0x3f35f0e3\n\t"
+#define GE11 "v_fmaak_f32 %[p1], %[p1], %[t1], 0x3f35f0e3\n\t"
+#define GE12 "v_fmaak_f32 %[p0], %[p0], %[t0], 0xbe11a98e\n\t"
+#define GE13 "v_fmaak_f32 %[p1], %[p1], %[t1], 0xbe11a98e\n\t"
+#define GE14 "v_fmaak_f32 %[p0], %[p0], %[t0], 0x3e027906\n\t"
+#define GE15 "v_fmaak_f32 %[p1], %[p1], %[t1], 0x3e027906\n\t"
+#define GE16 "v_mul_f32 %[e0], %[x0], %[x0]\n\t"
+#define GE17 "v_mul_f32 %[e1], %[x1], %[x1]\n\t"
+#define GE18 "v_mul_f32 %[e0], 0xbf38aa3b, %[e0]\n\t"
+#define GE19 "v_mul_f32 %[e1], 0xbf38aa3b, %[e1]\n\t"
+#define GE20 "v_exp_f32 %[e0], %[e0]\n\t"
+#define GE21 "v_exp_f32 %[e1], %[e1]\n\t"
+#define GE22 "v_mul_f32 %[p0], %[p0], %[t0]\n\t"
+#define GE23 "v_mul_f32 %[p1], %[p1], %[t1]\n\t"
+#define GE24 "v_mul_f32 %[p0], %[p0], %[e0]\n\t"
+#define GE25 "v_mul_f32 %[p1], %[p1], %[e1]\n\t"
+#define GE26 "v_mul_f32_e64 %[p0], %[p0], |%[x0]|\n\t"
+#define GE27 "v_mul_f32_e64 %[p1], %[p1], |%[x1]|\n\t"
+#define GE28 "v_max_f32_e64 %[x0], %[x0], 0\n\t"
+#define GE29 "v_max_f32_e64 %[x1], %[x1], 0\n\t"
+#define GE30 "v_sub_f32 %[x0], %[x0], %[p0]\n\t"
+#define GE31 "v_sub_f32 %[x1], %[x1], %[p1]\n\t"
+#define GE32 "v_cvt_pk_bf16_f32 %[dst], %[x0], %[x1]\n\t"
+
+struct Gelu {  // registers of the pair unit in flight
+    uint32_t x0, x1, t0, t1, p0, p1, e0, e1, dst;
+};
+struct GPieces {  // up to six LDS-DMA pieces of a statement: LDS destination, per-lane source offset; one wave-uniform source base
+    uint32_t m[6], vo[6];
+    const char* sb;
+};
+#define G_GELU_OUT(u) [x0] "+v"(u.x0), [x1] "+v"(u.x1), [t0] "+v"(u.t0), [t1] "+v"(u.t1), [p0] "+v"(u.p0), [p1] "+v"(u.p1), [e0] "+v"(u.e0), [e1] "+v"(u.e1), [dst] "+v"(u.dst)
+#define G_PIECES_IN(P)                                                                                                                                                   \
+    [m0] "s"(P.m[0]), [m1] "s"(P.m[1]), [m2] "s"(P.m[2]), [m3] "s"(P.m[3]), [m4] "s"(P.m[4]), [m5] "s"(P.m[5]), [vo0] "v"(P.vo[0]), [vo1] "v"(P.vo[1]), [vo2] "v"(P.vo[2]), \
+        [vo3] "v"(P.vo[3]), [vo4] "v"(P.vo[4]), [vo5] "v"(P.vo[5]), [sb] "s"(P.sb)
+#define G_M0(n) "s_mov_b32 m0, %[m" #n "]\n\t"
+#define G_DMA(n) "global_load_lds_dwordx4 %[vo" #n "], %[sb]\n\t"
+#define G_NONE ""
+#define G_LGKM0 "s_waitcnt lgkmcnt(0)\n\t"
+#define G_BAR "s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier\n\t"
+
+// ---- arm 32: acc a[lo:lo+15] = block (i, j) of 32 features x 32 tokens; fragments at %c[fw] + 4 i (weights), %c[ft] + 4 j (tokens); the next
+// step's eight fragments go to %c[rt] (tokens first, as the product) and %c[rw]
+#define G32_M(lo, wo, to)                                                                                                                                          \
+    "v_mfma_f32_32x32x16_bf16 a[" #lo ":" #lo "+15], v[%c[fw]+" #wo ":%c[fw]+" #wo "+3], v[%c[ft]+" #to ":%c[ft]+" #to "+3], a[" #lo ":" #lo "+15]\n\t"
+#define G32_RT(k, off) "ds_read_b128 v[%c[rt]+" #k ":%c[rt]+" #k "+3], %[adt] offset:" #off "\n\t"
+#define G32_RW(k, off) "ds_read_b128 v[%c[rw]+" #k ":%c[rw]+" #k "+3], %[adw] offset:" #off "\n\t"
+// KIND 0: K steps 0 / 1 (five pieces), 1: K step 2 (no piece, vmcnt + barrier), 2: K step 3 (six pieces)
+template <int KS>
+__device__ __forceinline__ void g32_step(uint32_t adw, uint32_t adt, Gelu& u, uint32_t src, float c0, const GPieces& P) {
+    constexpr int fw = (KS & 1) ? 224 : 192, ft = (KS & 1) ? 240 : 208, rw = (KS & 1) ? 192 : 224, rt = (KS & 1) ? 208 : 240;
+#define G32_IN [adw] "v"(adw), [adt] "v"(adt), [src] "v"(src), [c0] "s"(c0), [fw] "n"(fw), [ft] "n"(ft), [rw] "n"(rw), [rt] "n"(rt), G_PIECES_IN(P)
+    if constexpr (KS < 2)
+        asm volatile(G_LGKM0
+                     G32_M(0, 0, 0) G32_RT(0, 32768) G_M0(0) GE0 GE1
+                     G32_M(16, 4, 0) G32_RT(4, 36864) G_DMA(0) GE2 GE3
+                     G32_M(32, 8, 0) G32_RT(8, 40960) GE4 GE5 GE6
+                     G32_M(48, 12, 0) G32_RT(12, 45056) G_M0(1) GE7 GE8
+                     G32_M(64, 0, 4) G32_RW(0, 0) G_DMA(1) GE9 GE10
+                     G32_M(80, 4, 4) G32_RW(4, 4096) GE11 GE12 GE13
+                     G32_M(96, 8, 4) G32_RW(8, 8192) G_M0(2) GE14 GE15
+                     G32_M(112, 12, 4) G32_RW(12, 12288) G_DMA(2) GE16 GE17
+                     G32_M(128, 0, 8) GE18 GE19 GE20 GE21
+                     G32_M(144, 4, 8) G_M0(3) GE22 GE23 GE24
+                     G32_M(160, 8, 8) G_DMA(3) GE25 GE26 GE27
+                     G32_M(176, 12, 8) GE28 GE29 GE30 GE31
+                     G32_M(192, 0, 12) G_M0(4) GE32
+                     G32_M(208, 4, 12) G_DMA(4)
+                     G32_M(224, 8, 12)
+                     G32_M(240, 12, 12)
+                     : G_GELU_OUT(u) : G32_IN : G_OWNED, "memory");
+    else if constexpr (KS == 2)
+        asm volatile(G_LGKM0
+                     G32_M(0, 0, 0) G32_RT(0, 32768) GE0 GE1
+                     G32_M(16, 4, 0) G32_RT(4, 36864) GE2 GE3
+                     G32_M(32, 8, 0) G32_RT(8, 40960) GE4 GE5
+                     G32_M(48, 12, 0) G32_RT(12, 45056) GE6 GE7
+                     G32_M(64, 0, 4) G32_RW(0, 0) GE8 GE9
+                     G32_M(80, 4, 4) G32_RW(4, 4096) GE10 GE11
+                     G32_M(96, 8, 4) G32_RW(8, 8192) GE12 GE13
+                     G32_M(112, 12, 4) G32_RW(12, 12288) GE14 GE15
+                     G32_M(128, 0, 8) GE16 GE17 GE18
+                     G32_M(144, 4, 8) GE19 GE20 GE21
+                     G32_M(160, 8, 8) GE22 GE23 GE24
+                     G32_M(176, 12, 8) GE25 GE26 GE27
+                     G32_M(192, 0, 12) GE28 GE29 GE30
+                     G32_M(208, 4, 12) GE31 GE32
+                     G32_M(224, 8, 12)
+                     G32_M(240, 12, 12)
+                     G_BAR
+                     : G_GELU_OUT(u) : G32_IN : G_OWNED, "memory");
+    else
+        asm volatile(G_LGKM0
+                     G32_M(0, 0, 0) G32_RT(0, 32768) G_M0(0) GE0 GE1
+                     G32_M(16, 4, 0) G32_RT(4, 36864) G_DMA(0) GE2 GE3
+                     G32_M(32, 8, 0) G32_RT(8, 40960) GE4 GE5 GE6
+                     G32_M(48, 12, 0) G32_RT(12, 45056) G_M0(1) GE7 GE8
+                     G32_M(64, 0, 4) G32_RW(0, 0) G_DMA(1) GE9 GE10
+                     G32_M(80, 4, 4) G32_RW(4, 4096) G_M0(2) GE11 GE12
+                     G32_M(96, 8, 4) G32_RW(8, 8192) G_DMA(2) GE13 GE14
+                     G32_M(112, 12, 4) G32_RW(12, 12288) GE15 GE16 GE17
+                     G32_M(128, 0, 8) G_M0(3) GE18 GE19 GE20
+                     G32_M(144, 4, 8) G_DMA(3) GE21 GE22 GE23
+                     G32_M(160, 8, 8) GE24 GE25 GE26
+                     G32_M(176, 12, 8) G_M0(4) GE27 GE28 GE29
+                     G32_M(192, 0, 12) G_DMA(4) GE30 GE31 GE32
+                     G32_M(208, 4, 12) G_M0(5)
+                     G32_M(224, 8, 12) G_DMA(5)
+                     G32_M(240, 12, 12)
+                     : G_GELU_OUT(u) : G32_IN : G_OWNED, "memory");
+#undef G32_IN
+}
+
+// ---- arm 16: a quadrant of 4 x 4 blocks; block (i, j) of 16 features x 16 tokens is a[%c[ab] + 32 i + 4 j : +3] (the wave's 8 x 8 blocks, four
+// AGPRs each, block (I, J) at 4 (8 I + J)); its weight fragments at %c[fw] + 4 i, token fragments at %c[ft] + 4 j; four reads into %c[rd]
+#define G16_M(d, wo, to)                                                                                                                                      \
+    "v_mfma_f32_16x16x32_bf16 a[%c[ab]+" #d ":%c[ab]+" #d "+3], v[%c[fw]+" #wo ":%c[fw]+" #wo "+3], v[%c[ft]+" #to ":%c[ft]+" #to "+3], a[%c[ab]+" #d \
+    ":%c[ab]+" #d "+3]\n\t"
+#define G16_RD(k, n) "ds_read_b128 v[%c[rd]+" #k ":%c[rd]+" #k "+3], %[ad] offset:%c[ro" #n "]\n\t"
+// the unit's first 17 instructions over the gaps of an even quadrant, its last 16 over those of an odd one
+#define GEV0 GE0
+#define GEV1 GE1
+#define GEV2 GE2
+#define GEV3 GE3
+#define GEV4 GE4
+#define GEV5 GE5
+#define GEV6 GE6 GE7
+#define GEV7 GE8
+#define GEV8 GE9
+#define GEV9 GE10 GE11
+#define GEV10 GE12
+#define GEV11 GE13
+#define GEV12 GE14 GE15
+#define GEV13 GE16
+#define GOD0 GE17
+#define GOD1 GE18
+#define GOD2 GE19
+#define GOD3 GE20
+#define GOD4 GE21
+#define GOD5 GE22
+#define GOD6 GE23 GE24
+#define GOD7 GE25
+#define GOD8 GE26
+#define GOD9 GE27 GE28
+#define GOD10 GE29
+#define GOD11 GE30
+#define GOD12 GE31 GE32
+#define GOD13
+#define G16_BODY(H, MA, DA, MB, DB, MC, DC)                                                                                                                   \
+    G_LGKM0                                                                                                                                                   \
+    G16_M(0, 0, 0) G16_RD(0, 0) H##0                                                                                                                          \
+    G16_M(4, 0, 4) G16_RD(4, 1) H##1                                                                                                                          \
+    G16_M(8, 0, 8) G16_RD(8, 2) H##2                                                                                                                          \
+    G16_M(12, 0, 12) G16_RD(12, 3) H##3                                                                                                                       \
+    G16_M(32, 4, 0) MA H##4                                                                                                                                   \
+    G16_M(36, 4, 4) DA H##5                                                                                                                                   \
+    G16_M(40, 4, 8) H##6                                                                                                                                      \
+    G16_M(44, 4, 12) MB H##7                                                                                                                                  \
+    G16_M(64, 8, 0) DB H##8                                                                                                                                   \
+    G16_M(68, 8, 4) H##9                                                                                                                                      \
+    G16_M(72, 8, 8) MC H##10                                                                                                                                  \
+    G16_M(76, 8, 12) DC H##11                                                                                                                                 \
+    G16_M(96, 12, 0) H##12                                                                                                                                    \
+    G16_M(100, 12, 4) H##13                                                                                                                                   \
+    G16_M(104, 12, 8)                                                                                                                                         \
+    G16_M(108, 12, 12)
+// Q: the quadrant's place in the K tile, 0..7. Quadrants (feature half, token half) and what each reads (fragment group, K half of which stage):
+//   0: (0,0) T4-7 k0   1: (0,1) W4-7 k0   2: (1,1) W0-3 k1   3: (1,0) T4-7 k1   4: (0,1) T0-3 k1   5: (0,0) W4-7 k1   6: (1,0) W0-3 next k0   7: (1,1) T0-3 next k0
+template <int Q>
+__device__ __forceinline__ void g16_quadrant(uint32_t ad, Gelu& u, uint32_t src, float c0, const GPieces& P) {
+    constexpr int fh = (Q == 2 || Q == 3 || Q == 6 || Q == 7) ? 1 : 0, th = (Q == 1 || Q == 2 || Q == 4 || Q == 7) ? 1 : 0;
+    constexpr int ab = 128 * fh + 16 * th, fw = 192 + 16 * fh, ft = 224 + 16 * th;
+    constexpr int rd = (Q == 0 || Q == 3) ? 240 : (Q == 1 || Q == 5) ? 208 : (Q == 2 || Q == 6) ? 192 : 224;  // T4-7, W4-7, W0-3, T0-3
+    constexpr int ro = (rd >= 224 ? G_T_OFF : 0) + ((rd & 16) ? 4 * 2048 : 0);                                 // fragment f of an operand at 2048 f
+    static_assert(rd != fw && rd != ft, "a quadrant never reads into the fragments it multiplies");
+#define G16_IN                                                                                                                                                     \
+    [ad] "v"(ad), [src] "v"(src), [c0] "s"(c0), [ab] "n"(ab), [fw] "n"(fw), [ft] "n"(ft), [rd] "n"(rd), [ro0] "n"(ro), [ro1] "n"(ro + 2048), [ro2] "n"(ro + 4096), \
+        [ro3] "n"(ro + 6144), G_PIECES_IN(P)
+    if constexpr (Q == 0 || Q == 2 || Q == 6)  // even, three pieces
+        asm volatile(G16_BODY(GEV, G_M0(0), G_DMA(0), G_M0(1), G_DMA(1), G_M0(2), G_DMA(2)) : G_GELU_OUT(u) : G16_IN : G_OWNED, "memory");
+    else if constexpr (Q == 1 || Q == 3)  // odd, two pieces
+        asm volatile(G16_BODY(GOD, G_M0(0), G_DMA(0), G_M0(1), G_DMA(1), G_NONE, G_NONE) : G_GELU_OUT(u) : G16_IN : G_OWNED, "memory");
+    else if constexpr (Q == 4)  // even, no piece
+        asm volatile(G16_BODY(GEV, G_NONE, G_NONE, G_NONE, G_NONE, G_NONE, G_NONE) : G_GELU_OUT(u) : G16_IN : G_OWNED, "memory");
+    else if constexpr (Q == 5)  // odd, no piece, the tile's barrier behind it
+        asm volatile(G16_BODY(GOD, G_NONE, G_NONE, G_NONE, G_NONE, G_NONE, G_NONE) G_BAR : G_GELU_OUT(u) : G16_IN : G_OWNED, "memory");
+    else  // Q == 7: odd, three pieces
+        asm volatile(G16_BODY(GOD, G_M0(0), G_DMA(0), G_M0(1), G_DMA(1), G_M0(2), G_DMA(2)) : G_GELU_OUT(u) : G16_IN : G_OWNED, "memory");
+#undef G16_IN
+}
+
+template <int SHAPE>
+__global__ __launch_bounds__(256, 1) void gemm_tile_kernel(const char* __restrict__ src, const uint32_t* __restrict__ xsrc, int tiles, Stamps* __restrict__ stamps) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave & 1, wm = wave >> 1;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    static_for<0, 256>([&](auto rc) { acc_write<decltype(rc)::value>(0u); });
+    // LDS-DMA: the product's per-lane source offsets (row wave * 64 + 8 q + lane / 8 of the panel, chunk (lane & 7) ^ (row >> 1 & 7)); piece p = 0..7 weights, 8..15 tokens
+    uint32_t vo[16];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+        const int r = wave * 64 + 8 * q + (lane >> 3);
+        const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+        vo[q] = (uint32_t)(r * G_LD + chunk * 16);
+        vo[8 + q] = vo[q] + (uint32_t)G_PANEL;
+    }
+#pragma unroll
+    for (int p = 0; p < 16; ++p) asm volatile("" : "+v"(vo[p]));
+    auto piece_dst = [&](int p, int stage) -> uint32_t { return lds0 + (uint32_t)(stage * G_STAGE + (p >> 3) * G_T_OFF + (p & 7) * 1024) + (uint32_t)wave * 8192u; };
+    // both stages complete (K tiles 0 and 1 of the panels), published by a barrier
+#pragma unroll
+    for (int st = 0; st < 2; ++st)
+#pragma unroll
+        for (int p = 0; p < 16; ++p)
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + st * 128 + vo[p]),
+                                             (__attribute__((address_space(3))) void*)(smem + st * G_STAGE + (p >> 3) * G_T_OFF + (p & 7) * 1024 + wave * 8192), 16, 0, 0);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // the pair units' inputs: four registers of random bf16 pairs (the packed accumulators of a finished tile)
+    uint32_t xin[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        xin[i] = xsrc[i * 256 + tid];
+        asm volatile("" : "+v"(xin[i]));
+    }
+    Gelu u{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    const float c0 = 0.3275911f * 0.70710678118654752440f;
+    // fragment read addresses. arm 32 (the product's): row lane & 31, chunk (lane >> 5) ^ (row >> 1 & 7), ^ 32 bytes per K step; arm 16: row lane & 15, chunk
+    // (lane >> 4) ^ (row >> 1 & 7), ^ 64 bytes for the second K half. Token fragments at + G_T_OFF by the instruction's offset.
+    uint32_t adw[2][4], adt[2][4];
+    if constexpr (SHAPE == 32) {
+        const int l31 = lane & 31, g = lane >> 5;
+        const uint32_t ch = (uint32_t)((g ^ ((l31 >> 1) & 7)) << 4);
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) {
+                adw[st][ks] = ((lds0 + (uint32_t)((wn * 128 + l31) * 128) + ch) ^ (uint32_t)(ks << 5)) + (uint32_t)(st * G_STAGE);
+                adt[st][ks] = ((lds0 + (uint32_t)((wm * 128 + l31) * 128) + ch) ^ (uint32_t)(ks << 5)) + (uint32_t)(st * G_STAGE);
+            }
+        asm volatile("ds_read_b128 v[192:195], %0\n\tds_read_b128 v[196:199], %0 offset:4096\n\tds_read_b128 v[200:203], %0 offset:8192\n\t"
+                     "ds_read_b128 v[204:207], %0 offset:12288\n\tds_read_b128 v[208:211], %1 offset:32768\n\tds_read_b128 v[212:215], %1 offset:36864\n\t"
+                     "ds_read_b128 v[216:219], %1 offset:40960\n\tds_read_b128 v[220:223], %1 offset:45056" ::"v"(adw[0][0]), "v"(adt[0][0]) : G_OWNED, "memory");
+    } else {
+        const int l15 = lane & 15, c = lane >> 4;
+        const uint32_t ch = (uint32_t)((c ^ ((l15 >> 1) & 7)) << 4);
+#pragma unroll
+        for (int st = 0; st < 2; ++st)
+#pragma unroll
+            for (int kh = 0; kh < 2; ++kh) {
+                adw[st][kh] = ((lds0 + (uint32_t)((wn * 128 + l15) * 128) + ch) ^ (uint32_t)(kh << 6)) + (uint32_t)(st * G_STAGE);
+                adt[st][kh] = ((lds0 + (uint32_t)((wm * 128 + l15) * 128) + ch) ^ (uint32_t)(kh << 6)) + (uint32_t)(st * G_STAGE);
+            }
+        // W0-3 and T0-3 of K tile 0's first half
+        asm volatile("ds_read_b128 v[192:195], %0\n\tds_read_b128 v[196:199], %0 offset:2048\n\tds_read_b128 v[200:203], %0 offset:4096\n\t"
+                     "ds_read_b128 v[204:207], %0 offset:6144\n\tds_read_b128 v[224:227], %1 offset:32768\n\tds_read_b128 v[228:231], %1 offset:34816\n\t"
+                     "ds_read_b128 v[232:235], %1 offset:36864\n\tds_read_b128 v[236:239], %1 offset:38912" ::"v"(adw[0][0]), "v"(adt[0][0]) : G_OWNED, "memory");
+    }
+
+    auto tile = [&](int t, auto par_c) {
+        constexpr int S = decltype(par_c)::value;
+        // the tile's 16 pieces: 0..9 fetch K tile t + 1 into the other stage, 10..15 K tile t + 2 into this one (free behind the barrier), as the product's
+        const char* sb1 = src + (size_t)((t + 1) & 63) * 128;
+        const char* sb2 = src + (size_t)((t + 2) & 63) * 128;
+        auto pieces = [&](int first, int n) -> GPieces {
+            GPieces P{};
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                const int p = (first + (i < n ? i : 0)) & 15;
+                P.m[i] = piece_dst(p, first < 10 ? (S ^ 1) : S);
+                P.vo[i] = vo[p];
+            }
+            P.sb = first < 10 ? sb1 : sb2;
+            return P;
+        };
+        if constexpr (SHAPE == 32) {
+            g32_step<0>(adw[S][1], adt[S][1], u, xin[0], c0, pieces(0, 5));
+            g32_step<1>(adw[S][2], adt[S][2], u, xin[1], c0, pieces(5, 5));
+            g32_step<2>(adw[S][3], adt[S][3], u, xin[2], c0, pieces(0, 0));
+            g32_step<3>(adw[S ^ 1][0], adt[S ^ 1][0], u, xin[3], c0, pieces(10, 6));
+        } else {
+            g16_quadrant<0>(adt[S][0], u, xin[0], c0, pieces(0, 3));
+            g16_quadrant<1>(adw[S][0], u, xin[0], c0, pieces(3, 2));
+            g16_quadrant<2>(adw[S][1], u, xin[1], c0, pieces(5, 3));
+            g16_quadrant<3>(adt[S][1], u, xin[1], c0, pieces(8, 2));
+            g16_quadrant<4>(adt[S][1], u, xin[2], c0, pieces(0, 0));
+            g16_quadrant<5>(adw[S][1], u, xin[2], c0, pieces(0, 0));
+            g16_quadrant<6>(adw[S ^ 1][0], u, xin[3], c0, pieces(10, 3));
+            g16_quadrant<7>(adt[S ^ 1][0], u, xin[3], c0, pieces(13, 3));
+        }
+    };
+
+    const unsigned long long c0s = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
+    for (int t = 0; t < tiles; t += 2) {
+        tile(t, std::integral_constant<int, 0>{});
+        tile(t + 1, std::integral_constant<int, 1>{});
+    }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" ::: "memory", G_OWNED);
+    const unsigned long long c1s = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
+    if (lane == 0) stamps[blockIdx.x * 4 + wave] = Stamps{c0s, c1s, r0, r1};
+    if (u.dst == 0x12345678u && u.x0 == 0x9abcdef0u) stamps[0].c0 = 0;  // keep the unit's results alive
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------ host
 static uint16_t f32_to_bf16(float f) {
     uint32_t u;
@@ -552,14 +890,89 @@ static void run_wall(int tiles) {
     verdict(1, med[3] < med[4] ? 3 : 4, "V^T ahead as well (third V^T stage)");
 }
 
+static void run_wall_gemm(int tiles) {
+    const int WGS = 256;
+    std::vector<uint16_t> hsrc((size_t)G_PANEL);  // two panels of 2 MiB: G_PANEL bf16
+    std::vector<uint16_t> hx(4 * 256 * 2);
+    for (size_t i = 0; i < hsrc.size(); ++i) hsrc[i] = f32_to_bf16(randn() * (i < hsrc.size() / 2 ? 0.02f : 1.f));  // weights 0.02 N(0, 1), tokens N(0, 1)
+    for (auto& v : hx) v = f32_to_bf16(randn());
+    char* dsrc;
+    uint32_t* dx;
+    CHECK(hipMalloc(&dsrc, 2 * (size_t)G_PANEL));
+    CHECK(hipMalloc(&dx, hx.size() * 2));
+    CHECK(hipMemcpy(dsrc, hsrc.data(), 2 * (size_t)G_PANEL, hipMemcpyHostToDevice));
+    CHECK(hipMemcpy(dx, hx.data(), hx.size() * 2, hipMemcpyHostToDevice));
+    const int ROUNDS = 3, ARMS = 2;
+    const char* names[ARMS] = {"32x32x16", "16x16x32"};
+    Stamps* dst[ARMS][ROUNDS];
+    Stamps* dwarm;
+    CHECK(hipMalloc(&dwarm, 1024 * sizeof(Stamps)));
+    for (int a = 0; a < ARMS; ++a)
+        for (int r = 0; r < ROUNDS; ++r) CHECK(hipMalloc(&dst[a][r], 1024 * sizeof(Stamps)));
+    using Kernel = void (*)(const char*, const uint32_t*, int, Stamps*);
+    Kernel kernels[ARMS] = {gemm_tile_kernel<32>, gemm_tile_kernel<16>};
+    for (int a = 0; a < ARMS; ++a) CHECK(hipFuncSetAttribute((const void*)kernels[a], hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS));
+    auto launch = [&](int arm, Stamps* st) { hipLaunchKernelGGL(kernels[arm], dim3(WGS), dim3(256), G_LDS, 0, dsrc, dx, tiles, st); };
+    hipEvent_t e0, e1, ev[ARMS][ROUNDS][2];
+    CHECK(hipEventCreate(&e0));
+    CHECK(hipEventCreate(&e1));
+    for (int a = 0; a < ARMS; ++a)
+        for (int r = 0; r < ROUNDS; ++r) {
+            CHECK(hipEventCreate(&ev[a][r][0]));
+            CHECK(hipEventCreate(&ev[a][r][1]));
+        }
+    float ms1[ARMS], ms_all = 0.f;
+    for (int a = 0; a < ARMS; ++a) {
+        CHECK(hipEventRecord(e0, 0));
+        launch(a, dwarm);
+        CHECK(hipEventRecord(e1, 0));
+        CHECK(hipEventSynchronize(e1));
+        CHECK(hipEventElapsedTime(&ms1[a], e0, e1));
+        ms_all += ms1[a];
+    }
+    const int warm = (int)(2200.f / ms_all) + 1;  // >= 2 s of back-to-back launches, then the timed launches in the same queue without a gap
+    for (int i = 0; i < warm; ++i)
+        for (int a = 0; a < ARMS; ++a) launch(a, dwarm);
+    for (int r = 0; r < ROUNDS; ++r)
+        for (int a = 0; a < ARMS; ++a) {
+            CHECK(hipEventRecord(ev[a][r][0], 0));
+            launch(a, dst[a][r]);
+            CHECK(hipEventRecord(ev[a][r][1], 0));
+        }
+    CHECK(hipDeviceSynchronize());
+    printf("gemm wall: %d K tiles per wave and launch, 256 workgroups x 4 waves, warm-up %d launch pairs (first launches %.2f / %.2f ms)\n", tiles, warm, ms1[0], ms1[1]);
+    float lo[ARMS], hi[ARMS], med[ARMS];
+    for (int r = 0; r < ROUNDS; ++r)
+        for (int a = 0; a < ARMS; ++a) {
+            float ms;
+            CHECK(hipEventElapsedTime(&ms, ev[a][r][0], ev[a][r][1]));
+            const ArmResult res = read_stamps(dst[a][r], ms, tiles);
+            const double flop = (double)WGS * 4 * tiles * 2.0 * 128 * 128 * 64;
+            printf("  round %d  %-9s  wall %8.3f ms  %7.1f TFLOP/s  K tile %7.1f cycles  in-kernel clock %.3f GHz\n", r, names[a], ms, flop / ms / 1e9, res.tile_cycles, res.clock_ghz);
+            if (r == 0) lo[a] = 1e30f, hi[a] = 0.f, med[a] = 0.f;
+            lo[a] = std::min(lo[a], ms), hi[a] = std::max(hi[a], ms), med[a] += ms;
+        }
+    for (int a = 0; a < ARMS; ++a) {
+        med[a] = med[a] - lo[a] - hi[a];  // the middle one of three
+        printf("  %-9s: median %.3f ms, spread between its runs %.2f %%\n", names[a], med[a], 100.f * (hi[a] - lo[a]) / med[a]);
+    }
+    const float spread = std::max((hi[0] - lo[0]) / med[0], (hi[1] - lo[1]) / med[1]), gain = med[0] / med[1] - 1.f;
+    printf("  16x16x32 against 32x32x16 by wall: %+.2f %% (go needs more than %.2f %% = twice the larger spread): %s\n", 100.f * gain, 200.f * spread,
+           gain > 2.f * spread ? "GO" : "NO-GO");
+}
+
 int main(int argc, char** argv) {
     srand(20240607);
-    const int tiles = argc > 1 ? atoi(argv[1]) & ~1 : 40000;  // ~1.5 us per tile: 60 ms per launch
-    if (tiles < 2) {
-        fprintf(stderr, "usage: %s [tiles per launch, even, default 40000]\n", argv[0]);
+    const int tiles = argc > 1 ? atoi(argv[1]) & ~1 : 40000;  // 1 to 1.5 us per tile: 40 to 60 ms per launch
+    const char* what = argc > 2 ? argv[2] : "all";           // "attn": sections a and b, "gemm": section c
+    if (tiles < 2 || (strcmp(what, "all") && strcmp(what, "attn") && strcmp(what, "gemm"))) {
+        fprintf(stderr, "usage: %s [tiles per launch, even, default 40000] [all | attn | gemm]\n", argv[0]);
         return 2;
     }
-    run_bits();
-    run_wall(tiles);
+    if (strcmp(what, "gemm")) {
+        run_bits();
+        run_wall(tiles);
+    }
+    if (strcmp(what, "attn")) run_wall_gemm(tiles);
     return 0;
 }

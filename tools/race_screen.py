@@ -5,7 +5,8 @@ boundaries) and demands BITWISE equal outputs.
   run (GPU box):                python tools/race_screen.py [--no-tokenizer] [--mxfp8-producers-only: the last section alone]
                                                             [--bounded-cp-only: the no-max key-sharded attention section alone]
                                                             [--mfma16-only: the 16x16x32 no-max attention section alone]
-                                                            [--ranges-only: the range-table attention section alone]"""
+                                                            [--ranges-only: the range-table attention section alone]
+                                                            [--gemm-mfma16-only: the deferred GEMM's 16x16x32 body alone]"""
 import ctypes as C
 import math
 import os
@@ -41,7 +42,8 @@ bad = 0
 ONLY_BCP = "--bounded-cp-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded_cp_bf16
 ONLY_W4C = "--mfma16-only" in sys.argv  # run only the section of g3_self_attn_fwd_bounded16_bf16
 ONLY_RNG = "--ranges-only" in sys.argv  # run only the section of g3_self_attn_fwd_ranges_bf16
-ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP or ONLY_W4C or ONLY_RNG  # run only the last section (the launches that emit MXFP8)
+ONLY_G16 = "--gemm-mfma16-only" in sys.argv  # run only the section of the deferred GEMM's 16x16x32 body
+ONLY_MX = "--mxfp8-producers-only" in sys.argv or ONLY_BCP or ONLY_W4C or ONLY_RNG or ONLY_G16  # run only the last section (the launches that emit MXFP8)
 
 
 def both(fn):
@@ -213,6 +215,30 @@ for (M, N, K, epi) in [] if ONLY_MX else [(56320, 4096, 4096, 2), (7040, 12288, 
         report(f"gemm {M}x{N}x{K} epi{epi} pingpong={pp}", x, y)
     del a_, w_, gate, res
 
+# ---- the deferred-epilogue GEMM with its K loop on 16x16x32 MFMAs (gemm_mfma16 = 1: gemm_bf16_nt_w4e16_kernel) at its launch forms: the three epilogue classes,
+# both piece orders, two tiles per workgroup at the minimum of 38 K tiles, 66 carried epilogues in a row on 8 workgroups and a flush behind a carry on 248. Every
+# fragment read lands in registers the quadrant before it multiplied, and the barrier sits between two quadrants: what the jitter stretches
+for (M, N, K, epi, grid) in [] if (ONLY_MX and not ONLY_G16) else [(8192, 4096, 2432, 0, 0), (8192, 4096, 2432, 1, 0), (8192, 4096, 2432, 2, 0), (8448, 4096, 2560, 1, 8),
+                                                                    (8448, 4096, 2560, 2, 248), (56320, 4096, 4096, 2, 0), (16384, 16384, 4096, 1, 0)]:
+    a_ = torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16)
+    w_ = (torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16)
+    gate = torch.randn(2, N, device=dev, generator=g).to(torch.bfloat16)
+    res = torch.randn(M, N, device=dev, generator=g).to(torch.bfloat16)
+    for tf in (0, 1):
+        def run(lib):
+            for opt, val in ((b"gemm_pingpong", 3), (b"gemm_persistent", 0), (b"gemm_deferred", 1), (b"gemm_mfma16", 1), (b"gemm_deferred_grid", grid), (b"gemm_tokens_first", tf)):
+                lib.g3_set_option(opt, val)
+            o = torch.empty(M, N, device=dev, dtype=torch.bfloat16)
+            rc = lib.g3_gemm_bf16_nt(a_.data_ptr(), K, w_.data_ptr(), K, o.data_ptr(), N, M, N, K, epi, gate.data_ptr() if epi == 2 else None, 2, N,
+                                     res.data_ptr() if epi == 2 else None, N, st)
+            assert rc == 0, lib.g3_last_error()
+            lib.g3_set_option(b"gemm_deferred_grid", 0)
+            lib.g3_set_option(b"gemm_tokens_first", 2)
+            return o
+        x, y = both(run)
+        report(f"gemm 16x16x32 body {M}x{N}x{K} epi{epi} grid={grid or 'CUs'} tokens_first={tf}", x, y)
+    del a_, w_, gate, res
+
 # ---- implicit-GEMM convolutions (tokenizer geometries: 1x3x3, causal 3x1x1, strided)
 for (C_in, C_out, T, Hh, Ww, kt, kh, kw, st_, sh, sw) in [] if ONLY_MX else [(128, 256, 5, 48, 64, 1, 3, 3, 1, 1, 1), (256, 256, 6, 40, 48, 3, 1, 1, 1, 1, 1), (128, 128, 5, 48, 64, 1, 3, 3, 1, 2, 2),
                                                            (256, 256, 7, 24, 32, 3, 1, 1, 2, 1, 1)]:
@@ -284,7 +310,7 @@ if "--no-tokenizer" not in sys.argv and not ONLY_MX:
 # ---- range-table self-attention (g3_self_attn_fwd_ranges_bf16): both kernel forms on the three shapes of tests/test_attn_ranges_gpu.py (its hand-made tables:
 # one to three tiles per block; random lists under a head-to-pattern lookup on the 3-D grid; 64 one-tile ranges on the 1-D grid) - the cursor's range changes
 # sit between the statements whose LDS hand-offs the jitter stretches
-if not (ONLY_BCP or ONLY_W4C or "--mxfp8-producers-only" in sys.argv):
+if not (ONLY_BCP or ONLY_W4C or ONLY_G16 or "--mxfp8-producers-only" in sys.argv):
     from tests.test_attn_ranges_gpu import _shape as rng_shape
     for i in (1, 2, 3):
         S_, B_, H_, tab, hp = rng_shape(i)
@@ -308,7 +334,7 @@ if not (ONLY_BCP or ONLY_W4C or "--mxfp8-producers-only" in sys.argv):
 # ---- the producers that emit MXFP8 from their registers (mxfp8_producers = "fused"): the GEMM with MXFP8 output (its K loop carries the jitter; the epilogue
 # transposes through each wave's own LDS slice and quantises across lane quads) and the two LayerNorm forms, plain and with the position embedding
 LN_WAVE_START = int(os.environ.get("G3_LN_WAVE_ROWS", "0"))  # what both libraries start with (csrc/api.hip); restored after each case
-for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG) else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
+for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG or ONLY_G16) else [(14080, 16384, 4096, 1), (7040, 4096, 4096, 0), (513, 1024, 256, 1), (300, 512, 256, 0)]:
     aq, as_ = ops.quant_mxfp8(torch.randn(M, K, device=dev, generator=g).to(torch.bfloat16))
     wq, ws = ops.quant_mxfp8((torch.randn(N, K, device=dev, generator=g) / math.sqrt(K)).to(torch.bfloat16))
 
@@ -322,7 +348,7 @@ for (M, N, K, epi) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG) else [(14080, 163
     a, b = both(run)
     report(f"gemm_mxfp8 with MXFP8 output {M}x{N}x{K} epi{epi}", a, b)
     del aq, as_, wq, ws
-for (T_, Hp, Wp, B_, D_, wave) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG) else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
+for (T_, Hp, Wp, B_, D_, wave) in [] if (ONLY_BCP or ONLY_W4C or ONLY_RNG or ONLY_G16) else [(4, 20, 22, 2, 4096, 1), (4, 20, 22, 2, 4096, 0), (3, 5, 7, 1, 2048, 0)]:
     rows = T_ * Hp * Wp * B_
     x_ = torch.randn(rows, D_, device=dev, generator=g).to(torch.bfloat16)
     pe = (0.3 * torch.randn(T_ * Hp * Wp, D_, device=dev, generator=g)).to(torch.bfloat16)
